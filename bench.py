@@ -2,6 +2,7 @@
 """bench.py - headline benchmark of the MI355X Ed25519 / X25519 engine.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--op all|verify|x25519|sign] [--log2n L]
+                    [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): ed25519 verifies/s and x25519 ops/s at batch 2^20 on 1/2/4/8 MI355X.
 One "step" = one pass of the hot path over the whole synthetic batch, inputs already resident in HBM.
@@ -12,25 +13,32 @@ One "step" = one pass of the hot path over the whole synthetic batch, inputs alr
           rank per GPU, no data-path collective; the step ends with the RCCL all-gather of the
           verdict bytes.  Total work fixed: "strong".  --log2n overrides the per-GPU size
           (then "weak").
-After the verify region the same process times config 3 (2^20 x25519 per GPU) and config 5 (2^20
+
+A plain run sets up, warms up, times exactly K steps, writes the last step's outputs (--dump-outputs DIR:
+DIR/<name>.npy, float32, see dump_outputs) and prints the line: the headline keys, and `outputs_correct`
+(verify: the verdicts equal the constructed ones; x25519 / sign: null, their checks need --full).
+Everything below is measured or checked only with --full.
+
+With --full, after the verify region the same process times config 3 (2^20 x25519 per GPU) and config 5 (2^20
 signs per GPU) with the same step count and reports them under "secondary" (--op all, the default),
 together with the opt-in batch verification on the config's items before corruption.
 
 `--gpus N` without a torch.distributed environment spawns the N ranks itself (a child
 `python -m torch.distributed.run`, started before this process touches the GPU) and relays rank 0's line.
 
-Prints ONE JSON line on rank 0 (see the driver contract), with two extra objects:
+Prints ONE JSON line on rank 0 (see the driver contract); with --full, three extra objects:
+  verdicts      (verify) the SHA-512 of the whole verdict vector, checked against the reference's digest of that batch
   roofline      the verify pass (three kernels; the dominant one, k_verify_main_half, is broken out under
                 "dominant") against the integer-VALU multiply-issue roofline SURVEY 8(d) prescribes for
                 this path, plus the HBM view of the same launch
   cpu_baseline  the reference itself (oracle/_ref, compiled from its own sources) timed on this
                 box's host cores on a bounded sample of the same workload (rank 0; at N > 1 the other ranks
                 sleep in a host-side barrier meanwhile)
-At N = 1 `secondary.verify_host_to_host` is the PCIe-inclusive rate of the same batch through the host-pointer entry
+At N = 1 (--full) `secondary.verify_host_to_host` is the PCIe-inclusive rate of the same batch through the host-pointer entry
 point (for the record; `value` never includes transfers), `secondary.verify_small_calls` the latency of one single-item
 call and of a batch of 256 through the same entry points, and `secondary.verify_sustained` repeats the config-2 pass back to back for --sustained seconds (default 10)
 and reports the rate of the last half with the power and clock rocm-smi shows: the headline region lasts 0.2 s,
-which a power-bound chip runs above its steady-state clock.  At N > 1 `per_rank` breaks the step down by rank
+which a power-bound chip runs above its steady-state clock.  At N > 1 (--full) `per_rank` breaks the step down by rank
 (device, kernel ms, gather ms, wall ms, clock and power, the slowest rank) and `rccl` states what the result gather ran over
 (world size == N, backend, RCCL version, every rank on a device of its own - the run exits non-zero otherwise), so that a
 scaling point can be attributed.
@@ -493,33 +501,59 @@ def all_ranks_agree(flag, world, device):
     return bool(t.item())
 
 
-def measure(op, w, n, steps, warmup, world, device):
+def measure(op, w, n, steps, warmup, world, device, detail=True):
     """warm up, then time `steps` steps of `op` on this rank's n items (plus the result gather);
     -> (elapsed seconds, last output, average kernel-only ms from HIP events on the launch stream,
-        verify's per-kernel phase times or None)"""
+        verify's per-kernel phase times or None, the gathered result, average gather ms).
+    detail=False (a plain run): no HIP events and no phase timing in the steps; kernel and gather ms are None"""
     marks, gathered = [], [None]
 
     def step():
-        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-        e0.record()
+        if detail:
+            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            e0.record()
         out = run_step(op, w)
-        e1.record()
+        if detail:
+            e1.record()
         gathered[0] = gather_results(out, world, everywhere=(op == "verify"))   # the final result gather (RCCL over xGMI)
-        e2.record()
-        marks.append((e0, e1, e2))
+        if detail:
+            e2.record()
+            marks.append((e0, e1, e2))
         return out
 
     for _ in range(warmup):
         step()
     marks.clear()
-    if op == "verify":
+    if detail and op == "verify":
         ed.set_profiling(True)
     elapsed, out = timed_region(step, steps, world, torch.cuda.synchronize, device)
+    if not detail:
+        return elapsed, out, None, None, gathered[0], None
     phases = ed.verify_phase_ms() if op == "verify" else None
     ed.set_profiling(False)
     k_ms = sum(a.elapsed_time(b) for a, b, _ in marks) / len(marks)
     g_ms = sum(b.elapsed_time(c) for _, b, c in marks) / len(marks)       # kernels' end -> gather's end on this rank's stream
     return elapsed, out, k_ms, phases, gathered[0], g_ms
+
+
+DUMP_NAMES = {"verify": "verdicts", "x25519": "x25519_outputs", "sign": "signatures"}
+DUMP_ITEM_BYTES = {"verify": 1, "x25519": 32, "sign": 64}
+DUMP_MAX_BYTES = 32 << 20        # float32 bytes written at most (the largest default output, 2^20 x 64 signature bytes, is 256 MiB)
+DUMP_SEED = 20251016
+
+
+def dump_outputs(path, op, result):
+    """--dump-outputs: what a caller of the timed path received from its last step - the verdict bytes (n,), the x25519
+    outputs (n, 32) or the signatures (n, 64), gathered over the ranks at N > 1 - as <path>/<name>.npy in float32 (byte
+    values 0..255).  When that is more than DUMP_MAX_BYTES, the file holds a fixed sample: the items whose indices a
+    generator seeded with DUMP_SEED draws without replacement, in ascending order - the same items for the same arguments."""
+    width = DUMP_ITEM_BYTES[op]
+    a = result.cpu().numpy().reshape(-1, width)
+    keep = DUMP_MAX_BYTES // (4 * width)
+    if a.shape[0] > keep:
+        a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], keep, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, DUMP_NAMES[op] + ".npy"), (a[:, 0] if width == 1 else a).astype(np.float32))
 
 
 def fixture_check(full, world, n, seed, config):
@@ -598,10 +632,17 @@ def main():
     ap.add_argument("--op", choices=("all", "verify", "x25519", "sign"), default="all")
     ap.add_argument("--log2n", type=int, default=None,
                     help="items per GPU = 2^log2n (default: 2^20 at N = 1; config 4's 2^24 / N verifies at N > 1)")
-    ap.add_argument("--cpu-sample", type=int, default=1 << 18)
+    ap.add_argument("--cpu-sample", type=int, default=1 << 18, help="items of the CPU baseline (--full)")
     ap.add_argument("--sustained", type=float, default=10.0,
-                    help="seconds of back-to-back verify passes for secondary.verify_sustained (N = 1, --op all; 0 = skip)")
+                    help="seconds of back-to-back verify passes for secondary.verify_sustained (N = 1, --op all, --full; 0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last step as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the reference's digest, the CPU baseline, the per-rank breakdown and, with "
+                         "--op all, the secondary ops and configurations")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -650,19 +691,12 @@ def main():
 
     w = make_workload(main_op, n, rank * n, device, seed, config)
     torch.cuda.synchronize()
-    elapsed, out, k_ms, phases, full, g_ms = measure(main_op, w, n, args.steps, args.warmup, world, device)
-    per_rank = per_rank_breakdown(world, rank, args.steps, k_ms, g_ms)
+    elapsed, out, k_ms, phases, full, g_ms = measure(main_op, w, n, args.steps, args.warmup, world, device, detail=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, main_op, full)
     correct = bool(torch.equal(out, w["expect"])) if main_op == "verify" else True
     correct = all_ranks_agree(correct, world, device)
-    pinned = fixture_check(full, world, n, seed, config) if main_op == "verify" and rank == 0 else None
-    if pinned and pinned["matches_reference_digest"] is False:
-        correct = False
-    # the CPU baseline: rank 0 times it on all host cores while the other ranks sleep in a host-side barrier
-    base = cpu_baseline(main_op, w, out, min(args.cpu_sample, n)) if rank == 0 else None
-    host_barrier()
-    correct = correct and (base is None or base["gpu_matches_cpu_on_sample"])
     ms_per_step = elapsed / args.steps * 1e3
-    passes = (n + (1 << 20) - 1) >> 20
     line = {
         "metric": {"verify": "ed25519 verifies/sec", "x25519": "x25519 ops/sec", "sign": "ed25519 signs/sec"}[main_op],
         "value": world * n * args.steps / elapsed, "unit": UNIT[main_op],
@@ -672,17 +706,28 @@ def main():
         "config": {"workload": f"{what}, " + ("x25519 variable-base" if main_op == "x25519" else f"ed25519 {main_op}"),
                    "msg_len": 32 if main_op != "x25519" else None, "items_per_gpu": n, "total_items": world * n,
                    "parallelism": f"shard{world}+allgather" if world > 1 else "single"},
-        "outputs_correct": correct, "verdicts": pinned,
-        "roofline": roofline_of(main_op, n, k_ms, phases, ms_per_step, passes), "cpu_baseline": base,
+        "outputs_correct": correct if main_op == "verify" or args.full else None,
     }
-    if per_rank:
-        line["per_rank"] = per_rank
-    if world > 1:
-        line["rccl"] = collective_facts(world, backend, os.environ.get("EDDSA_BENCH_SHARE_GPU") == "1")
-        if line["rccl"]["world"] != args.gpus:
-            raise SystemExit(f"bench.py: the process group has {line['rccl']['world']} ranks, --gpus says {args.gpus}")
+    if args.full:
+        per_rank = per_rank_breakdown(world, rank, args.steps, k_ms, g_ms)
+        pinned = fixture_check(full, world, n, seed, config) if main_op == "verify" and rank == 0 else None
+        if pinned and pinned["matches_reference_digest"] is False:
+            correct = False
+        # the CPU baseline: rank 0 times it on all host cores while the other ranks sleep in a host-side barrier
+        base = cpu_baseline(main_op, w, out, min(args.cpu_sample, n)) if rank == 0 else None
+        host_barrier()
+        correct = correct and (base is None or base["gpu_matches_cpu_on_sample"])
+        passes = (n + (1 << 20) - 1) >> 20
+        line.update({"outputs_correct": correct, "verdicts": pinned,
+                     "roofline": roofline_of(main_op, n, k_ms, phases, ms_per_step, passes), "cpu_baseline": base})
+        if per_rank:
+            line["per_rank"] = per_rank
+        if world > 1:
+            line["rccl"] = collective_facts(world, backend, os.environ.get("EDDSA_BENCH_SHARE_GPU") == "1")
+            if line["rccl"]["world"] != args.gpus:
+                raise SystemExit(f"bench.py: the process group has {line['rccl']['world']} ranks, --gpus says {args.gpus}")
     secondary = {}
-    if args.op == "all" and main_op == "verify":
+    if args.full and args.op == "all" and main_op == "verify":
         # SURVEY 8(f)-3, opt-in: the same items BEFORE corruption through ed25519_verify_batch_rlc (groups of 8192
         # checked by one random linear combination; a group that fails falls back to the per-item kernels)
         m = min(n, 1 << 20)
@@ -708,7 +753,7 @@ def main():
             "items_per_gpu": m, "stats": st, "outputs_correct": good,
             "note": "not the headline: verdicts equal the per-item path's, see include/eddsa_amd.h for the caveat; "
                     "time of this rank (no gather)"}
-    if args.op == "all" and main_op == "verify" and world == 1:
+    if args.full and args.op == "all" and main_op == "verify" and world == 1:
         # PCIe-inclusive, for the record only (never `value`): the same batch from ordinary host memory to host memory through
         # the host-pointer entry point (staging, three lanes: libeddsa_amd/csrc/host_pipe.c)
         m = min(n, 1 << 20)
@@ -749,17 +794,17 @@ def main():
             "metric": "latency of host-pointer calls, one caller in a loop", "single_ed25519_verify_ms": t_one * 1e3,
             "verify_batch_256_valid_ms": t_256 * 1e3, "outputs_correct": good,
             "note": "concurrent single-item calls are merged into one launch (tests/c/threaded_callers.c measures that)"}
-    if args.op == "all" and main_op == "verify" and world == 1:
+    if args.full and args.op == "all" and main_op == "verify" and world == 1:
         secondary["verify_garbage_keys"] = garbage_keys(w, min(n, 1 << 20), args.steps, device)
         correct = correct and secondary["verify_garbage_keys"]["outputs_correct"]
         secondary["verify_ragged_messages"] = ragged_messages(max(2, args.steps // 2), device)
         correct = correct and secondary["verify_ragged_messages"]["outputs_correct"]
-    if args.op == "all" and main_op == "verify" and world == 1 and args.sustained > 0:
+    if args.full and args.op == "all" and main_op == "verify" and world == 1 and args.sustained > 0:
         secondary["verify_sustained"] = sustained_verify(w, n, args.sustained, local, line["value"])
         correct = correct and secondary["verify_sustained"]["outputs_correct"]
     del w, out, full
 
-    if args.op == "all":                                # the rest of BASELINE's metric, same process, same step count
+    if args.full and args.op == "all":                  # the rest of BASELINE's metric, same process, same step count
         for op in ("x25519", "sign"):
             w2 = make_workload(op, n2, rank * n2, device)
             torch.cuda.synchronize()

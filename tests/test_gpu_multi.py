@@ -97,7 +97,7 @@ def test_bench_spawns_its_own_ranks_for_config4(engine, golden):
     """the bare command `python bench.py --gpus 2` (no launcher): bench.py starts the two ranks itself and
     runs config 4 - 2^24 verifies in total, 2^23 per rank - here with both ranks on the box's single GPU
     and gloo standing in for RCCL; the gathered verdict vector hashes to the reference's digest"""
-    d = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--op", "verify"],
+    d = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--op", "verify", "--full"],
                {"EDDSA_BENCH_SHARE_GPU": "1", "EDDSA_BENCH_BACKEND": "gloo"})
     v = golden("batch_digests.json")["verify_2^24"]
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["outputs_correct"] is True
@@ -113,9 +113,9 @@ def test_bench_spawns_its_own_ranks_for_config4(engine, golden):
 
 
 def test_bench_default_line_carries_the_whole_metric(engine, golden):
-    """`python bench.py` at N = 1: config 2 verifies as `value`, x25519 and sign under `secondary`, each with
+    """`python bench.py --full` at N = 1: config 2 verifies as `value`, x25519 and sign under `secondary`, each with
     its own roofline fraction and CPU baseline, the verdict digest equal to the reference's"""
-    d = _bench(["--steps", "2", "--warmup", "1", "--cpu-sample", "4096", "--sustained", "2"])
+    d = _bench(["--steps", "2", "--warmup", "1", "--cpu-sample", "4096", "--sustained", "2", "--full"])
     assert d["n_gpus"] == 1 and d["outputs_correct"] is True and d["metric"] == "ed25519 verifies/sec"
     assert d["verdicts"]["verdicts_sha512"] == golden("batch_digests.json")["verify_2^20"]["verdicts_sha512"]
     assert d["verdicts"]["matches_reference_digest"] is True

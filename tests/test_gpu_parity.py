@@ -770,7 +770,7 @@ def _bench_line(args, env_extra=None, launcher=None):
 @pytest.mark.parametrize("op", ["verify", "x25519", "sign"])
 def test_bench_contract_single_gpu(engine, op):
     """bench.py's line carries the driver's keys plus roofline and cpu_baseline, and checks its outputs"""
-    d = _bench_line(["--op", op, "--steps", "2", "--warmup", "1", "--log2n", "14", "--cpu-sample", "2048"])
+    d = _bench_line(["--op", op, "--steps", "2", "--warmup", "1", "--log2n", "14", "--cpu-sample", "2048", "--full"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -780,10 +780,37 @@ def test_bench_contract_single_gpu(engine, op):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("op", ["verify", "x25519", "sign"])
+def test_bench_plain_line_and_dumped_outputs(engine, oracle, op, tmp_path):
+    """a plain run (no --full): the headline keys only, exactly --steps timed steps, and --dump-outputs writes what the last
+    step returned - the oracle's bytes on the same seeded inputs"""
+    import workload
+    n = 1 << 14
+    d = _bench_line(["--op", op, "--steps", "3", "--warmup", "1", "--log2n", "14", "--dump-outputs", str(tmp_path)])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert not {"roofline", "cpu_baseline", "verdicts", "secondary"} & set(d)
+    assert d["steps"] == 3 and d["outputs_correct"] is (True if op == "verify" else None)
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - n) < 1e-6 * n            # value = items / (ms_per_step)
+    if op == "verify":
+        sk, msg = workload.sign_inputs(n, seed=1, config=2)
+        pk = oracle.genpub_batch(sk)
+        want = workload.corrupt_for_verify(oracle.sign_batch(sk, pk, msg, 32), pk, msg)
+        name = "verdicts"
+    elif op == "x25519":
+        want, name = oracle.x25519_batch(*workload.x25519_inputs(n)), "x25519_outputs"
+    else:
+        sk, msg = workload.sign_inputs(n)
+        want, name = oracle.sign_batch(sk, oracle.genpub_batch(sk), msg, 32), "signatures"
+    got = np.load(tmp_path / (name + ".npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, want.astype(np.float32))
+
+
+@pytest.mark.gpu
 def test_bench_two_ranks_on_one_gpu(engine):
     """the N > 1 path of bench.py (shards, gather, max-over-ranks timing) launched exactly as the driver
     launches it, with the two ranks sharing the box's single GPU and gloo standing in for RCCL"""
-    d = _bench_line(["--gpus", "2", "--steps", "2", "--warmup", "1", "--log2n", "14"],
+    d = _bench_line(["--gpus", "2", "--steps", "2", "--warmup", "1", "--log2n", "14", "--full"],
                     {"EDDSA_BENCH_SHARE_GPU": "1", "EDDSA_BENCH_BACKEND": "gloo"}, launcher=2)
     assert d["n_gpus"] == 2 and d["outputs_correct"] is True and d["scaling"] == "weak"
     assert d["config"]["parallelism"] == "shard2+allgather"
