@@ -397,6 +397,52 @@ def _run_32(fn_host, fn_dev, what, inputs, out_width, n_from):
     return out
 
 
+def _host_msgs(msgs, msg_off, msg_len, n):
+    msgs = _as_np(msgs, 0, "msgs")
+    _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, False)
+    if off is not None:
+        off = np.ascontiguousarray(np.asarray(off, dtype=np.uint64))
+        if off.size != n + 1 or (n and int(off[-1]) > msgs.size):
+            raise ValueError("msg_off: expected n+1 offsets within msgs")
+    return msgs, off, mlen
+
+
+def _run_msgs(fn_host, fn_dev, what, first, first_w, first_name, pubs, msgs, msg_off, msg_len, out_shape, stats=None,
+              msgs_first=False):
+    """common driver for the calls that carry messages: `first` (sigs or secs: first_w bytes per item), pubs and msgs
+    -> (n,) + out_shape uint8.  fn_dev None: host pointers only.  stats (None: the C function takes no statistics): true
+    -> (output, the four counters); false on the device path: NULL is passed, nothing is counted.  msgs_first: the host path
+    looks at msgs before it compares the batch sizes (which complaint a doubly wrong call gets)."""
+    lib = library()
+    if fn_dev and _is_torch(first):
+        import torch
+        first = _torch_check(first, first_w, first_name); pubs = _torch_check(pubs, 32, "pubs")
+        msgs = _torch_check(msgs, 0, "msgs")
+        n = first.numel() // first_w
+        if pubs.numel() // 32 != n:
+            raise ValueError(f"{what}: {first_name} and pubs disagree on the batch size")
+        _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, True)
+        _torch_off_check(off, n)
+        out = torch.empty((n,) + out_shape, dtype=torch.uint8, device=first.device)
+        counts = torch.zeros((4,), dtype=torch.int32, device=first.device) if stats else None
+        args = [out] + ([counts] if stats is not None else []) + [first, pubs, msgs, off]
+        args = [_c_ptr(t.data_ptr()) if t is not None else None for t in args] + [_c_size(mlen), _c_size(n), _stream()]
+        _check(getattr(lib, fn_dev)(*args), what)
+        return (out, tuple(int(x) for x in counts.cpu())) if stats else out
+    first = _as_np(first, first_w, first_name); pubs = _as_np(pubs, 32, "pubs")
+    if msgs_first:
+        msgs = _as_np(msgs, 0, "msgs")
+    n = first.size // first_w
+    if pubs.size // 32 != n:
+        raise ValueError(f"{what}: {first_name} and pubs disagree on the batch size")
+    msgs, off, mlen = _host_msgs(msgs, msg_off, msg_len, n)
+    out = np.zeros((n,) + out_shape, dtype=np.uint8)
+    counts = (ctypes.c_uint32 * 4)()
+    args = [_np_ptr(out)] + ([counts] if stats is not None else []) + [_np_ptr(first), _np_ptr(pubs), _np_ptr(msgs)]
+    _check(getattr(lib, fn_host)(*args, _np_ptr(off) if off is not None else None, _c_size(mlen), _c_size(n)), what)
+    return (out, tuple(int(x) for x in counts)) if stats else out
+
+
 # ---------------------------------------------------------------------------------------------
 # batched entry points (include/eddsa_amd.h)
 # ---------------------------------------------------------------------------------------------
@@ -436,35 +482,8 @@ def ed25519_verify_batch(sigs, pubs, msgs, msg_off=None, msg_len=None):
 
     msgs is the concatenation of all messages; either every message has msg_len bytes
     (default: len(msgs) / n) or msg_off[0..n] (uint64) gives the ragged boundaries."""
-    lib = library()
-    if _is_torch(sigs):
-        import torch
-        sigs = _torch_check(sigs, 64, "sigs"); pubs = _torch_check(pubs, 32, "pubs")
-        msgs = _torch_check(msgs, 0, "msgs")
-        n = sigs.numel() // 64
-        if pubs.numel() // 32 != n:
-            raise ValueError("ed25519_verify_batch: sigs and pubs disagree on the batch size")
-        _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, True)
-        _torch_off_check(off, n)
-        ok = torch.empty((n,), dtype=torch.uint8, device=sigs.device)
-        _check(lib.ed25519_verify_batch_dev(_c_ptr(ok.data_ptr()), _c_ptr(sigs.data_ptr()), _c_ptr(pubs.data_ptr()),
-                                            _c_ptr(msgs.data_ptr()), _c_ptr(off.data_ptr()) if off is not None else None,
-                                            _c_size(mlen), _c_size(n), _stream()), "ed25519_verify_batch")
-        return ok
-    sigs = _as_np(sigs, 64, "sigs"); pubs = _as_np(pubs, 32, "pubs"); msgs = _as_np(msgs, 0, "msgs")
-    n = sigs.size // 64
-    if pubs.size // 32 != n:
-        raise ValueError("ed25519_verify_batch: sigs and pubs disagree on the batch size")
-    _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, False)
-    if off is not None:
-        off = np.ascontiguousarray(np.asarray(off, dtype=np.uint64))
-        if off.size != n + 1 or (n and int(off[-1]) > msgs.size):
-            raise ValueError("msg_off: expected n+1 offsets within msgs")
-    ok = np.zeros((n,), dtype=np.uint8)
-    _check(lib.ed25519_verify_batch(_np_ptr(ok), _np_ptr(sigs), _np_ptr(pubs), _np_ptr(msgs),
-                                    _np_ptr(off) if off is not None else None, _c_size(mlen), _c_size(n)),
-           "ed25519_verify_batch")
-    return ok
+    return _run_msgs("ed25519_verify_batch", "ed25519_verify_batch_dev", "ed25519_verify_batch",
+                     sigs, 64, "sigs", pubs, msgs, msg_off, msg_len, (), msgs_first=True)
 
 
 def ed25519_verify_batch_rlc(sigs, pubs, msgs, msg_off=None, msg_len=None, return_stats=False):
@@ -472,34 +491,8 @@ def ed25519_verify_batch_rlc(sigs, pubs, msgs, msg_off=None, msg_len=None, retur
     lib/ed25519-sha512.c:13-14): same arguments and verdicts as ed25519_verify_batch, groups that do not
     pass fall back to the per-item kernels.  return_stats=True -> (ok, (items decided by the combination,
     items decided per item, groups sent to the per-item kernels, groups decided by the combination))."""
-    lib = library()
-    if _is_torch(sigs):
-        import torch
-        sigs = _torch_check(sigs, 64, "sigs"); pubs = _torch_check(pubs, 32, "pubs")
-        msgs = _torch_check(msgs, 0, "msgs")
-        n = sigs.numel() // 64
-        if pubs.numel() // 32 != n:
-            raise ValueError("ed25519_verify_batch_rlc: sigs and pubs disagree on the batch size")
-        _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, True)
-        _torch_off_check(off, n)
-        ok = torch.empty((n,), dtype=torch.uint8, device=sigs.device)
-        stats = torch.zeros((4,), dtype=torch.int32, device=sigs.device) if return_stats else None   # (NULL: not counted)
-        _check(lib.ed25519_verify_batch_rlc_dev(_c_ptr(ok.data_ptr()), _c_ptr(stats.data_ptr()) if return_stats else None, _c_ptr(sigs.data_ptr()),
-                                                _c_ptr(pubs.data_ptr()), _c_ptr(msgs.data_ptr()),
-                                                _c_ptr(off.data_ptr()) if off is not None else None,
-                                                _c_size(mlen), _c_size(n), _stream()), "ed25519_verify_batch_rlc")
-        return (ok, tuple(int(x) for x in stats.cpu())) if return_stats else ok
-    sigs = _as_np(sigs, 64, "sigs"); pubs = _as_np(pubs, 32, "pubs")
-    n = sigs.size // 64
-    if pubs.size // 32 != n:
-        raise ValueError("ed25519_verify_batch_rlc: sigs and pubs disagree on the batch size")
-    msgs, off, mlen = _host_msgs(msgs, msg_off, msg_len, n)
-    ok = np.zeros((n,), dtype=np.uint8)
-    stats = (ctypes.c_uint32 * 4)()
-    _check(lib.ed25519_verify_batch_rlc(_np_ptr(ok), stats, _np_ptr(sigs), _np_ptr(pubs), _np_ptr(msgs),
-                                        _np_ptr(off) if off is not None else None, _c_size(mlen), _c_size(n)),
-           "ed25519_verify_batch_rlc")
-    return (ok, tuple(int(x) for x in stats)) if return_stats else ok
+    return _run_msgs("ed25519_verify_batch_rlc", "ed25519_verify_batch_rlc_dev", "ed25519_verify_batch_rlc",
+                     sigs, 64, "sigs", pubs, msgs, msg_off, msg_len, (), stats=bool(return_stats))
 
 
 def ed25519_verify_records(records, sig_off, pub_off, msg_off, msg_len):
@@ -529,76 +522,23 @@ def ed25519_verify_records(records, sig_off, pub_off, msg_off, msg_len):
 
 def ed25519_sign_batch(secs, pubs, msgs, msg_off=None, msg_len=None):
     """loop of ed25519_sign (reference lib/eddsa.h:47) -> (n, 64) uint8"""
-    lib = library()
-    if _is_torch(secs):
-        import torch
-        secs = _torch_check(secs, 32, "secs"); pubs = _torch_check(pubs, 32, "pubs")
-        msgs = _torch_check(msgs, 0, "msgs")
-        n = secs.numel() // 32
-        if pubs.numel() // 32 != n:
-            raise ValueError("ed25519_sign_batch: secs and pubs disagree on the batch size")
-        _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, True)
-        _torch_off_check(off, n)
-        sig = torch.empty((n, 64), dtype=torch.uint8, device=secs.device)
-        _check(lib.ed25519_sign_batch_dev(_c_ptr(sig.data_ptr()), _c_ptr(secs.data_ptr()), _c_ptr(pubs.data_ptr()),
-                                          _c_ptr(msgs.data_ptr()), _c_ptr(off.data_ptr()) if off is not None else None,
-                                          _c_size(mlen), _c_size(n), _stream()), "ed25519_sign_batch")
-        return sig
-    secs = _as_np(secs, 32, "secs"); pubs = _as_np(pubs, 32, "pubs"); msgs = _as_np(msgs, 0, "msgs")
-    n = secs.size // 32
-    if pubs.size // 32 != n:
-        raise ValueError("ed25519_sign_batch: secs and pubs disagree on the batch size")
-    _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, False)
-    if off is not None:
-        off = np.ascontiguousarray(np.asarray(off, dtype=np.uint64))
-        if off.size != n + 1 or (n and int(off[-1]) > msgs.size):
-            raise ValueError("msg_off: expected n+1 offsets within msgs")
-    sig = np.zeros((n, 64), dtype=np.uint8)
-    _check(lib.ed25519_sign_batch(_np_ptr(sig), _np_ptr(secs), _np_ptr(pubs), _np_ptr(msgs),
-                                  _np_ptr(off) if off is not None else None, _c_size(mlen), _c_size(n)),
-           "ed25519_sign_batch")
-    return sig
+    return _run_msgs("ed25519_sign_batch", "ed25519_sign_batch_dev", "ed25519_sign_batch",
+                     secs, 32, "secs", pubs, msgs, msg_off, msg_len, (64,), msgs_first=True)
 
 
 # ---------------------------------------------------------------------------------------------
 # several devices in one process (include/eddsa_amd.h: *_multi), after init_devices()
 # ---------------------------------------------------------------------------------------------
 
-def _host_msgs(msgs, msg_off, msg_len, n):
-    msgs = _as_np(msgs, 0, "msgs")
-    _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, False)
-    if off is not None:
-        off = np.ascontiguousarray(np.asarray(off, dtype=np.uint64))
-        if off.size != n + 1 or (n and int(off[-1]) > msgs.size):
-            raise ValueError("msg_off: expected n+1 offsets within msgs")
-    return msgs, off, mlen
-
-
 def ed25519_verify_batch_multi(sigs, pubs, msgs, msg_off=None, msg_len=None):
     """ed25519_verify_batch over the device set: contiguous shards, one host thread per device"""
-    sigs = _as_np(sigs, 64, "sigs"); pubs = _as_np(pubs, 32, "pubs")
-    n = sigs.size // 64
-    if pubs.size // 32 != n:
-        raise ValueError("ed25519_verify_batch_multi: sigs and pubs disagree on the batch size")
-    msgs, off, mlen = _host_msgs(msgs, msg_off, msg_len, n)
-    ok = np.zeros((n,), dtype=np.uint8)
-    _check(library().ed25519_verify_batch_multi(_np_ptr(ok), _np_ptr(sigs), _np_ptr(pubs), _np_ptr(msgs),
-                                                _np_ptr(off) if off is not None else None, _c_size(mlen), _c_size(n)),
-           "ed25519_verify_batch_multi")
-    return ok
+    return _run_msgs("ed25519_verify_batch_multi", None, "ed25519_verify_batch_multi",
+                     sigs, 64, "sigs", pubs, msgs, msg_off, msg_len, ())
 
 
 def ed25519_sign_batch_multi(secs, pubs, msgs, msg_off=None, msg_len=None):
-    secs = _as_np(secs, 32, "secs"); pubs = _as_np(pubs, 32, "pubs")
-    n = secs.size // 32
-    if pubs.size // 32 != n:
-        raise ValueError("ed25519_sign_batch_multi: secs and pubs disagree on the batch size")
-    msgs, off, mlen = _host_msgs(msgs, msg_off, msg_len, n)
-    sig = np.zeros((n, 64), dtype=np.uint8)
-    _check(library().ed25519_sign_batch_multi(_np_ptr(sig), _np_ptr(secs), _np_ptr(pubs), _np_ptr(msgs),
-                                              _np_ptr(off) if off is not None else None, _c_size(mlen), _c_size(n)),
-           "ed25519_sign_batch_multi")
-    return sig
+    return _run_msgs("ed25519_sign_batch_multi", None, "ed25519_sign_batch_multi",
+                     secs, 32, "secs", pubs, msgs, msg_off, msg_len, (64,))
 
 
 def x25519_batch_multi(scalars, points):
@@ -653,80 +593,38 @@ def _b(x, n, name):
     return x
 
 
-def ed25519_genpub(sec):
-    out = ctypes.create_string_buffer(32)
-    library().ed25519_genpub(out, _b(sec, 32, "sec"))
-    return out.raw
+def _single(name, out_bytes, *fixed, data=False):
+    """the eddsa.h function `name`: fixed = (argument, bytes) of each fixed-width input; data: a message of any length
+    follows them; out_bytes bytes come back (0: the C function's bool)"""
+    names = [nm for nm, _ in fixed] + ["data"] * data
+
+    def fn(*args, **kw):
+        given = dict(zip(names, args), **kw)
+        if len(args) > len(names) or len(given) != len(args) + len(kw) or set(given) != set(names):
+            raise TypeError(f"{name}({', '.join(names)}): got {len(args)} positional arguments and keywords {sorted(kw)}")
+        tail = [bytes(given["data"])] if data else []
+        f = getattr(library(), name)
+        cargs = [_b(given[nm], w, nm) for nm, w in fixed] + tail + [_c_size(len(d)) for d in tail]
+        if not out_bytes:
+            return bool(f(*cargs))
+        out = ctypes.create_string_buffer(out_bytes)
+        f(out, *cargs)
+        return out.raw
+    fn.__name__ = fn.__qualname__ = name
+    return fn
 
 
-def ed25519_sign(sec, pub, data):
-    out = ctypes.create_string_buffer(64)
-    data = bytes(data)
-    library().ed25519_sign(out, _b(sec, 32, "sec"), _b(pub, 32, "pub"), data, _c_size(len(data)))
-    return out.raw
-
-
-def ed25519_verify(sig, pub, data):
-    data = bytes(data)
-    return bool(library().ed25519_verify(_b(sig, 64, "sig"), _b(pub, 32, "pub"), data, _c_size(len(data))))
-
-
-def x25519_base(scalar):
-    out = ctypes.create_string_buffer(32)
-    library().x25519_base(out, _b(scalar, 32, "scalar"))
-    return out.raw
-
-
-def x25519(scalar, point):
-    out = ctypes.create_string_buffer(32)
-    library().x25519(out, _b(scalar, 32, "scalar"), _b(point, 32, "point"))
-    return out.raw
-
-
-def pk_ed25519_to_x25519(pub):
-    out = ctypes.create_string_buffer(32)
-    library().pk_ed25519_to_x25519(out, _b(pub, 32, "pub"))
-    return out.raw
-
-
-def sk_ed25519_to_x25519(sec):
-    out = ctypes.create_string_buffer(32)
-    library().sk_ed25519_to_x25519(out, _b(sec, 32, "sec"))
-    return out.raw
-
-
+ed25519_genpub = _single("ed25519_genpub", 32, ("sec", 32))
+ed25519_sign = _single("ed25519_sign", 64, ("sec", 32), ("pub", 32), data=True)
+ed25519_verify = _single("ed25519_verify", 0, ("sig", 64), ("pub", 32), data=True)
+x25519_base = _single("x25519_base", 32, ("scalar", 32))
+x25519 = _single("x25519", 32, ("scalar", 32), ("point", 32))
+pk_ed25519_to_x25519 = _single("pk_ed25519_to_x25519", 32, ("pub", 32))
+sk_ed25519_to_x25519 = _single("sk_ed25519_to_x25519", 32, ("sec", 32))
 # obsolete names kept by the reference (lib/eddsa.h:92-113)
-def eddsa_genpub(sec):
-    out = ctypes.create_string_buffer(32)
-    library().eddsa_genpub(out, _b(sec, 32, "sec"))
-    return out.raw
-
-
-def eddsa_sign(sec, pub, data):
-    out = ctypes.create_string_buffer(64)
-    data = bytes(data)
-    library().eddsa_sign(out, _b(sec, 32, "sec"), _b(pub, 32, "pub"), data, _c_size(len(data)))
-    return out.raw
-
-
-def eddsa_verify(sig, pub, data):
-    data = bytes(data)
-    return bool(library().eddsa_verify(_b(sig, 64, "sig"), _b(pub, 32, "pub"), data, _c_size(len(data))))
-
-
-def DH(sec, point):
-    out = ctypes.create_string_buffer(32)
-    library().DH(out, _b(sec, 32, "sec"), _b(point, 32, "point"))
-    return out.raw
-
-
-def eddsa_pk_eddsa_to_dh(pub):
-    out = ctypes.create_string_buffer(32)
-    library().eddsa_pk_eddsa_to_dh(out, _b(pub, 32, "pub"))
-    return out.raw
-
-
-def eddsa_sk_eddsa_to_dh(sec):
-    out = ctypes.create_string_buffer(32)
-    library().eddsa_sk_eddsa_to_dh(out, _b(sec, 32, "sec"))
-    return out.raw
+eddsa_genpub = _single("eddsa_genpub", 32, ("sec", 32))
+eddsa_sign = _single("eddsa_sign", 64, ("sec", 32), ("pub", 32), data=True)
+eddsa_verify = _single("eddsa_verify", 0, ("sig", 64), ("pub", 32), data=True)
+DH = _single("DH", 32, ("sec", 32), ("point", 32))
+eddsa_pk_eddsa_to_dh = _single("eddsa_pk_eddsa_to_dh", 32, ("pub", 32))
+eddsa_sk_eddsa_to_dh = _single("eddsa_sk_eddsa_to_dh", 32, ("sec", 32))

@@ -62,14 +62,6 @@ void hip_forget_error(void)
     (void)hipGetLastError();               /* the caller has handled the answer it stands for */
 }
 
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-int eddsa_amd_debug_teardown_errors(int *first_hip_error)
-{
-    if (first_hip_error) *first_hip_error = __atomic_load_n(&g_teardown.first, __ATOMIC_ACQUIRE);
-    return __atomic_load_n(&g_teardown.count, __ATOMIC_ACQUIRE);
-}
-#endif
-
 /* ------------------------------------------------------------------------------------------
  * engines
  * ---------------------------------------------------------------------------------------- */
@@ -104,10 +96,14 @@ static void ws_release(struct vslot *v)
     v->ws.flags = NULL;
 }
 
+/* bytes of the two secret-bearing buffers of a fixed-base workspace of `cap` items */
+static size_t fws_acc_bytes(size_t cap) { return cap * ACC_WORDS * sizeof(uint32_t); }
+static size_t fws_aux_bytes(size_t cap) { return cap * 16 * sizeof(uint32_t); }
+
 static void fws_release(struct vslot *v)
 {
-    wipe_free(v->fws.acc, v->fws.capacity * ACC_WORDS * sizeof(uint32_t));
-    wipe_free(v->fws.aux, v->fws.capacity * 16 * sizeof(uint32_t));
+    wipe_free(v->fws.acc, fws_acc_bytes(v->fws.capacity));
+    wipe_free(v->fws.aux, fws_aux_bytes(v->fws.capacity));
     if (v->fws.tiles) HIP_NOTE(hipFree(v->fws.tiles));
     if (v->fws.perm) HIP_NOTE(hipFree(v->fws.perm));
     if (v->fws.lenbins) HIP_NOTE(hipFree(v->fws.lenbins));
@@ -135,12 +131,12 @@ static int fws_reserve(struct vslot *v, size_t items, hipStream_t st)
     if (cap <= v->fws.capacity) return 0;
     TRY(hipEventSynchronize(v->free));
     fws_release(v);
-    TRY(hipMalloc((void **)&v->fws.acc, cap * ACC_WORDS * sizeof(uint32_t)));
-    TRY(hipMalloc((void **)&v->fws.aux, cap * 16 * sizeof(uint32_t)));
+    TRY(hipMalloc((void **)&v->fws.acc, fws_acc_bytes(cap)));
+    TRY(hipMalloc((void **)&v->fws.aux, fws_aux_bytes(cap)));
     /* recycled memory: start clean.  On the pass's own stream: a hipMemset on the null stream is not ordered
      * with the kernels of a non-blocking stream and could land after their first stores */
-    TRY(hipMemsetAsync(v->fws.acc, 0, cap * ACC_WORDS * sizeof(uint32_t), st));
-    TRY(hipMemsetAsync(v->fws.aux, 0, cap * 16 * sizeof(uint32_t), st));
+    TRY(hipMemsetAsync(v->fws.acc, 0, fws_acc_bytes(cap), st));
+    TRY(hipMemsetAsync(v->fws.aux, 0, fws_aux_bytes(cap), st));
     TRY(hipMalloc((void **)&v->fws.perm, cap * sizeof(uint32_t)));
     TRY(hipMalloc((void **)&v->fws.lenbins, 2 * EDK_LEN_BINS * sizeof(uint32_t)));
     TRY(hipMalloc((void **)&v->fws.tiles, 256));
@@ -398,115 +394,8 @@ void eddsa_amd_shutdown(void)
 }
 
 /* ------------------------------------------------------------------------------------------
- * the test surface (include/eddsa_amd_debug.h): inert unless armed
+ * settings
  * ---------------------------------------------------------------------------------------- */
-
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-int eddsa_amd_debug_init(int device, unsigned flags)
-{
-    const int rc = eddsa_amd_init(device);
-    if (rc) return rc;
-    __atomic_store_n(&g_hooks_armed, (flags & EDDSA_AMD_TEST_HOOKS) != 0, __ATOMIC_RELEASE);
-    edk_debug_counting((flags & EDDSA_AMD_TEST_HOOKS) != 0);
-    if (!(flags & EDDSA_AMD_TEST_HOOKS)) (void)edk_debug_fail_in(0);
-    return 0;
-}
-#endif
-
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-int eddsa_amd_debug_fail_hip_call(int nth)
-{
-    if (!__atomic_load_n(&g_hooks_armed, __ATOMIC_ACQUIRE)) return EDDSA_AMD_HOOKS_OFF;
-    (void)edk_debug_fail_in(nth < 0 ? 0 : nth);
-    return 0;
-}
-#endif
-
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-int eddsa_amd_debug_hip_calls(void)
-{
-    return edk_debug_fail_in(-1);
-}
-#endif
-
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-int eddsa_amd_debug_withhold_handoff(int tile_plus_1)
-{
-    struct call c;
-    int rc, gave_up = 0;
-    if (!__atomic_load_n(&g_hooks_armed, __ATOMIC_ACQUIRE)) return EDDSA_AMD_HOOKS_OFF;
-    if ((rc = enter(&c, -1))) return rc;
-    pthread_mutex_lock(&c.e->lk);
-    TRY(hipDeviceSynchronize());
-    for (int i = 0; i < VERIFY_SLOTS; i++) {
-        const uint32_t w = tile_plus_1 > 0 ? (uint32_t)tile_plus_1 : 0u;
-        if (c.e->vs[i].ws.offcount) TRY(hipMemcpy(c.e->vs[i].ws.offcount + EDK_WITHHOLD_WORD, &w, sizeof(w), hipMemcpyHostToDevice));
-        if (c.e->vs[i].rws.base) {
-            uint32_t *hook = (uint32_t *)((char *)c.e->vs[i].rws.base + edk_rlc_hook_offset(c.e->vs[i].rws.capacity));
-            uint32_t two[2] = { 0, 0 };
-            TRY(hipMemcpy(two, hook, sizeof(two), hipMemcpyDeviceToHost));
-            gave_up += (int)two[1];
-            two[0] = w; two[1] = 0;
-            TRY(hipMemcpy(hook, two, sizeof(two), hipMemcpyHostToDevice));
-        }
-    }
-    rc = gave_up;
-out:
-    pthread_mutex_unlock(&c.e->lk);
-    leave(&c);
-    return rc;
-}
-#endif
-
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-int eddsa_amd_dump_tables(uint32_t *base16_words, uint32_t *comb_words)
-{
-    struct call c;
-    int rc = enter(&c, -1);
-    if (rc) return rc;
-    TRY(hipMemcpy(base16_words, c.e->base16, (size_t)TABLE_BASE16_ENTRIES * TABLE_ENTRY_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    TRY(hipMemcpy(comb_words, c.e->comb, TABLE_COMB_ENTRIES * TABLE_ENTRY_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
-out:
-    leave(&c);
-    return rc;
-}
-#endif
-
-/* Which evaluation ed25519_verify* uses (same verdicts; a measurement and test aid).  0 (default): half-length
- * scalars (csrc/halve.h), four lanes per item up to 2^15 items and one above; 1: full-length windows always;
- * 2: half-length scalars with one lane per item always. */
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-void eddsa_amd_set_verify_algo(int algo)
-{
-    pthread_rwlock_wrlock(&g_table);
-    g_verify_algo = algo >= 1 && algo <= 3 ? algo : 0;
-    pthread_rwlock_unlock(&g_table);
-}
-#endif
-
-/* diagnostic for the tests: how many half-length pairs the exact integer check (csrc/lanes.h: verify_half_scalars_lane)
- * has refused on the default device since its workspaces were allocated.  Waits for the device.  Expected: 0. */
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-int eddsa_amd_halve_rejected(uint64_t *count)
-{
-    struct call c;
-    int rc = enter(&c, -1);
-    if (rc) return rc;
-    *count = 0;
-    pthread_mutex_lock(&c.e->lk);
-    TRY(hipDeviceSynchronize());
-    for (int i = 0; i < VERIFY_SLOTS; i++) {
-        uint32_t w = 0;
-        if (!c.e->vs[i].ws.offcount) continue;
-        TRY(hipMemcpy(&w, c.e->vs[i].ws.offcount + EDK_REFUSED_WORD, sizeof(w), hipMemcpyDeviceToHost));
-        *count += w;
-    }
-out:
-    pthread_mutex_unlock(&c.e->lk);
-    leave(&c);
-    return rc;
-}
-#endif
 
 /* How verify treats a public key that does not decode to a curve point (ed_import never fails,
  * reference lib/ed.c:100-149).  EXACT (default): such items are evaluated in the reference's own
@@ -531,45 +420,6 @@ void eddsa_amd_set_rlc_min_items(size_t items)
     pthread_rwlock_unlock(&g_table);
 }
 
-/* per-kernel timing of the verify pass, for bench.py's roofline line: HIP events recorded on the
- * launch stream around k_verify_prepare / k_verify_main / k_verify_finish of every chunk */
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-void eddsa_amd_set_profiling(int on)
-{
-    pthread_rwlock_wrlock(&g_table);       /* no call in flight: nobody is bumping marks_used */
-    g_profiling = on != 0;
-    for (int d = 0; d < MAX_DEVICES; d++) if (g_eng[d]) g_eng[d]->marks_used = 0;
-    pthread_rwlock_unlock(&g_table);
-}
-#endif
-
-/* average duration (ms) of each of the three kernels over the passes recorded on the default device
- * since profiling was switched on (at most MARK_SLOTS; later passes are not recorded) */
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-int eddsa_amd_verify_phase_ms(float out[3])
-{
-    struct call c;
-    int rc = enter(&c, -1);
-    if (rc) return rc;
-    pthread_mutex_lock(&c.e->lk);
-    const int used = c.e->marks_used < MARK_SLOTS ? c.e->marks_used : MARK_SLOTS;
-    if (used == 0) { rc = -(int)hipErrorNotReady; goto out; }
-    out[0] = out[1] = out[2] = 0.0f;
-    for (int s = 0; s < used; s++) {
-        TRY(hipEventSynchronize(c.e->marks[s][3]));
-        for (int i = 0; i < 3; i++) {
-            float ms = 0.0f;
-            TRY(hipEventElapsedTime(&ms, c.e->marks[s][i], c.e->marks[s][i + 1]));
-            out[i] += ms / (float)used;
-        }
-    }
-out:
-    pthread_mutex_unlock(&c.e->lk);
-    leave(&c);
-    return rc;
-}
-#endif
-
 /* ------------------------------------------------------------------------------------------
  * device-pointer work on one engine (the engine's device is current)
  * ---------------------------------------------------------------------------------------- */
@@ -588,60 +438,83 @@ int take_async_error(struct engine *e)
     return __atomic_exchange_n(e->status, 0u, __ATOMIC_ACQ_REL) == EDK_STATUS_STALLED ? EDDSA_AMD_STALLED : 0;
 }
 
-/* both verify forms: chunks of at most CHUNK_MAX items through the workspace */
-int verify_on(struct engine *e, uint8_t *ok, const edk_verify_src *all, size_t n, hipStream_t st, hipEvent_t bulk_done, int bulk_early)
+/* A workspace pass: the chunks of one call, at most CHUNK_MAX items each, through one slot of the pool on stream `st`.
+ * pass_open takes e->lk, picks the slot, grows the workspaces named in `what` to the call's largest chunk and orders the
+ * stream behind the slot's previous pass (closing the pass itself if that fails); pass_close records the slot free behind
+ * the pass - or, after an error, waits for what was queued - and drops the lock.  The caller queues its chunks in between. */
+enum { PASS_WS = 1, PASS_RWS = 2, PASS_FWS = 4,
+       PASS_BUSY = 8 };   /* the caller drops e->lk inside the pass: the slot is marked busy, which ws_pick honours */
+struct pass { struct engine *e; struct vslot *v; hipStream_t st; int queued; };
+
+static int pass_close(struct pass *p, int rc)
 {
-    int rc = 0;
-    if (n == 0) return 0;
-    if ((rc = take_async_error(e))) return rc;   /* an earlier pass's kernels gave up: see engine.h */
-    pthread_mutex_lock(&e->lk);
-    struct vslot *v = ws_pick(e, st);
-    rc = ws_reserve(v, n < CHUNK_MAX ? n : CHUNK_MAX);
-    if (rc) goto unlock;
-    v->ws.exact_offcurve = g_offcurve_mode;
-    v->ws.algo = g_offcurve_mode ? g_verify_algo : 1;   /* the reject mode has no exact path for the items the pair search gives up on */
-    /* the slot may have served another stream: order this pass behind its previous one */
-    TRY(hipStreamWaitEvent(st, v->free, 0));
-    edk_verify_src whole = *all;
-    if (whole.msg_off && !whole.msg_end) whole.msg_end = whole.msg_off + n;   /* the kernels clamp every span into [0, msg_off[n]) */
-    for (size_t done = 0; done < n; done += CHUNK_MAX) {
-        size_t m = n - done < CHUNK_MAX ? n - done : CHUNK_MAX;
-        edk_verify_src src = whole;
-        src.sigs += done * all->sig_stride;
-        src.pubs += done * all->pub_stride;
-        if (all->msg_off) src.msg_off += done; else src.msgs += done * all->msg_stride;
-        hipEvent_t *marks = NULL;
-        if (g_profiling && e->marks_used < MARK_SLOTS) marks = e->marks[e->marks_used++];
-        TRY(edk_verify(ok + done, &src, m, e->base16, &v->ws, marks, done + CHUNK_MAX >= n ? bulk_done : NULL, bulk_early, st));
-    }
-    TRY(hipEventRecord(v->free, st));
-out:
-    if (rc) slot_quiesce(v, st);
-unlock:
-    pthread_mutex_unlock(&e->lk);
+    if (p->queued && !rc) rc = -(int)hipEventRecord(p->v->free, p->st);
+    if (p->queued && rc) slot_quiesce(p->v, p->st);   /* (a failed reserve has queued nothing) */
+    if (p->v->busy) { p->v->busy = 0; pthread_cond_broadcast(&p->e->slot_cv); }
+    pthread_mutex_unlock(&p->e->lk);
     return rc;
 }
 
-/* the fixed-base operations and x25519 share one driver: chunks of at most CHUNK_MAX items through fws */
+static int pass_open(struct pass *p, struct engine *e, size_t n, int what, hipStream_t st)
+{
+    int rc = 0;
+    const size_t items = n < CHUNK_MAX ? n : CHUNK_MAX;
+    pthread_mutex_lock(&e->lk);
+    *p = (struct pass){ e, ws_pick(e, st), st, 0 };
+    p->v->busy = (what & PASS_BUSY) != 0;
+    if (what & PASS_WS) rc = ws_reserve(p->v, items);
+    if (!rc && (what & PASS_RWS)) rc = rws_reserve(p->v, items);
+    if (!rc && (what & PASS_FWS)) rc = fws_reserve(p->v, items, st);
+    p->queued = !rc;
+    if (!rc) rc = -(int)hipStreamWaitEvent(st, p->v->free, 0);   /* the slot may have served another stream: behind its previous pass */
+    return rc ? pass_close(p, rc) : 0;
+}
+
+/* what the pass that starts at item `done` of a call of n items reads */
+static edk_verify_src src_at(const edk_verify_src *all, size_t n, size_t done)
+{
+    edk_verify_src src = *all;
+    if (all->msg_off && !all->msg_end) src.msg_end = all->msg_off + n;   /* the kernels clamp every span into [0, msg_off[n]) */
+    src.sigs += done * all->sig_stride;
+    src.pubs += done * all->pub_stride;
+    if (all->msg_off) src.msg_off += done; else src.msgs += done * all->msg_stride;
+    return src;
+}
+
+/* both verify forms */
+int verify_on(struct engine *e, uint8_t *ok, const edk_verify_src *all, size_t n, hipStream_t st, hipEvent_t bulk_done, int bulk_early)
+{
+    int rc = 0;
+    struct pass p;
+    if (n == 0) return 0;
+    if ((rc = take_async_error(e))) return rc;   /* an earlier pass's kernels gave up: see engine.h */
+    if ((rc = pass_open(&p, e, n, PASS_WS, st))) return rc;
+    p.v->ws.exact_offcurve = g_offcurve_mode;
+    p.v->ws.algo = g_offcurve_mode ? g_verify_algo : 1;   /* the reject mode has no exact path for the items the pair search gives up on */
+    for (size_t done = 0; done < n; done += CHUNK_MAX) {
+        const size_t m = n - done < CHUNK_MAX ? n - done : CHUNK_MAX;
+        const edk_verify_src src = src_at(all, n, done);
+        hipEvent_t *marks = NULL;
+        if (g_profiling && e->marks_used < MARK_SLOTS) marks = e->marks[e->marks_used++];
+        TRY(edk_verify(ok + done, &src, m, e->base16, &p.v->ws, marks, done + CHUNK_MAX >= n ? bulk_done : NULL, bulk_early, st));
+    }
+out:
+    return pass_close(&p, rc);
+}
+
+/* the fixed-base operations and x25519 share one driver */
 typedef hipError_t (*fixed_step)(struct engine *e, size_t done, size_t m, const void *ctx, const edk_fixed_ws *fws, hipStream_t st);
 
 static int fixed_on(struct engine *e, size_t n, fixed_step step, const void *ctx, hipStream_t st)
 {
     int rc = 0;
+    struct pass p;
     if (n == 0) return 0;
-    pthread_mutex_lock(&e->lk);
-    struct vslot *v = ws_pick(e, st);
-    rc = fws_reserve(v, n < CHUNK_MAX ? n : CHUNK_MAX, st);
-    if (rc) goto unlock;
-    TRY(hipStreamWaitEvent(st, v->free, 0));
+    if ((rc = pass_open(&p, e, n, PASS_FWS, st))) return rc;
     for (size_t done = 0; done < n; done += CHUNK_MAX)
-        TRY(step(e, done, n - done < CHUNK_MAX ? n - done : CHUNK_MAX, ctx, &v->fws, st));
-    TRY(hipEventRecord(v->free, st));
+        TRY(step(e, done, n - done < CHUNK_MAX ? n - done : CHUNK_MAX, ctx, &p.v->fws, st));
 out:
-    if (rc) slot_quiesce(v, st);
-unlock:
-    pthread_mutex_unlock(&e->lk);
-    return rc;
+    return pass_close(&p, rc);
 }
 
 struct sign_ctx { uint8_t *sigs; const uint8_t *secs, *pubs, *msgs; const uint64_t *msg_off, *msg_end; size_t msg_len; };
@@ -722,6 +595,7 @@ int sk_to_x_on(struct engine *e, uint8_t *out, const uint8_t *in, size_t n, hipS
 int rlc_on(struct engine *e, uint8_t *ok, uint32_t *stats, const edk_verify_src *all, size_t n, hipStream_t st)
 {
     int rc = 0;
+    struct pass p;
     if (n == 0) return 0;
     if (n < g_rlc_min_items) {
         /* the combination has about 1 ms of latency of its own (hash tree, one serial Horner per group): below
@@ -734,58 +608,46 @@ int rlc_on(struct engine *e, uint8_t *ok, uint32_t *stats, const edk_verify_src 
     /* The combination's group verdicts are read by the host, once per pass.  The wait for the stream happens OUTSIDE
      * e->lk (other threads keep enqueueing on this engine meanwhile); the workspace slot stays reserved through its
      * busy mark, which ws_pick honours. */
-    pthread_mutex_lock(&e->lk);
-    struct vslot *v = ws_pick(e, st);
-    v->busy = 1;
-    rc = ws_reserve(v, n < CHUNK_MAX ? n : CHUNK_MAX);
-    if (!rc) rc = rws_reserve(v, n < CHUNK_MAX ? n : CHUNK_MAX);
-    if (rc) goto release;
-    v->ws.exact_offcurve = g_offcurve_mode ? g_offcurve_mode : 1;
-    v->ws.algo = g_verify_algo;
-    TRY(hipStreamWaitEvent(st, v->free, 0));
-    edk_verify_src whole = *all;
-    if (whole.msg_off && !whole.msg_end) whole.msg_end = whole.msg_off + n;
+    if ((rc = pass_open(&p, e, n, PASS_WS | PASS_RWS | PASS_BUSY, st))) return rc;
+    p.v->ws.exact_offcurve = g_offcurve_mode ? g_offcurve_mode : 1;
+    p.v->ws.algo = g_verify_algo;
     for (size_t done = 0; done < n; done += CHUNK_MAX) {
-        size_t m = n - done < CHUNK_MAX ? n - done : CHUNK_MAX;
-        edk_verify_src src = whole;
-        src.sigs += done * all->sig_stride;
-        src.pubs += done * all->pub_stride;
-        if (all->msg_off) src.msg_off += done; else src.msgs += done * all->msg_stride;
-        TRY(edk_verify_rlc(ok + done, stats, &src, m, e->base16, &v->ws, &v->rws, st));
+        const size_t m = n - done < CHUNK_MAX ? n - done : CHUNK_MAX;
+        const edk_verify_src src = src_at(all, n, done);
+        TRY(edk_verify_rlc(ok + done, stats, &src, m, e->base16, &p.v->ws, &p.v->rws, st));
         pthread_mutex_unlock(&e->lk);
         hipError_t er = hipStreamSynchronize(st);
         pthread_mutex_lock(&e->lk);
         TRY(er);
-        TRY(edk_verify_rlc_fallback(ok + done, &src, m, e->base16, &v->ws, &v->rws, st));
+        TRY(edk_verify_rlc_fallback(ok + done, &src, m, e->base16, &p.v->ws, &p.v->rws, st));
     }
-    TRY(hipEventRecord(v->free, st));
 out:
-    if (rc) slot_quiesce(v, st);
-release:
-    v->busy = 0;
-    pthread_cond_broadcast(&e->slot_cv);
-    pthread_mutex_unlock(&e->lk);
-    return rc;
+    return pass_close(&p, rc);
 }
 
 /* ------------------------------------------------------------------------------------------
- * device-pointer entry points: run on the device that holds the output buffer
+ * device-pointer entry points: run on the device that holds the output buffer (an empty batch
+ * is done before that pointer is looked at)
  * ---------------------------------------------------------------------------------------- */
 
-#define DEV_ENTER(outptr) \
-    struct call c; int dev_ = -1, rc; \
-    if (n == 0) return 0; \
-    rc = device_of(outptr, &dev_); if (rc) return rc; \
-    rc = enter(&c, dev_); if (rc) return rc
+static int enter_dev(struct call *c, const void *out)
+{
+    int dev = -1;
+    const int rc = device_of(out, &dev);
+    return rc ? rc : enter(c, dev);
+}
+
+/* return leave_with(&c, work(c.e, ..)): the work's answer, after leave() */
+static int leave_with(struct call *c, int rc) { leave(c); return rc; }
 
 int ed25519_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs,
                              const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
     const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL };
-    DEV_ENTER(ok);
-    rc = verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0);
-    leave(&c);
-    return rc;
+    struct call c;
+    int rc = 0;
+    if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
+    return leave_with(&c, verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
 }
 
 /* fixed-size records: see include/eddsa_amd.h */
@@ -801,72 +663,69 @@ int ed25519_verify_records_dev(uint8_t *ok, const uint8_t *records, size_t strid
     if (!records_ok(stride, sig_off, pub_off, msg_off, msg_len)) return -(int)hipErrorInvalidValue;
     const edk_verify_src src = { records + sig_off, records + pub_off, records + msg_off, NULL, msg_len,
                                  stride, stride, stride, NULL };
-    DEV_ENTER(ok);
-    rc = verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0);
-    leave(&c);
-    return rc;
+    struct call c;
+    int rc = 0;
+    if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
+    return leave_with(&c, verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
 }
 
 int ed25519_verify_batch_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *sigs, const uint8_t *pubs,
                                  const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
     const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL };
-    DEV_ENTER(ok);
-    rc = rlc_on(c.e, ok, stats, &src, n, (hipStream_t)stream);
-    leave(&c);
-    return rc;
+    struct call c;
+    int rc = 0;
+    if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
+    return leave_with(&c, rlc_on(c.e, ok, stats, &src, n, (hipStream_t)stream));
 }
 
 int ed25519_sign_batch_dev(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
                            const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
-    DEV_ENTER(sigs);
-    rc = sign_on(c.e, sigs, secs, pubs, msgs, msg_off, msg_len, n, (hipStream_t)stream);
-    leave(&c);
-    return rc;
+    struct call c;
+    int rc = 0;
+    if (n == 0 || (rc = enter_dev(&c, sigs))) return rc;
+    return leave_with(&c, sign_on(c.e, sigs, secs, pubs, msgs, msg_off, msg_len, n, (hipStream_t)stream));
 }
 
 int ed25519_genpub_batch_dev(uint8_t *pubs, const uint8_t *secs, size_t n, void *stream)
 {
-    struct io_ctx x = { pubs, secs };
-    DEV_ENTER(pubs);
-    rc = fixed_on(c.e, n, genpub_step, &x, (hipStream_t)stream);
-    leave(&c);
-    return rc;
+    struct call c;
+    int rc = 0;
+    if (n == 0 || (rc = enter_dev(&c, pubs))) return rc;
+    return leave_with(&c, genpub_on(c.e, pubs, secs, n, (hipStream_t)stream));
 }
 
 int x25519_batch_dev(uint8_t *out, const uint8_t *scalars, const uint8_t *points, size_t n, void *stream)
 {
-    struct io2_ctx x = { out, scalars, points };
-    DEV_ENTER(out);
-    rc = fixed_on(c.e, n, x25519_step, &x, (hipStream_t)stream);
-    leave(&c);
-    return rc;
+    struct call c;
+    int rc = 0;
+    if (n == 0 || (rc = enter_dev(&c, out))) return rc;
+    return leave_with(&c, x25519_on(c.e, out, scalars, points, n, (hipStream_t)stream));
 }
 
 int x25519_base_batch_dev(uint8_t *out, const uint8_t *scalars, size_t n, void *stream)
 {
-    struct io_ctx x = { out, scalars };
-    DEV_ENTER(out);
-    rc = fixed_on(c.e, n, xbase_step, &x, (hipStream_t)stream);
-    leave(&c);
-    return rc;
+    struct call c;
+    int rc = 0;
+    if (n == 0 || (rc = enter_dev(&c, out))) return rc;
+    return leave_with(&c, xbase_on(c.e, out, scalars, n, (hipStream_t)stream));
 }
 
 int pk_ed25519_to_x25519_batch_dev(uint8_t *out, const uint8_t *in, size_t n, void *stream)
 {
-    DEV_ENTER(out);
-    rc = pk_to_x_on(c.e, out, in, n, (hipStream_t)stream);
-    leave(&c);
-    return rc;
+    struct call c;
+    int rc = 0;
+    if (n == 0 || (rc = enter_dev(&c, out))) return rc;
+    return leave_with(&c, pk_to_x_on(c.e, out, in, n, (hipStream_t)stream));
 }
 
 int sk_ed25519_to_x25519_batch_dev(uint8_t *out, const uint8_t *in, size_t n, void *stream)
 {
-    DEV_ENTER(out);
-    rc = sk_to_x_on(c.e, out, in, n, (hipStream_t)stream);
-    leave(&c);
-    return rc;
+    struct call c;
+    int rc = 0;
+    if (n == 0 || (rc = enter_dev(&c, out))) return rc;
+    return leave_with(&c, sk_to_x_on(c.e, out, in, n, (hipStream_t)stream));
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -1025,11 +884,150 @@ out:
     return rc;
 }
 
+/* ------------------------------------------------------------------------------------------
+ * the test and measurement surface (include/eddsa_amd_debug.h): only libeddsa_amd_debug.so has it; the fault injectors
+ * are inert unless armed
+ * ---------------------------------------------------------------------------------------- */
+
+#ifdef EDDSA_AMD_DEBUG_BUILD
+int eddsa_amd_debug_init(int device, unsigned flags)
+{
+    const int rc = eddsa_amd_init(device);
+    if (rc) return rc;
+    __atomic_store_n(&g_hooks_armed, (flags & EDDSA_AMD_TEST_HOOKS) != 0, __ATOMIC_RELEASE);
+    edk_debug_counting((flags & EDDSA_AMD_TEST_HOOKS) != 0);
+    if (!(flags & EDDSA_AMD_TEST_HOOKS)) (void)edk_debug_fail_in(0);
+    return 0;
+}
+
+int eddsa_amd_debug_fail_hip_call(int nth)
+{
+    if (!__atomic_load_n(&g_hooks_armed, __ATOMIC_ACQUIRE)) return EDDSA_AMD_HOOKS_OFF;
+    (void)edk_debug_fail_in(nth < 0 ? 0 : nth);
+    return 0;
+}
+
+int eddsa_amd_debug_hip_calls(void)
+{
+    return edk_debug_fail_in(-1);
+}
+
+int eddsa_amd_debug_withhold_handoff(int tile_plus_1)
+{
+    struct call c;
+    int rc, gave_up = 0;
+    if (!__atomic_load_n(&g_hooks_armed, __ATOMIC_ACQUIRE)) return EDDSA_AMD_HOOKS_OFF;
+    if ((rc = enter(&c, -1))) return rc;
+    pthread_mutex_lock(&c.e->lk);
+    TRY(hipDeviceSynchronize());
+    for (int i = 0; i < VERIFY_SLOTS; i++) {
+        const uint32_t w = tile_plus_1 > 0 ? (uint32_t)tile_plus_1 : 0u;
+        if (c.e->vs[i].ws.offcount) TRY(hipMemcpy(c.e->vs[i].ws.offcount + EDK_WITHHOLD_WORD, &w, sizeof(w), hipMemcpyHostToDevice));
+        if (c.e->vs[i].rws.base) {
+            uint32_t *hook = (uint32_t *)((char *)c.e->vs[i].rws.base + edk_rlc_hook_offset(c.e->vs[i].rws.capacity));
+            uint32_t two[2] = { 0, 0 };
+            TRY(hipMemcpy(two, hook, sizeof(two), hipMemcpyDeviceToHost));
+            gave_up += (int)two[1];
+            two[0] = w; two[1] = 0;
+            TRY(hipMemcpy(hook, two, sizeof(two), hipMemcpyHostToDevice));
+        }
+    }
+    rc = gave_up;
+out:
+    pthread_mutex_unlock(&c.e->lk);
+    leave(&c);
+    return rc;
+}
+
+int eddsa_amd_dump_tables(uint32_t *base16_words, uint32_t *comb_words)
+{
+    struct call c;
+    int rc = enter(&c, -1);
+    if (rc) return rc;
+    TRY(hipMemcpy(base16_words, c.e->base16, (size_t)TABLE_BASE16_ENTRIES * TABLE_ENTRY_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    TRY(hipMemcpy(comb_words, c.e->comb, TABLE_COMB_ENTRIES * TABLE_ENTRY_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+out:
+    leave(&c);
+    return rc;
+}
+
+/* Which evaluation ed25519_verify* uses (same verdicts; a measurement and test aid).  0 (default): half-length
+ * scalars (csrc/halve.h), four lanes per item up to 2^15 items and one above; 1: full-length windows always;
+ * 2: half-length scalars with one lane per item always. */
+void eddsa_amd_set_verify_algo(int algo)
+{
+    pthread_rwlock_wrlock(&g_table);
+    g_verify_algo = algo >= 1 && algo <= 3 ? algo : 0;
+    pthread_rwlock_unlock(&g_table);
+}
+
+/* diagnostic for the tests: how many half-length pairs the exact integer check (csrc/lanes.h: verify_half_scalars_lane)
+ * has refused on the default device since its workspaces were allocated.  Waits for the device.  Expected: 0. */
+int eddsa_amd_halve_rejected(uint64_t *count)
+{
+    struct call c;
+    int rc = enter(&c, -1);
+    if (rc) return rc;
+    *count = 0;
+    pthread_mutex_lock(&c.e->lk);
+    TRY(hipDeviceSynchronize());
+    for (int i = 0; i < VERIFY_SLOTS; i++) {
+        uint32_t w = 0;
+        if (!c.e->vs[i].ws.offcount) continue;
+        TRY(hipMemcpy(&w, c.e->vs[i].ws.offcount + EDK_REFUSED_WORD, sizeof(w), hipMemcpyDeviceToHost));
+        *count += w;
+    }
+out:
+    pthread_mutex_unlock(&c.e->lk);
+    leave(&c);
+    return rc;
+}
+
+int eddsa_amd_debug_teardown_errors(int *first_hip_error)
+{
+    if (first_hip_error) *first_hip_error = __atomic_load_n(&g_teardown.first, __ATOMIC_ACQUIRE);
+    return __atomic_load_n(&g_teardown.count, __ATOMIC_ACQUIRE);
+}
+
+/* per-kernel timing of the verify pass, for bench.py's roofline line: HIP events recorded on the
+ * launch stream around k_verify_prepare / k_verify_main / k_verify_finish of every chunk */
+void eddsa_amd_set_profiling(int on)
+{
+    pthread_rwlock_wrlock(&g_table);       /* no call in flight: nobody is bumping marks_used */
+    g_profiling = on != 0;
+    for (int d = 0; d < MAX_DEVICES; d++) if (g_eng[d]) g_eng[d]->marks_used = 0;
+    pthread_rwlock_unlock(&g_table);
+}
+
+/* average duration (ms) of each of the three kernels over the passes recorded on the default device
+ * since profiling was switched on (at most MARK_SLOTS; later passes are not recorded) */
+int eddsa_amd_verify_phase_ms(float out[3])
+{
+    struct call c;
+    int rc = enter(&c, -1);
+    if (rc) return rc;
+    pthread_mutex_lock(&c.e->lk);
+    const int used = c.e->marks_used < MARK_SLOTS ? c.e->marks_used : MARK_SLOTS;
+    if (used == 0) { rc = -(int)hipErrorNotReady; goto out; }
+    out[0] = out[1] = out[2] = 0.0f;
+    for (int s = 0; s < used; s++) {
+        TRY(hipEventSynchronize(c.e->marks[s][3]));
+        for (int i = 0; i < 3; i++) {
+            float ms = 0.0f;
+            TRY(hipEventElapsedTime(&ms, c.e->marks[s][i], c.e->marks[s][i + 1]));
+            out[i] += ms / (float)used;
+        }
+    }
+out:
+    pthread_mutex_unlock(&c.e->lk);
+    leave(&c);
+    return rc;
+}
+
 /* Secret hygiene check (tests): non-zero bytes left on the default device in out[0] the scalar
  * workspace `aux` (sign's a and r), out[1] the point workspace `acc` (x25519's (x2 : z2); public for
  * the other operations), out[2] the host pipeline's first input staging buffers (secret keys /
  * scalars), out[3] its output staging buffer.  Waits for the device to go idle first. */
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
 int eddsa_amd_secret_residue(uint64_t out[4])
 {
     struct call c;
@@ -1040,8 +1038,8 @@ int eddsa_amd_secret_residue(uint64_t out[4])
     TRY(hipDeviceSynchronize());
     for (int i = 0; i < VERIFY_SLOTS && !rc; i++) {
         const struct vslot *v = &c.e->vs[i];
-        rc = count_nonzero_dev(v->fws.aux, v->fws.capacity * 16 * sizeof(uint32_t), &out[0]);
-        if (!rc) rc = count_nonzero_dev(v->fws.acc, v->fws.capacity * ACC_WORDS * sizeof(uint32_t), &out[1]);
+        rc = count_nonzero_dev(v->fws.aux, fws_aux_bytes(v->fws.capacity), &out[0]);
+        if (!rc) rc = count_nonzero_dev(v->fws.acc, fws_acc_bytes(v->fws.capacity), &out[1]);
     }
 out:
     pthread_mutex_unlock(&c.e->lk);

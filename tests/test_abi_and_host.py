@@ -88,15 +88,19 @@ def test_the_reference_selftests_compile_against_our_header():
     """the reference's runnable selftests (test/selftest-x25519.c, -convert.c, -x25519_base.c) compile unchanged against
     include/eddsa.h: the header IS the reference's contract (lib/eddsa.h:44-113).  The oracle's recipe compiles them where
     the reference's sources lie (nothing is copied) into oracle/_ref/ at build time; this test reads what it left.  The
-    x25519 one links and passes against the GPU library through tests/c/selftest_dropin.c, which drives the same table."""
+    x25519 one links and passes against the GPU library through tests/c/selftest_dropin.c, which drives the same table.
+    Each object must have been compiled against include/eddsa.h AS IT IS NOW: the recipe records the header's sha256 beside
+    the object (file times say when a checkout or a copy wrote a file, not whether its content changed)."""
+    import hashlib
     ref = os.path.join(ROOT, "oracle", "_ref")
     if not os.path.exists(os.path.join(ref, "libeddsa_ref.so")):
         pytest.skip("oracle/_ref not built: no reference checkout where the project was built")
-    header = os.path.getmtime(os.path.join(ROOT, "include", "eddsa.h"))
+    header = hashlib.sha256(open(os.path.join(ROOT, "include", "eddsa.h"), "rb").read()).hexdigest()
     for name in ("selftest-x25519", "selftest-convert", "selftest-x25519_base"):
-        obj, log = os.path.join(ref, name + ".o"), os.path.join(ref, name + ".log")
+        obj, log, stamp = (os.path.join(ref, name + ext) for ext in (".o", ".log", ".header"))
         assert os.path.exists(obj), name + ": " + (open(log).read() if os.path.exists(log) else "not compiled: rebuild oracle/_ref")
-        assert os.path.getmtime(obj) >= header, name + ": compiled before include/eddsa.h changed: rebuild oracle/_ref"
+        assert os.path.exists(stamp), name + ": no record of the header it was compiled against: rebuild oracle/_ref"
+        assert open(stamp).read().split()[0] == header, name + ": compiled before include/eddsa.h changed: rebuild oracle/_ref"
 
 
 def test_the_hooks_are_inert_until_armed():
@@ -226,6 +230,51 @@ def test_argument_validation():
         ed.ed25519_verify_records(np.zeros((2, 128), np.uint8), 0, 64, 100, 32)    # message sticks out
     with pytest.raises(ValueError):
         ed.ed25519_verify_records(np.zeros(128, np.uint8), 0, 64, 96, 32)
+    # the five calls that carry messages share one driver: each refuses the same bad inputs, in the words it always used
+    for fn, first, w in ((ed.ed25519_verify_batch, "sigs", 64), (ed.ed25519_verify_batch_rlc, "sigs", 64),
+                         (ed.ed25519_sign_batch, "secs", 32), (ed.ed25519_verify_batch_multi, "sigs", 64),
+                         (ed.ed25519_sign_batch_multi, "secs", 32)):
+        a, p, m = np.zeros((2, w), np.uint8), np.zeros((2, 32), np.uint8), np.zeros(6, np.uint8)
+        for args, kw, exc, text in (
+                ((a, np.zeros((3, 32), np.uint8), m), {}, ValueError, f"{fn.__name__}: {first} and pubs disagree on the batch size"),
+                ((a, p, np.zeros(5, np.uint8)), {}, ValueError, "msgs: size is not a multiple of the batch size; pass msg_len or msg_off"),
+                ((a, p, m), {"msg_off": [0, 3]}, ValueError, "msg_off: expected n+1 offsets within msgs"),              # wrong length
+                ((a, p, m), {"msg_off": [0, 3, 9]}, ValueError, "msg_off: expected n+1 offsets within msgs"),           # runs past msgs
+                ((a.astype(np.int32), p, m), {}, TypeError, f"{first}: expected uint8 data"),
+                ((a, p.astype(np.int32), m), {}, TypeError, "pubs: expected uint8 data"),
+                ((a, p, m.astype(np.int32)), {}, TypeError, "msgs: expected uint8 data"),
+                ((np.zeros(2 * w + 1, np.uint8), p, m), {}, ValueError, f"{first}: size {2 * w + 1} is not a multiple of {w}")):
+            with pytest.raises(exc) as e:
+                fn(*args, **kw)
+            assert type(e.value) is exc and str(e.value) == text, (fn.__name__, text, e.value)
+        # a doubly wrong call: the plain and the sign form look at msgs first, the other three at the batch sizes
+        msgs_first = fn in (ed.ed25519_verify_batch, ed.ed25519_sign_batch)
+        with pytest.raises(TypeError if msgs_first else ValueError) as e:
+            fn(a, np.zeros((3, 32), np.uint8), m.astype(np.int32))
+        assert str(e.value) == ("msgs: expected uint8 data" if msgs_first else f"{fn.__name__}: {first} and pubs disagree on the batch size")
+    # the thirteen eddsa.h names: every fixed-width argument of each, one byte short (refused before the C function is called)
+    sec, pub, sig = ("sec", 32), ("pub", 32), ("sig", 64)
+    singles = {"ed25519_genpub": (sec,), "ed25519_sign": (sec, pub, b""), "ed25519_verify": (sig, pub, b""),
+               "x25519_base": (("scalar", 32),), "x25519": (("scalar", 32), ("point", 32)), "pk_ed25519_to_x25519": (pub,),
+               "sk_ed25519_to_x25519": (sec,), "eddsa_genpub": (sec,), "eddsa_sign": (sec, pub, b""), "eddsa_verify": (sig, pub, b""),
+               "DH": (sec, ("point", 32)), "eddsa_pk_eddsa_to_dh": (pub,), "eddsa_sk_eddsa_to_dh": (sec,)}
+    assert len(singles) == 13
+    for name, params in singles.items():
+        fixed = [x for x in params if x != b""]
+        for short in range(len(fixed)):
+            args = [bytes(wd - (k == short)) for k, (_, wd) in enumerate(fixed)] + [b""] * (len(params) - len(fixed))
+            with pytest.raises(ValueError) as e:
+                getattr(ed, name)(*args)
+            assert str(e.value) == f"{fixed[short][0]}: expected {fixed[short][1]} bytes, got {fixed[short][1] - 1}", name
+        # by keyword as well; too few, too many, unknown and doubled arguments are a TypeError
+        good = {nm: bytes(wd) for nm, wd in fixed}
+        good.update({"data": b""} if len(params) > len(fixed) else {})
+        with pytest.raises(ValueError) as e:
+            getattr(ed, name)(**dict(good, **{fixed[0][0]: bytes(fixed[0][1] + 1)}))
+        assert str(e.value) == f"{fixed[0][0]}: expected {fixed[0][1]} bytes, got {fixed[0][1] + 1}", name
+        for args, kw in (((), {}), (tuple(good.values()) + (b"",), {}), ((), dict(good, other=b"")), (tuple(good.values()), {fixed[0][0]: b""})):
+            with pytest.raises(TypeError):
+                getattr(ed, name)(*args, **kw)
 
 
 def test_bench_insists_on_a_device_per_rank():
