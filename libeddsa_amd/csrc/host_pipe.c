@@ -24,6 +24,9 @@
  * Jobs that carry secrets (secret keys, scalars, shared secrets) zero their staging copies - in HBM, in the
  * pinned host buffers and in the combiner's buffers - before the call returns, on the error path too (the
  * reference wipes its stack after the same operations: lib/ed25519-sha512.c:77,136, lib/x25519.c:208,221).
+ *
+ * What an operation is - widths, wipes, chunk sizes, combiner slot - is one row of the table g_ops; a call (struct hjob) is
+ * a row and its pointers.  The measurement aids and test hooks of the debug library stand together at the end of the file.
  */
 #define _GNU_SOURCE                    /* syscall(): the combiner's waiters sleep on a futex */
 #include "engine.h"
@@ -213,47 +216,47 @@ static int is_pinned(const void *p, size_t bytes)
 #define PIPE_PIECE ((size_t)8 << 20)         /* staging granularity: a piece is handed to the DMA engine while the next is copied */
 #define PIN_CHECK_MIN ((size_t)1 << 20)      /* smaller arrays are staged without asking whether they are pinned */
 
+/* (set by the measurement aids at the end of the file, which only libeddsa_amd_debug.so has) */
 static size_t g_pipe_first, g_pipe_stage;   /* eddsa_amd_set_pipeline: 0 = the defaults above / the job's own stage size */
 static int g_pipe_chain = -1;               /* -1: the job's own; 0: the lanes' kernels run side by side; 1: in chunk order; 2: verify's next chunk starts beside the main kernel */
 
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-void eddsa_amd_set_pipeline_chain(int mode)
-{
-    pthread_rwlock_wrlock(&g_table);
-    g_pipe_chain = mode;
-    pthread_rwlock_unlock(&g_table);
-}
-#endif
-
-/* tuning: items of the first chunk of a host-pointer call and of its later stages (0 = default).  A measurement aid. */
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-void eddsa_amd_set_pipeline(size_t first_chunk, size_t stage_chunk)
-{
-    pthread_rwlock_wrlock(&g_table);
-    g_pipe_first = first_chunk;
-    g_pipe_stage = stage_chunk;
-    pthread_rwlock_unlock(&g_table);
-}
-#endif
-
 enum { WIPE_NONE = 0, WIPE_IN0 = 1, WIPE_OUT = 2 };   /* which staging buffers held secrets */
+/* combiner slots (engine.h: COMB_KINDS): small calls of one kind may be merged; KIND_NONE: never */
+enum { KIND_NONE = 0, KIND_VERIFY = 1, KIND_SIGN = 2, KIND_X25519 = 3, KIND_GENPUB = 4, KIND_XBASE = 5, KIND_PK_TO_X = 6, KIND_SK_TO_X = 7 };
 
-struct hjob {
-    int n_in; const uint8_t *in[PIPE_MAX_IN]; size_t in_w[PIPE_MAX_IN];   /* fixed-width inputs */
-    int has_msgs; const uint8_t *msgs; const uint64_t *msg_off; size_t msg_len;
-    uint8_t *out; size_t out_w;
-    int (*run)(struct engine *e, const struct hjob *j, uint8_t *d_out, uint8_t *const d_in[PIPE_MAX_IN],
-               const uint8_t *d_msgs, const uint64_t *d_off, size_t msg_len, size_t m, hipStream_t st, hipEvent_t kdone);
-    size_t rec_sig, rec_pub, rec_msg;          /* records: offsets inside in[0]'s items (in_w[0] = stride) */
-    size_t chunk;                              /* items per pipeline stage (0: PIPE_CHUNK) */
-    int wipe;                                  /* WIPE_* */
-    uint32_t *stats;                           /* rlc: host copy of the pass statistics (4 words) or NULL */
-    size_t first_chunk;                        /* items of the first chunk (0: PIPE_FIRST_CHUNK); later ones double up to `chunk` */
-    int chain;                                 /* the kernels of consecutive chunks run in chunk order (else side by side) */
-    int kind;                                  /* combiner slot (engine.h: COMB_KINDS): small calls of this operation may be merged; 0: never */
-    int src_pinned;                            /* every host array of the job is page-locked: no staging */
-    int traced;                                /* the caller (the combiner's leader) has started the call's trace already */
+/* one chunk of a job as its kernels see it: the HBM buffers of the lane that carries it, m items, on stream st */
+struct chunk {
+    uint8_t *d_out; uint8_t *const *d_in; const uint8_t *d_msgs; size_t m; hipStream_t st;
+    const uint64_t *d_off;                     /* ragged messages: the chunk's offset table, rebased to its first byte; else NULL */
+    hipEvent_t kdone;                          /* the lane's "kernels queued" event */
+    uint32_t *d_stats;                         /* rlc: the pass statistics in HBM (4 words) or NULL */
 };
+
+/* what an operation is; the table (g_ops) stands in front of the entry points */
+struct hjob;
+struct op {
+    int n_in; size_t in_w[PIPE_MAX_IN];        /* fixed-width inputs (width 0: the call's own, hjob.stride) */
+    size_t out_w; int has_msgs;
+    int (*run)(struct engine *e, const struct hjob *j, const struct chunk *c);
+    int wipe;                                  /* WIPE_* */
+    int chain;                                 /* the kernels of consecutive chunks run in chunk order (else side by side) */
+    int kind;                                  /* KIND_*: small calls of this operation may be merged */
+    size_t chunk;                              /* items per pipeline stage (0: PIPE_CHUNK) */
+    size_t first_chunk;                        /* items of the first chunk (0: PIPE_FIRST_CHUNK); later ones double up to `chunk` */
+    int reports;                               /* its kernels report through the engine's status word (take_async_error) */
+};
+
+/* a call: the operation and its pointers */
+struct hjob {
+    const struct op *op;
+    const uint8_t *in[PIPE_MAX_IN]; uint8_t *out;
+    const uint8_t *msgs; const uint64_t *msg_off; size_t msg_len;
+    size_t stride, rec_sig, rec_pub, rec_msg;  /* records: the width of in[0]'s items and the offsets inside them */
+    uint32_t *stats;                           /* rlc: host copy of the pass statistics (4 words) or NULL */
+    int src_pinned;                            /* every host array of the job is page-locked: no staging */
+};
+
+static size_t in_w(const struct hjob *j, int i) { return j->op->in_w[i] ? j->op->in_w[i] : j->stride; }
 
 /* (new memory starts zeroed, on the stream that will use it: what the allocator hands out is whatever a freed buffer held,
  * and the residue check of the tests - pipe_residue - looks at whole buffers) */
@@ -401,6 +404,15 @@ out:
     return rc;
 }
 
+/* queue the download of the lane's chunk - into pend_via or straight into pend_dst - and the wipe of secret results in HBM */
+static int lane_download(struct lane *L, int wipe)
+{
+    hipError_t e = hipMemcpyAsync(L->pend_via ? L->pend_via : (void *)L->pend_dst, L->pend_dev, L->pend_bytes, hipMemcpyDeviceToHost, L->st);
+    if (e == hipSuccess && (wipe & WIPE_OUT)) e = hipMemsetAsync(L->pend_dev, 0, L->pend_bytes, L->st);    /* shared secrets leave HBM with the call */
+    L->pend_queued = 1;
+    return -(int)e;
+}
+
 /* Wait for the kernels of the chunk the lane carries, fetch its results, deliver them and zero the staging copies of
  * secrets.  The download is queued only now, when it can run at once: a copy queued behind kernels still to run sits at
  * the head of one of the DMA engines' queues, and the UPLOADS that the runtime later hands to the same engine wait
@@ -411,15 +423,14 @@ static int lane_drain(struct lane *L, int wipe, int *wipes)
     TRY(hipStreamSynchronize(L->st));
     if (L->pend_bytes) {
         if (!L->pend_queued) {
-            TRY(hipMemcpyAsync(L->pend_via ? L->pend_via : (void *)L->pend_dst, L->pend_dev, L->pend_bytes, hipMemcpyDeviceToHost, L->st));
-            if (wipe & 2) TRY(hipMemsetAsync(L->pend_dev, 0, L->pend_bytes, L->st));    /* shared secrets leave HBM with the call */
+            if ((rc = lane_download(L, wipe))) goto out;
             TRY(hipStreamSynchronize(L->st));
         }
         if (L->pend_via) par_copy(L->pend_dst, L->pend_via, L->pend_bytes);
     }
     /* wipes == NULL: the lane is about to be reused, zero it now; otherwise queue the zeroing (end of the call) */
-    if ((wipe & 1) && L->used_in0) { if (wipes) pool_submit(wipes, (uint8_t *)L->h_in[0], NULL, L->used_in0, 0); else par_copy(L->h_in[0], NULL, L->used_in0); }
-    if ((wipe & 2) && L->pend_bytes && L->pend_via) { if (wipes) pool_submit(wipes, (uint8_t *)L->pend_via, NULL, L->pend_bytes, 0); else par_copy(L->pend_via, NULL, L->pend_bytes); }
+    if ((wipe & WIPE_IN0) && L->used_in0) { if (wipes) pool_submit(wipes, (uint8_t *)L->h_in[0], NULL, L->used_in0, 0); else par_copy(L->h_in[0], NULL, L->used_in0); }
+    if ((wipe & WIPE_OUT) && L->pend_bytes && L->pend_via) { if (wipes) pool_submit(wipes, (uint8_t *)L->pend_via, NULL, L->pend_bytes, 0); else par_copy(L->pend_via, NULL, L->pend_bytes); }
 out:
     L->pend_bytes = 0;
     L->used_in0 = 0;
@@ -427,6 +438,13 @@ out:
 }
 
 static int g_fail_next_host_call;      /* eddsa_amd_debug_fail_next_host_call: set and consumed atomically */
+
+static int64_t now_ns(void)
+{
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (int64_t)ts.tv_sec * 1000000000 + ts.tv_nsec;
+}
 
 /* measurement aid: host-side time stamps of the last host-pointer call (eddsa_amd_debug_pipe_trace) */
 #define TRACE_MAX 512
@@ -436,63 +454,11 @@ static int g_fail_next_host_call;      /* eddsa_amd_debug_fail_next_host_call: s
  * data race); on / n / seen are read and written atomically; the reader holds g_table for writing, i.e. no call is in flight */
 static struct { int on, n, seen; int tag[TRACE_MAX]; unsigned chunk[TRACE_MAX]; int64_t t_ns[TRACE_MAX]; } g_trace;
 #define TRACE_ON() __atomic_load_n(&g_trace.on, __ATOMIC_RELAXED)
-static int64_t trace_now(void)
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (int64_t)ts.tv_sec * 1000000000 + ts.tv_nsec;
-}
 #define TRACE(tag_, k_) do { if (TRACE_ON()) { const int i_ = __atomic_fetch_add(&g_trace.n, 1, __ATOMIC_RELAXED); \
     if (i_ >= 0 && i_ < TRACE_MAX) { __atomic_store_n(&g_trace.tag[i_], (tag_), __ATOMIC_RELAXED); \
-        __atomic_store_n(&g_trace.chunk[i_], (unsigned)(k_), __ATOMIC_RELAXED); __atomic_store_n(&g_trace.t_ns[i_], trace_now(), __ATOMIC_RELAXED); } } } while (0)
+        __atomic_store_n(&g_trace.chunk[i_], (unsigned)(k_), __ATOMIC_RELAXED); __atomic_store_n(&g_trace.t_ns[i_], now_ns(), __ATOMIC_RELAXED); } } } while (0)
 #define TRACE_RESTART() __atomic_store_n(&g_trace.n, 0, __ATOMIC_RELAXED)
 
-/* on != 0: record host-side time stamps in every host-pointer call from now on; returns the number of stamps of the last
- * call and copies up to `max` of them: tag (0 call start, 1 lane drained, 2 inputs staged and queued, 3 kernels queued,
- * 4 download queued, 5 all lanes drained, 6 call end; of a combined launch also 7 leader elected, 8 callers gathered,
- * 9 requests packed, 10 results handed back), chunk index, milliseconds since the call started.  on = 2: recording stops
- * by itself after the 20th combined launch of 32 calls or more, so that a typical launch under load can be read */
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-int eddsa_amd_debug_pipe_trace(int on, int *tags, unsigned *chunks, double *ms, int max)
-{
-    pthread_rwlock_wrlock(&g_table);       /* no call in flight: nobody is stamping */
-    int n = __atomic_load_n(&g_trace.n, __ATOMIC_RELAXED);
-    n = n > TRACE_MAX ? TRACE_MAX : n;
-    n = n < max ? n : max;
-    for (int i = 0; i < n; i++) {
-        tags[i] = __atomic_load_n(&g_trace.tag[i], __ATOMIC_RELAXED); chunks[i] = __atomic_load_n(&g_trace.chunk[i], __ATOMIC_RELAXED);
-        ms[i] = 1e-6 * (double)(__atomic_load_n(&g_trace.t_ns[i], __ATOMIC_RELAXED) - __atomic_load_n(&g_trace.t_ns[0], __ATOMIC_RELAXED));
-    }
-    __atomic_store_n(&g_trace.on, on, __ATOMIC_RELAXED);
-    __atomic_store_n(&g_trace.seen, 0, __ATOMIC_RELAXED);
-    pthread_rwlock_unlock(&g_table);
-    return n;
-}
-#endif
-
-/* test hook (inert unless armed, include/eddsa_amd_debug.h): the next host-pointer call fails (hipErrorUnknown) after its
- * inputs were staged and its kernels launched, so that the error path's clean-up (the staging copies of secrets are wiped
- * there too) can be exercised */
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-int eddsa_amd_debug_fail_next_host_call(void)
-{
-    if (!__atomic_load_n(&g_hooks_armed, __ATOMIC_ACQUIRE)) return EDDSA_AMD_HOOKS_OFF;
-    __atomic_store_n(&g_fail_next_host_call, 1, __ATOMIC_RELEASE);
-    return 0;
-}
-#endif
-
-/* One host-pointer job on engine e (its device is current).
- * Chunk k travels on lane k mod 3: [wait for the lane's previous chunk, fetch and deliver its results] - stage and
- * upload - kernels, all on the lane's stream; copies and kernels of different lanes overlap.  How the KERNELS of
- * consecutive chunks are ordered is the job's choice (hjob.chain; tools/pipe_sweep.py has the measurements):
- *   in chunk order (each chunk's kernels wait for the previous lane's `kdone`): x25519, sign and the other fixed-base
- *     operations, whose chunk is one long kernel - side by side three of them share the chip, finish together, and the
- *     pipeline drains and refills in bursts (x25519 84-93 M/s against 103-105 in order);
- *   side by side: verify, whose three kernels per chunk leave ramps and tails that the neighbours fill (95.7 M/s
- *     against 79-86 in order).
- * `kdone` is recorded before a verify pass waits for its exact path, so that those few latency-bound waves never hold
- * up the next chunk (each lane's stream has its own workspace). */
 /* A ragged call's offset table (m + 1 entries of the caller's memory) must not decrease, and the bytes it spans must be an
  * amount a buffer can hold: everything below takes msg_off[k + 1] - msg_off[k] for a length.  Checked chunk by chunk, right
  * before the chunk's offsets are first used (the walk of chunk k runs beside the GPU work of chunk k - 1); a table that
@@ -505,141 +471,206 @@ static int offsets_ok(const uint64_t *off, size_t m)
     return !bad && off[m] - off[0] <= MSG_BYTES_MAX;
 }
 
-static int pipe_run_on(struct engine *e, const struct hjob *j, size_t n)
+/* dst[0 .. m] = the offset table off[0 .. m], rebased to 0 */
+static void offsets_rebase(uint64_t *dst, const uint64_t *off, size_t m)
 {
-    int rc = 0, wipes = 0;
-    struct pipe *p = &e->pipe;
-    int staged_in[PIPE_MAX_IN] = { 0 }, staged_msgs = 0, staged_out = 0;
-    if (n == 0) return 0;
-    const int ragged = j->has_msgs && j->msg_off != NULL;
-    const int tunable = j->stats == NULL;                       /* (a combination covers a fixed number of items) */
-    const size_t stage = tunable && g_pipe_stage ? g_pipe_stage : j->chunk ? j->chunk : PIPE_CHUNK;
-    const size_t first = tunable && g_pipe_first ? g_pipe_first : j->first_chunk ? j->first_chunk : PIPE_FIRST_CHUNK;
-    /* The offset table as a whole, before anything is touched: it must not end before it starts, nor span more than 2^46
-     * bytes (include/eddsa_amd.h).  Whether it DEcreases somewhere in between is checked chunk by chunk below, as each chunk is
-     * about to be staged (one pass over the table in step with the copies instead of a second one in front of them): a table
-     * that is bad further on is found after earlier chunks have run, the call then returns -hipErrorInvalidValue and its
-     * outputs are unspecified, as on every error. */
-    if (ragged && (j->msg_off[n] < j->msg_off[0] || j->msg_off[n] - j->msg_off[0] > MSG_BYTES_MAX)) return -(int)hipErrorInvalidValue;
-    const size_t msg_total = !j->has_msgs ? 0 : ragged ? (size_t)(j->msg_off[n] - j->msg_off[0]) : n * j->msg_len;
-    /* one chunk, one lane (any); several chunks - and the batch verification, whose statistics live in the pipe - all of them */
-    const int all = j->stats != NULL || n > first;
-    const int base = lanes_acquire(e, all);
-    if (base < 0) return base;
-#define LANE_OF(k) (&p->lane[all ? (k) % PIPE_LANES : (unsigned)base])
-    if (TRACE_ON() && !j->traced) TRACE_RESTART();
-    TRACE(0, 0);
-    {
-        struct lane *prev = NULL;
-        for (int i = 0; i < j->n_in; i++)
-            staged_in[i] = !j->src_pinned && !(n * j->in_w[i] >= PIN_CHECK_MIN && is_pinned(j->in[i], n * j->in_w[i]));
-        staged_msgs = !j->src_pinned && !(msg_total >= PIN_CHECK_MIN && is_pinned(ragged ? j->msgs + j->msg_off[0] : j->msgs, msg_total));
-        staged_out = !j->src_pinned && !(n * j->out_w >= PIN_CHECK_MIN && is_pinned(j->out, n * j->out_w));
-        if (j->stats) {
-            TRY(hipMemsetAsync(p->d_stats, 0, 16, p->lane[0].st));
-            TRY(hipStreamSynchronize(p->lane[0].st));           /* the other lanes' kernels add to it too */
+    const uint64_t base0 = off[0];
+    for (size_t t = 0; t <= m; t++) dst[t] = off[t] - base0;
+}
+
+/* one host-pointer call in flight: the job, how it is cut into chunks, its lanes and which of its arrays are staged */
+struct pcall {
+    struct engine *e; const struct hjob *j; size_t n;
+    int ragged;                                /* the messages come with an offset table */
+    size_t first, stage;                       /* items of the first chunk and of a full stage */
+    int all, base;                             /* the call holds all lanes; else the one lane it holds */
+    int staged_in[PIPE_MAX_IN], staged_msgs, staged_out;   /* 0: the caller's array is page-locked and used in place */
+    int wipes;                                 /* zeroing of pinned staging buffers queued with the copier pool (pool_wait) */
+};
+
+/* chunk k travels on lane k mod 3 (a call of one chunk: on the lane it was given) */
+static struct lane *call_lane(const struct pcall *c, unsigned k) { return &c->e->pipe.lane[c->all ? k % PIPE_LANES : (unsigned)c->base]; }
+
+/* items of chunk k, `left` items being still to do: the first chunk doubles up to the stage size */
+static size_t chunk_items(const struct pcall *c, unsigned k, size_t left)
+{
+    size_t m = c->first << (k < 8 ? k : 8);
+    if (m > c->stage) m = c->stage;
+    return !c->all || m > left || left - m < m / 2 ? left : m;   /* (a short tail travels with the last chunk) */
+}
+
+/* stage and upload items lo .. lo + m of the call on lane L: inputs, message bytes, offset table; room for the output */
+static int chunk_upload(const struct pcall *c, struct lane *L, size_t lo, size_t m)
+{
+    const struct hjob *j = c->j;
+    int rc = 0;
+    for (int i = 0; i < j->op->n_in; i++) {
+        if ((rc = dev_grow(&L->d_in[i], &L->d_in_cap[i], m * in_w(j, i), L->st))) goto out;
+        if ((rc = lane_upload(L, L->d_in[i], &L->h_in[i], &L->h_in_cap[i], j->in[i] + lo * in_w(j, i), m * in_w(j, i), c->staged_in[i]))) goto out;
+    }
+    if (c->staged_in[0]) L->used_in0 = m * in_w(j, 0);
+    if (j->op->has_msgs) {
+        /* ragged messages: the chunk's own bytes, msg_off[lo] .. msg_off[lo + m) */
+        const size_t bytes = c->ragged ? (size_t)(j->msg_off[lo + m] - j->msg_off[lo]) : m * j->msg_len;
+        const uint8_t *src = c->ragged ? j->msgs + j->msg_off[lo] : j->msgs + lo * j->msg_len;
+        if ((rc = dev_grow(&L->d_msgs, &L->d_msgs_cap, bytes, L->st))) goto out;
+        if ((rc = lane_upload(L, L->d_msgs, &L->h_msgs, &L->h_msgs_cap, src, bytes, c->staged_msgs))) goto out;
+    }
+    if (c->ragged) {
+        /* ... and its own offset table, rebased to the chunk's first byte (the kernels index it by the item's
+         * number inside the chunk).  A table that starts at 0 in page-locked memory - the combiner's - goes as it is. */
+        const size_t ob = (m + 1) * sizeof(uint64_t);
+        const int as_it_is = j->src_pinned && j->msg_off[lo] == 0;
+        if ((rc = dev_grow(&L->d_off, &L->d_off_cap, ob, L->st))) goto out;
+        if (!as_it_is && (rc = host_grow(&L->h_off, &L->h_off_cap, ob))) goto out;
+        if (!as_it_is) offsets_rebase((uint64_t *)L->h_off, j->msg_off + lo, m);
+        TRY(hipMemcpyAsync(L->d_off, as_it_is ? (const void *)(j->msg_off + lo) : L->h_off, ob, hipMemcpyHostToDevice, L->st));
+    }
+    rc = dev_grow(&L->d_out, &L->d_out_cap, m * j->op->out_w, L->st);
+out:
+    return rc;
+}
+
+/* queue the kernels of chunk k (m items, on lane L) - behind those of the chunk before it, on lane `prev`, where chunks run in order */
+static int chunk_launch(const struct pcall *c, struct lane *L, const struct lane *prev, unsigned k, size_t m)
+{
+    const struct hjob *j = c->j;
+    int rc = 0;
+    if (prev && (g_pipe_chain < 0 ? j->op->chain : g_pipe_chain)) TRY(hipStreamWaitEvent(L->st, prev->kdone, 0));      /* kernels in chunk order */
+    const struct chunk ch = { .d_out = (uint8_t *)L->d_out, .d_in = (uint8_t *const *)L->d_in, .d_msgs = (const uint8_t *)L->d_msgs, .m = m, .st = L->st,
+                              .d_off = c->ragged ? (const uint64_t *)L->d_off : NULL, .kdone = L->kdone, .d_stats = j->stats ? c->e->pipe.d_stats : NULL };
+    rc = j->op->run(c->e, j, &ch);
+    TRACE(3, k);
+    if (!rc && __atomic_exchange_n(&g_fail_next_host_call, 0, __ATOMIC_ACQ_REL)) rc = -(int)hipErrorUnknown;
+out:
+    return rc;
+}
+
+/* note where the results of the chunk on lane L (items lo .. lo + m) go: the download is queued by lane_drain, once the
+ * kernels are done - except for a call of one chunk, which has no uploads to hold up: everything in order, one wait */
+static int chunk_note_download(const struct pcall *c, struct lane *L, size_t lo, size_t m)
+{
+    const struct hjob *j = c->j;
+    int rc = 0;
+    L->pend_via = NULL;
+    if (c->staged_out) {
+        if ((rc = host_grow(&L->h_out, &L->h_out_cap, m * j->op->out_w))) return rc;
+        L->pend_via = (uint8_t *)L->h_out;
+    }
+    L->pend_dst = j->out + lo * j->op->out_w; L->pend_dev = (uint8_t *)L->d_out; L->pend_bytes = m * j->op->out_w;
+    L->pend_queued = 0;
+    if (lo == 0 && m == c->n) rc = lane_download(L, j->op->wipe);
+    return rc;
+}
+
+/* the chunks of the call, one after the other; on return without an error every lane of the call is drained */
+static int call_chunks(struct pcall *c)
+{
+    const struct hjob *j = c->j;
+    const int wipe = j->op->wipe;
+    struct lane *prev = NULL;
+    int rc = 0;
+    size_t lo = 0;
+    for (unsigned k = 0; lo < c->n; k++) {
+        struct lane *L = call_lane(c, k);
+        const size_t m = chunk_items(c, k, c->n - lo);
+        if (c->ragged && !offsets_ok(j->msg_off + lo, m)) return -(int)hipErrorInvalidValue;   /* before anything of the chunk is staged */
+        /* the lane's previous chunk (k - 3): the two chunks after it keep the GPU busy meanwhile */
+        if (k >= PIPE_LANES && (rc = lane_drain(L, wipe, NULL))) goto out;    /* (every call leaves its lanes drained) */
+        TRACE(1, k);
+        if ((rc = chunk_upload(c, L, lo, m))) goto out;
+        TRACE(2, k);
+        rc = chunk_launch(c, L, prev, k, m);
+        prev = L;
+        if (rc || (rc = chunk_note_download(c, L, lo, m))) goto out;
+        /* secrets do not outlive the call in HBM */
+        if (wipe & WIPE_IN0) TRY(hipMemsetAsync(L->d_in[0], 0, m * in_w(j, 0), L->st));
+        lo += m;
+        TRACE(4, k);
+        if (lo >= c->n) {                  /* the chunks still in flight, oldest first */
+            for (unsigned t = k + 1 < PIPE_LANES ? PIPE_LANES - k : 1; t <= PIPE_LANES; t++)
+                if ((rc = lane_drain(call_lane(c, k + t), wipe, &c->wipes))) goto out;
+            TRACE(5, k);
         }
-        size_t lo = 0;
-        for (unsigned k = 0; lo < n; k++) {
-            struct lane *L = LANE_OF(k);
-            size_t m = first << (k < 8 ? k : 8);
-            if (m > stage) m = stage;
-            if (!all || m > n - lo || n - lo - m < m / 2) m = n - lo;   /* (a short tail travels with the last chunk) */
-            if (ragged && !offsets_ok(j->msg_off + lo, m)) { rc = -(int)hipErrorInvalidValue; goto out; }   /* before anything of the chunk is staged */
-            /* the lane's previous chunk (k - 3): the two chunks after it keep the GPU busy meanwhile */
-            if (k >= PIPE_LANES && (rc = lane_drain(L, j->wipe, NULL))) goto out;    /* (every call leaves its lanes drained) */
-            TRACE(1, k);
-            for (int i = 0; i < j->n_in; i++) {
-                if ((rc = dev_grow(&L->d_in[i], &L->d_in_cap[i], m * j->in_w[i], L->st))) goto out;
-                if ((rc = lane_upload(L, L->d_in[i], &L->h_in[i], &L->h_in_cap[i], j->in[i] + lo * j->in_w[i], m * j->in_w[i], staged_in[i]))) goto out;
-            }
-            if (staged_in[0]) L->used_in0 = m * j->in_w[0];
-            if (j->has_msgs) {
-                /* ragged messages: the chunk's own bytes, msg_off[lo] .. msg_off[lo + m) */
-                const size_t bytes = ragged ? (size_t)(j->msg_off[lo + m] - j->msg_off[lo]) : m * j->msg_len;
-                const uint8_t *src = ragged ? j->msgs + j->msg_off[lo] : j->msgs + lo * j->msg_len;
-                if ((rc = dev_grow(&L->d_msgs, &L->d_msgs_cap, bytes, L->st))) goto out;
-                if ((rc = lane_upload(L, L->d_msgs, &L->h_msgs, &L->h_msgs_cap, src, bytes, staged_msgs))) goto out;
-            }
-            if (ragged) {
-                /* ... and its own offset table, rebased to the chunk's first byte (the kernels index it by the item's
-                 * number inside the chunk).  A table that starts at 0 in page-locked memory - the combiner's - goes as it is. */
-                const size_t ob = (m + 1) * sizeof(uint64_t);
-                if ((rc = dev_grow(&L->d_off, &L->d_off_cap, ob, L->st))) goto out;
-                if (j->src_pinned && j->msg_off[lo] == 0) {
-                    TRY(hipMemcpyAsync(L->d_off, j->msg_off + lo, ob, hipMemcpyHostToDevice, L->st));
-                } else {
-                    if ((rc = host_grow(&L->h_off, &L->h_off_cap, ob))) goto out;
-                    uint64_t *ho = (uint64_t *)L->h_off;
-                    const uint64_t base0 = j->msg_off[lo];
-                    for (size_t t = 0; t <= m; t++) ho[t] = j->msg_off[lo + t] - base0;
-                    TRY(hipMemcpyAsync(L->d_off, ho, ob, hipMemcpyHostToDevice, L->st));
-                }
-            }
-            if ((rc = dev_grow(&L->d_out, &L->d_out_cap, m * j->out_w, L->st))) goto out;
-            TRACE(2, k);
-            if (prev && (g_pipe_chain < 0 ? j->chain : g_pipe_chain)) TRY(hipStreamWaitEvent(L->st, prev->kdone, 0));      /* kernels in chunk order */
-            {
-                struct hjob jj = *j;
-                jj.stats = j->stats ? p->d_stats : NULL;
-                rc = j->run(e, &jj, (uint8_t *)L->d_out, (uint8_t *const *)L->d_in, (const uint8_t *)L->d_msgs,
-                            ragged ? (const uint64_t *)L->d_off : NULL, j->msg_len, m, L->st, L->kdone);
-            }
-            prev = L;
-            TRACE(3, k);
-            if (!rc && __atomic_exchange_n(&g_fail_next_host_call, 0, __ATOMIC_ACQ_REL)) rc = -(int)hipErrorUnknown;
-            if (rc) goto out;
-            /* the download: queued by lane_drain, once the kernels are done */
-            L->pend_via = NULL;
-            if (staged_out) {
-                if ((rc = host_grow(&L->h_out, &L->h_out_cap, m * j->out_w))) goto out;
-                L->pend_via = (uint8_t *)L->h_out;
-            }
-            L->pend_dst = j->out + lo * j->out_w; L->pend_dev = (uint8_t *)L->d_out; L->pend_bytes = m * j->out_w;
-            L->pend_queued = 0;
-            if (k == 0 && m == n) {            /* a call of one chunk has no uploads to hold up: everything in order, one wait */
-                TRY(hipMemcpyAsync(L->pend_via ? L->pend_via : (void *)L->pend_dst, L->pend_dev, L->pend_bytes, hipMemcpyDeviceToHost, L->st));
-                if (j->wipe & WIPE_OUT) TRY(hipMemsetAsync(L->pend_dev, 0, L->pend_bytes, L->st));
-                L->pend_queued = 1;
-            }
-            /* secrets do not outlive the call in HBM */
-            if (j->wipe & WIPE_IN0) TRY(hipMemsetAsync(L->d_in[0], 0, m * j->in_w[0], L->st));
-            lo += m;
-            TRACE(4, k);
-            if (lo >= n) {                     /* the chunks still in flight, oldest first */
-                for (unsigned t = k + 1 < PIPE_LANES ? PIPE_LANES - k : 1; t <= PIPE_LANES; t++)
-                    if ((rc = lane_drain(LANE_OF(k + t), j->wipe, &wipes))) goto out;
-                TRACE(5, k);
-            }
-        }
-        if (j->stats) {
-            TRY(hipMemcpyAsync(p->h_stats, p->d_stats, 16, hipMemcpyDeviceToHost, p->lane[0].st));
-            TRY(hipStreamSynchronize(p->lane[0].st));
-            memcpy(j->stats, p->h_stats, 16);
-        }
-        /* every lane of the call has been waited for: what a verify pass's kernels reported (a hand-off given up) is this
-         * call's error (the other operations' kernels have nothing to report: a sign call does not take a verify call's word) */
-        if (j->out_w == 1 && (rc = take_async_error(e))) goto out;
     }
 out:
-    if (rc) {
-        /* a failed call must not leave its secrets behind either (best effort: whole buffers, HBM and pinned) */
-        for (int l = 0; l < PIPE_LANES; l++) {
-            struct lane *L = &p->lane[l];
-            if (!all && l != base) continue;
-            HIP_NOTE(hipStreamSynchronize(L->st));
-            L->pend_bytes = 0; L->used_in0 = 0;
-            if ((j->wipe & WIPE_IN0) && L->d_in[0]) HIP_NOTE(hipMemsetAsync(L->d_in[0], 0, L->d_in_cap[0], L->st));
-            if ((j->wipe & WIPE_OUT) && L->d_out) HIP_NOTE(hipMemsetAsync(L->d_out, 0, L->d_out_cap, L->st));
-            if (j->wipe) HIP_NOTE(hipStreamSynchronize(L->st));
-            if ((j->wipe & WIPE_IN0) && L->h_in[0]) pool_submit(&wipes, (uint8_t *)L->h_in[0], NULL, L->h_in_cap[0], 0);
-            if ((j->wipe & WIPE_OUT) && L->h_out) pool_submit(&wipes, (uint8_t *)L->h_out, NULL, L->h_out_cap, 0);
-        }
+    return rc;
+}
+
+/* a failed call must not leave its secrets behind either (best effort: whole buffers, HBM and pinned) */
+static void call_scrub(struct pcall *c)
+{
+    const int wipe = c->j->op->wipe;
+    for (int l = 0; l < PIPE_LANES; l++) {
+        struct lane *L = &c->e->pipe.lane[l];
+        if (!c->all && l != c->base) continue;
+        HIP_NOTE(hipStreamSynchronize(L->st));
+        L->pend_bytes = 0; L->used_in0 = 0;
+        if ((wipe & WIPE_IN0) && L->d_in[0]) HIP_NOTE(hipMemsetAsync(L->d_in[0], 0, L->d_in_cap[0], L->st));
+        if ((wipe & WIPE_OUT) && L->d_out) HIP_NOTE(hipMemsetAsync(L->d_out, 0, L->d_out_cap, L->st));
+        if (wipe) HIP_NOTE(hipStreamSynchronize(L->st));
+        if ((wipe & WIPE_IN0) && L->h_in[0]) pool_submit(&c->wipes, (uint8_t *)L->h_in[0], NULL, L->h_in_cap[0], 0);
+        if ((wipe & WIPE_OUT) && L->h_out) pool_submit(&c->wipes, (uint8_t *)L->h_out, NULL, L->h_out_cap, 0);
     }
-    if (j->wipe) pool_wait(&wipes);            /* nothing secret outlives the call in the pinned staging buffers */
+}
+
+/* One host-pointer job on engine e (its device is current).
+ * Chunk k travels on lane k mod 3: [wait for the lane's previous chunk, fetch and deliver its results] - stage and
+ * upload - kernels, all on the lane's stream; copies and kernels of different lanes overlap.  How the KERNELS of
+ * consecutive chunks are ordered is the operation's choice (op.chain; tools/pipe_sweep.py has the measurements):
+ *   in chunk order (each chunk's kernels wait for the previous lane's `kdone`): x25519, sign and the other fixed-base
+ *     operations, whose chunk is one long kernel - side by side three of them share the chip, finish together, and the
+ *     pipeline drains and refills in bursts (x25519 84-93 M/s against 103-105 in order);
+ *   side by side: verify, whose three kernels per chunk leave ramps and tails that the neighbours fill (95.7 M/s
+ *     against 79-86 in order).
+ * `kdone` is recorded before a verify pass waits for its exact path, so that those few latency-bound waves never hold
+ * up the next chunk (each lane's stream has its own workspace).
+ * traced: the caller (the combiner's leader) has started the call's trace already. */
+static int pipe_run_on(struct engine *e, const struct hjob *j, size_t n, int traced)
+{
+    struct pipe *p = &e->pipe;
+    int rc = 0;
+    if (n == 0) return 0;
+    struct pcall c = { .e = e, .j = j, .n = n, .ragged = j->op->has_msgs && j->msg_off != NULL };
+    const int tunable = j->stats == NULL;                       /* (a combination covers a fixed number of items) */
+    c.stage = tunable && g_pipe_stage ? g_pipe_stage : j->op->chunk ? j->op->chunk : PIPE_CHUNK;
+    c.first = tunable && g_pipe_first ? g_pipe_first : j->op->first_chunk ? j->op->first_chunk : PIPE_FIRST_CHUNK;
+    /* The offset table as a whole, before anything is touched: it must not end before it starts, nor span more than 2^46
+     * bytes (include/eddsa_amd.h).  Whether it DEcreases somewhere in between is checked chunk by chunk (call_chunks), as each
+     * chunk is about to be staged (one pass over the table in step with the copies instead of a second one in front of them): a
+     * table that is bad further on is found after earlier chunks have run, the call then returns -hipErrorInvalidValue and its
+     * outputs are unspecified, as on every error. */
+    if (c.ragged && (j->msg_off[n] < j->msg_off[0] || j->msg_off[n] - j->msg_off[0] > MSG_BYTES_MAX)) return -(int)hipErrorInvalidValue;
+    /* one chunk, one lane (any); several chunks - and the batch verification, whose statistics live in the pipe - all of them */
+    c.all = j->stats != NULL || n > c.first;
+    c.base = lanes_acquire(e, c.all);
+    if (c.base < 0) return c.base;
+    if (TRACE_ON() && !traced) TRACE_RESTART();
+    TRACE(0, 0);
+    /* which of the call's arrays go through pinned staging: all, unless the array is large enough to ask and page-locked */
+    const size_t msg_total = !j->op->has_msgs ? 0 : c.ragged ? (size_t)(j->msg_off[n] - j->msg_off[0]) : n * j->msg_len;
+    for (int i = 0; i < j->op->n_in; i++)
+        c.staged_in[i] = !j->src_pinned && !(n * in_w(j, i) >= PIN_CHECK_MIN && is_pinned(j->in[i], n * in_w(j, i)));
+    c.staged_msgs = !j->src_pinned && !(msg_total >= PIN_CHECK_MIN && is_pinned(c.ragged ? j->msgs + j->msg_off[0] : j->msgs, msg_total));
+    c.staged_out = !j->src_pinned && !(n * j->op->out_w >= PIN_CHECK_MIN && is_pinned(j->out, n * j->op->out_w));
+    if (j->stats) {
+        TRY(hipMemsetAsync(p->d_stats, 0, 16, p->lane[0].st));
+        TRY(hipStreamSynchronize(p->lane[0].st));           /* the other lanes' kernels add to it too */
+    }
+    if ((rc = call_chunks(&c))) goto out;
+    if (j->stats) {
+        TRY(hipMemcpyAsync(p->h_stats, p->d_stats, 16, hipMemcpyDeviceToHost, p->lane[0].st));
+        TRY(hipStreamSynchronize(p->lane[0].st));
+        memcpy(j->stats, p->h_stats, 16);
+    }
+    /* every lane of the call has been waited for: what a verify pass's kernels reported (a hand-off given up) is this
+     * call's error (the other operations' kernels have nothing to report: a sign call does not take a verify call's word) */
+    if (j->op->reports) rc = take_async_error(e);
+out:
+    if (rc) call_scrub(&c);
+    if (j->op->wipe) pool_wait(&c.wipes);      /* nothing secret outlives the call in the pinned staging buffers */
     TRACE(6, 0);
-#undef LANE_OF
-    lanes_release(e, all, base);
+    lanes_release(e, c.all, c.base);
     return rc;
 }
 
@@ -674,43 +705,22 @@ void combiner_release(struct combiner *q)
     pthread_mutex_destroy(&q->lk);
 }
 
-/* diagnostic: combined launches and the items they carried on the default device since its engine was built */
-#ifdef EDDSA_AMD_DEBUG_BUILD   /* include/eddsa_amd_debug.h: only libeddsa_amd_debug.so has it */
-int eddsa_amd_combiner_stats(uint64_t out[2])
-{
-    struct call c;
-    int rc = enter(&c, -1);
-    if (rc) return rc;
-    pthread_mutex_lock(&c.e->comb_q.lk);
-    out[0] = c.e->comb_q.batches; out[1] = c.e->comb_q.items;
-    pthread_mutex_unlock(&c.e->comb_q.lk);
-    leave(&c);
-    return 0;
-}
-#endif
-
-static int64_t now_ns(void)
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (int64_t)ts.tv_sec * 1000000000 + ts.tv_nsec;
-}
-
 /* the leader's work: pack the requests of `batch` (a list through ->next, all of one operation), run them as one job
  * from the operation's pinned buffers, scatter the results.  Returns the job's status. */
 static int combiner_run(struct engine *e, struct comb_kind *K, struct creq *batch, size_t total)
 {
     const struct hjob *j0 = batch->j;
+    const struct op *op = j0->op;
     int rc = 0, same_len = 1;
     size_t msg_bytes = 0;
     for (struct creq *r = batch; r; r = r->next) {
         if (r->j->msg_len != j0->msg_len) same_len = 0;
         msg_bytes += r->n * r->j->msg_len;
     }
-    for (int i = 0; i < j0->n_in; i++) if ((rc = host_grow(&K->h_in[i], &K->h_in_cap[i], total * j0->in_w[i]))) return rc;
-    if (j0->has_msgs && (rc = host_grow(&K->h_msgs, &K->h_msgs_cap, msg_bytes))) return rc;
-    if ((rc = host_grow(&K->h_out, &K->h_out_cap, total * j0->out_w))) return rc;
-    if (j0->has_msgs && !same_len) {
+    for (int i = 0; i < op->n_in; i++) if ((rc = host_grow(&K->h_in[i], &K->h_in_cap[i], total * op->in_w[i]))) return rc;
+    if (op->has_msgs && (rc = host_grow(&K->h_msgs, &K->h_msgs_cap, msg_bytes))) return rc;
+    if ((rc = host_grow(&K->h_out, &K->h_out_cap, total * op->out_w))) return rc;
+    if (op->has_msgs && !same_len) {
         void *p = K->h_off;
         rc = host_grow(&p, &K->h_off_cap, (total + 1) * sizeof(uint64_t));
         K->h_off = (uint64_t *)p;
@@ -718,33 +728,31 @@ static int combiner_run(struct engine *e, struct comb_kind *K, struct creq *batc
     }
     size_t at = 0, mat = 0;
     for (struct creq *r = batch; r; r = r->next) {
-        for (int i = 0; i < j0->n_in; i++) memcpy((uint8_t *)K->h_in[i] + at * j0->in_w[i], r->j->in[i], r->n * j0->in_w[i]);
-        if (j0->has_msgs) {
+        for (int i = 0; i < op->n_in; i++) memcpy((uint8_t *)K->h_in[i] + at * op->in_w[i], r->j->in[i], r->n * op->in_w[i]);
+        if (op->has_msgs) {
             if (r->n * r->j->msg_len != 0) memcpy((uint8_t *)K->h_msgs + mat, r->j->msgs, r->n * r->j->msg_len);
             if (!same_len) for (size_t k = 0; k < r->n; k++) K->h_off[at + k] = mat + k * r->j->msg_len;
             mat += r->n * r->j->msg_len;
         }
         at += r->n;
     }
-    if (j0->has_msgs && !same_len) K->h_off[total] = mat;
+    if (op->has_msgs && !same_len) K->h_off[total] = mat;
     struct hjob big = *j0;
-    for (int i = 0; i < j0->n_in; i++) big.in[i] = (const uint8_t *)K->h_in[i];
+    for (int i = 0; i < op->n_in; i++) big.in[i] = (const uint8_t *)K->h_in[i];
     big.msgs = (const uint8_t *)K->h_msgs;
-    big.msg_off = j0->has_msgs && !same_len ? K->h_off : NULL;
+    big.msg_off = op->has_msgs && !same_len ? K->h_off : NULL;
     big.out = (uint8_t *)K->h_out;
-    big.kind = 0;
     big.src_pinned = 1;
-    big.traced = 1;
     TRACE(9, (unsigned)total);
-    rc = pipe_run_on(e, &big, total);
+    rc = pipe_run_on(e, &big, total, 1);
     at = 0;
     for (struct creq *r = batch; r && !rc; r = r->next) {
-        memcpy(r->j->out, (uint8_t *)K->h_out + at * j0->out_w, r->n * j0->out_w);
+        memcpy(r->j->out, (uint8_t *)K->h_out + at * op->out_w, r->n * op->out_w);
         at += r->n;
     }
     /* the packed copies of secrets go as well */
-    if (j0->wipe & WIPE_IN0) memset(K->h_in[0], 0, total * j0->in_w[0]);
-    if (j0->wipe & WIPE_OUT) memset(K->h_out, 0, total * j0->out_w);
+    if (op->wipe & WIPE_IN0) memset(K->h_in[0], 0, total * op->in_w[0]);
+    if (op->wipe & WIPE_OUT) memset(K->h_out, 0, total * op->out_w);
     TRACE(10, (unsigned)total);
     if (TRACE_ON() == 2 && total >= 32 && __atomic_add_fetch(&g_trace.seen, 1, __ATOMIC_RELAXED) == 20)
         __atomic_store_n(&g_trace.on, 0, __ATOMIC_RELAXED);   /* on = 2: keep the 20th launch that carried 32 calls or more */
@@ -757,13 +765,87 @@ static int combiner_run(struct engine *e, struct comb_kind *K, struct creq *batc
  * caller it carried is woken at once and leaves on its own `done` flag without touching the queue's mutex (with a
  * condition variable the 64 callers of a launch re-acquired the mutex one after the other, a context switch each,
  * which cost more than the GPU pass). */
-static void gen_wait(uint32_t *gen, uint32_t seen)
+static void gen_wait(uint32_t *gen, uint32_t seen) { (void)syscall(SYS_futex, gen, FUTEX_WAIT_PRIVATE, seen, NULL, NULL, 0); }
+static void gen_wake_all(uint32_t *gen) { (void)syscall(SYS_futex, gen, FUTEX_WAKE_PRIVATE, INT_MAX, NULL, NULL, 0); }
+
+/* Under contention the callers of the launch that has just finished are about to queue again (they do within
+ * microseconds of being woken): give them a moment, or the callers split into two camps that take turns and
+ * every launch carries half of them.  Expected: whoever was already waiting when that launch ended, plus the
+ * calls it carried.  Never long; a lone caller (the previous launch carried one call) never waits.
+ * Entered and left with q->lk held; while the leader yields, the lock is dropped so that the callers can queue. */
+static void leader_gather(struct combiner *q, const struct comb_kind *K)
 {
-    (void)syscall(SYS_futex, gen, FUTEX_WAIT_PRIVATE, seen, NULL, NULL, 0);
+    const unsigned want = K->waiting_at_end + K->last_reqs;
+    if (K->last_reqs <= 1 || K->queued >= want) return;
+    const int64_t until = now_ns() + COMBINE_GATHER_NS;
+    pthread_mutex_unlock(&q->lk);
+    for (;;) {
+        sched_yield();
+        pthread_mutex_lock(&q->lk);
+        if (K->queued >= want || now_ns() >= until) break;
+        pthread_mutex_unlock(&q->lk);
+    }
 }
-static void gen_wake_all(uint32_t *gen)
+
+/* Take everything queued for operation `kind` off the queue, up to the limits of one launch (the leader's own request is
+ * among it unless thousands are ahead of it: then it leads again): a list through ->next.  Entered and left with q->lk held. */
+static struct creq *batch_unlink(struct combiner *q, struct comb_kind *K, int kind, size_t *total, size_t *reqs)
 {
-    (void)syscall(SYS_futex, gen, FUTEX_WAKE_PRIVATE, INT_MAX, NULL, NULL, 0);
+    struct creq *batch = NULL, *btail = NULL, **pp = &q->head, *last = NULL;
+    size_t bytes = 0;
+    *total = *reqs = 0;
+    while (*pp) {
+        struct creq *r = *pp;
+        const size_t rb = r->j->op->has_msgs ? r->n * r->j->msg_len : 0;
+        if (r->j->op->kind == kind && *total + r->n <= COMBINE_MAX_BATCH && (*reqs == 0 || bytes + rb <= COMBINE_MAX_BATCH_BYTES)) {
+            *pp = r->next;
+            r->next = NULL;
+            if (btail) btail->next = r; else batch = r;
+            btail = r;
+            *total += r->n; ++*reqs; bytes += rb;
+            K->queued--;
+        } else { last = r; pp = &r->next; }
+    }
+    q->tail = last;
+    return batch;
+}
+
+/* A merged launch shares one status, and the eddsa.h callers abort() on failure: before anybody is told, every
+ * request gets a run of its own (a transient error, or the packed batch's staging allocation, need not concern
+ * the others; a request that is itself the cause fails again, alone) */
+/* ... but not without end: a batch holds up to 16 384 requests, and when the cause is the device (lost, out of
+ * memory) every retry stages secrets, fails, waits and wipes while all callers stay blocked.  After
+ * COMBINE_RETRY_GIVE_UP retries in a row that end with the batch's own error the rest are told that error. */
+/* Only for errors of the DEVICE: an error a caller can bring about by itself (an invalid argument, a bad offset
+ * table) says nothing about the next request - four faulty callers in a row must not fail everybody behind
+ * them - so such a batch is retried request by request to the end. */
+/* Called without q->lk (no lock is held while a job runs); every r->rc of the batch holds rc, the launch's error. */
+static void batch_retry(struct engine *e, struct creq *batch, int rc)
+{
+    const int device_fault = rc != -(int)hipErrorInvalidValue && rc != -(int)hipErrorInvalidDevicePointer;
+    int same = 0;
+    for (struct creq *r = batch; r; r = r->next) {
+        if (device_fault && same >= COMBINE_RETRY_GIVE_UP) continue;
+        r->rc = pipe_run_on(e, r->j, r->n, 1);
+        same = r->rc == rc ? same + 1 : 0;
+    }
+}
+
+/* Hand the batch's results to its callers and wake them.  Entered and left without q->lk, which it takes for the bookkeeping. */
+static void batch_publish(struct combiner *q, struct comb_kind *K, struct creq *batch, size_t reqs)
+{
+    pthread_mutex_lock(&q->lk);
+    q->batches++; q->items += reqs;
+    K->last_reqs = (unsigned)reqs;
+    K->waiting_at_end = K->queued;
+    for (struct creq *r = batch, *nx; r; r = nx) {  /* a caller may return (and its request vanish) the moment `done` is set */
+        nx = r->next;
+        __atomic_store_n(&r->done, 1, __ATOMIC_RELEASE);
+    }
+    K->active = 0;
+    __atomic_add_fetch(&K->gen, 1, __ATOMIC_RELEASE);
+    pthread_mutex_unlock(&q->lk);
+    gen_wake_all(&K->gen);
 }
 
 /* One leader per OPERATION at a time: the calls queued for verify travel in one launch while, side by side on another
@@ -772,14 +854,13 @@ static void gen_wake_all(uint32_t *gen)
 static int combiner_submit(struct engine *e, const struct hjob *j, size_t n)
 {
     struct combiner *q = &e->comb_q;
-    struct comb_kind *K = &q->kind[j->kind];
+    struct comb_kind *K = &q->kind[j->op->kind];
     struct creq me = { j, n, 0, 0, NULL };
     pthread_mutex_lock(&q->lk);
     if (q->tail) q->tail->next = &me; else q->head = &me;
     q->tail = &me;
     K->queued++;
-    for (;;) {
-        if (__atomic_load_n(&me.done, __ATOMIC_ACQUIRE)) break;
+    while (!__atomic_load_n(&me.done, __ATOMIC_ACQUIRE)) {    /* (q->lk is held here) */
         if (K->active) {
             const uint32_t seen = __atomic_load_n(&K->gen, __ATOMIC_RELAXED);
             pthread_mutex_unlock(&q->lk);
@@ -788,85 +869,18 @@ static int combiner_submit(struct engine *e, const struct hjob *j, size_t n)
             pthread_mutex_lock(&q->lk);
             continue;
         }
-        K->active = 1;
+        K->active = 1;                                 /* this thread leads one launch */
         if (TRACE_ON()) TRACE_RESTART();
         TRACE(7, 0);
-        /* Under contention the callers of the launch that has just finished are about to queue again (they do within
-         * microseconds of being woken): give them a moment, or the callers split into two camps that take turns and
-         * every launch carries half of them.  Expected: whoever was already waiting when that launch ended, plus the
-         * calls it carried.  Never long; a lone caller (the previous launch carried one call) never waits. */
-        {
-            const unsigned want = K->waiting_at_end + K->last_reqs;
-            if (K->last_reqs > 1 && K->queued < want) {
-                const int64_t until = now_ns() + COMBINE_GATHER_NS;
-                pthread_mutex_unlock(&q->lk);
-                for (;;) {
-                    sched_yield();
-                    pthread_mutex_lock(&q->lk);
-                    if (K->queued >= want || now_ns() >= until) break;
-                    pthread_mutex_unlock(&q->lk);
-                }
-            }
-        }
-        /* everything queued for this operation (this thread's own request is among it unless thousands are ahead of it:
-         * then it leads again) */
+        leader_gather(q, K);
         TRACE(8, K->queued);
-        struct creq *batch = NULL, *btail = NULL, **pp = &q->head, *last = NULL;
-        size_t total = 0, reqs = 0, bytes = 0;
-        while (*pp) {
-            struct creq *r = *pp;
-            const size_t rb = r->j->has_msgs ? r->n * r->j->msg_len : 0;
-            if (r->j->kind == j->kind && total + r->n <= COMBINE_MAX_BATCH && (reqs == 0 || bytes + rb <= COMBINE_MAX_BATCH_BYTES)) {
-                *pp = r->next;
-                r->next = NULL;
-                if (btail) btail->next = r; else batch = r;
-                btail = r;
-                total += r->n; reqs++; bytes += rb;
-                K->queued--;
-            } else {
-                last = r;
-                pp = &r->next;
-            }
-        }
-        q->tail = last;
-        pthread_mutex_unlock(&q->lk);
-        struct hjob own = *j;
-        own.traced = 1;
-        const int rc = reqs == 1 && batch == &me ? pipe_run_on(e, &own, n) : combiner_run(e, K, batch, total);
+        size_t total, reqs;
+        struct creq *batch = batch_unlink(q, K, j->op->kind, &total, &reqs);
+        pthread_mutex_unlock(&q->lk);                  /* no lock is held while a job runs */
+        const int rc = reqs == 1 && batch == &me ? pipe_run_on(e, j, n, 1) : combiner_run(e, K, batch, total);
         for (struct creq *r = batch; r; r = r->next) r->rc = rc;
-        if (rc && reqs > 1) {
-            /* A merged launch shares one status, and the eddsa.h callers abort() on failure: before anybody is told, every
-             * request gets a run of its own (a transient error, or the packed batch's staging allocation, need not concern
-             * the others; a request that is itself the cause fails again, alone) */
-            /* ... but not without end: a batch holds up to 16 384 requests, and when the cause is the device (lost, out of
-             * memory) every retry stages secrets, fails, waits and wipes while all callers stay blocked.  After
-             * COMBINE_RETRY_GIVE_UP retries in a row that end with the batch's own error the rest are told that error. */
-            /* Only for errors of the DEVICE: an error a caller can bring about by itself (an invalid argument, a bad offset
-             * table) says nothing about the next request - four faulty callers in a row must not fail everybody behind
-             * them - so such a batch is retried request by request to the end. */
-            const int device_fault = rc != -(int)hipErrorInvalidValue && rc != -(int)hipErrorInvalidDevicePointer;
-            int same = 0;
-            for (struct creq *r = batch; r; r = r->next) {
-                if (device_fault && same >= COMBINE_RETRY_GIVE_UP) { r->rc = rc; continue; }
-                struct hjob alone = *r->j;
-                alone.traced = 1;
-                r->rc = pipe_run_on(e, &alone, r->n);
-                same = r->rc == rc ? same + 1 : 0;
-            }
-        }
-        pthread_mutex_lock(&q->lk);
-        q->batches++; q->items += reqs;
-        K->last_reqs = (unsigned)reqs;
-        K->waiting_at_end = K->queued;
-        for (struct creq *r = batch; r;) {             /* a caller may return (and its request vanish) the moment `done` is set */
-            struct creq *nx = r->next;
-            __atomic_store_n(&r->done, 1, __ATOMIC_RELEASE);
-            r = nx;
-        }
-        K->active = 0;
-        __atomic_add_fetch(&K->gen, 1, __ATOMIC_RELEASE);
-        pthread_mutex_unlock(&q->lk);
-        gen_wake_all(&K->gen);
+        if (rc && reqs > 1) batch_retry(e, batch, rc);
+        batch_publish(q, K, batch, reqs);
         pthread_mutex_lock(&q->lk);
     }
     pthread_mutex_unlock(&q->lk);
@@ -874,23 +888,22 @@ static int combiner_submit(struct engine *e, const struct hjob *j, size_t n)
 }
 
 /* on the default device */
-static int pipe_run(const struct hjob *j, size_t n)
+static int pipe_run(const struct hjob j, size_t n)
 {
     struct call c;
-    int rc;
     if (n == 0) return 0;
-    rc = enter(&c, -1);
+    int rc = enter(&c, -1);
     if (rc) return rc;
-    if (j->kind && n <= COMBINE_MAX_N && !(j->has_msgs && (j->msg_off || n * j->msg_len > COMBINE_MAX_BYTES)))
-        rc = combiner_submit(c.e, j, n);
+    if (j.op->kind && n <= COMBINE_MAX_N && !(j.op->has_msgs && (j.msg_off || n * j.msg_len > COMBINE_MAX_BYTES)))
+        rc = combiner_submit(c.e, &j, n);
     else
-        rc = pipe_run_on(c.e, j, n);
+        rc = pipe_run_on(c.e, &j, n, 0);
     leave(&c);
     return rc;
 }
 
 /* ------------------------------------------------------------------------------------------
- * jobs
+ * operations
  * ---------------------------------------------------------------------------------------- */
 
 /* verify: chunks of 2^16, 2^17, 2^18 items, then the rest in one (measured, tools/pipe_verify_sweep.py, 2^20 items from
@@ -899,89 +912,66 @@ static int pipe_run(const struct hjob *j, size_t n)
 #define PIPE_CHUNK_VERIFY CHUNK_MAX
 #define PIPE_FIRST_CHUNK_VERIFY ((size_t)1 << 16)   /* the first chunk of a verify call (the other operations: PIPE_FIRST_CHUNK) */
 
-#define RUN_ARGS struct engine *e, const struct hjob *j, uint8_t *d_out, uint8_t *const d_in[PIPE_MAX_IN], \
-                 const uint8_t *d_msgs, const uint64_t *d_off, size_t msg_len, size_t m, hipStream_t st, hipEvent_t kdone
 /* record the lane's "kernels queued" event (verify does it itself, before its stream waits for the exact path) */
-#define RUN_DONE(rc_) do { int r_ = (rc_); if (!r_ && hipEventRecord(kdone, st) != hipSuccess) r_ = -(int)hipErrorUnknown; return r_; } while (0)
-static int run_verify(RUN_ARGS)
+static int run_done(int rc, const struct chunk *c) { return !rc && hipEventRecord(c->kdone, c->st) != hipSuccess ? -(int)hipErrorUnknown : rc; }
+static int run_verify(struct engine *e, const struct hjob *j, const struct chunk *c)
+{
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL };
+    return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
+}
+static int run_verify_rlc(struct engine *e, const struct hjob *j, const struct chunk *c)
+{
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL };
+    return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
+}
+static int run_verify_records(struct engine *e, const struct hjob *j, const struct chunk *c)
+{
+    const edk_verify_src src = { c->d_in[0] + j->rec_sig, c->d_in[0] + j->rec_pub, c->d_in[0] + j->rec_msg, NULL, j->msg_len,
+                                 j->stride, j->stride, j->stride, NULL };
+    return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
+}
+static int run_sign(struct engine *e, const struct hjob *j, const struct chunk *c)
+{
+    return run_done(sign_on(e, c->d_out, c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, c->m, c->st), c);
+}
+static int run_x25519(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     (void)j;
-    const edk_verify_src src = { d_in[0], d_in[1], d_msgs, d_off, msg_len, 64, 32, msg_len, NULL };
-    return verify_on(e, d_out, &src, m, st, kdone, g_pipe_chain == 2);
+    return run_done(x25519_on(e, c->d_out, c->d_in[0], c->d_in[1], c->m, c->st), c);
 }
-static int run_verify_rlc(RUN_ARGS)
-{
-    const edk_verify_src src = { d_in[0], d_in[1], d_msgs, d_off, msg_len, 64, 32, msg_len, NULL };
-    RUN_DONE(rlc_on(e, d_out, j->stats, &src, m, st));
-}
-static int run_verify_records(RUN_ARGS)
-{
-    (void)d_msgs; (void)d_off;
-    const edk_verify_src src = { d_in[0] + j->rec_sig, d_in[0] + j->rec_pub, d_in[0] + j->rec_msg, NULL, msg_len,
-                                 j->in_w[0], j->in_w[0], j->in_w[0], NULL };
-    return verify_on(e, d_out, &src, m, st, kdone, g_pipe_chain == 2);
-}
-static int run_sign(RUN_ARGS)
-{
-    (void)j;
-    RUN_DONE(sign_on(e, d_out, d_in[0], d_in[1], d_msgs, d_off, msg_len, m, st));
-}
-static int run_x25519(RUN_ARGS)
-{
-    (void)j; (void)d_msgs; (void)d_off; (void)msg_len;
-    RUN_DONE(x25519_on(e, d_out, d_in[0], d_in[1], m, st));
-}
-static int run_genpub(RUN_ARGS)
-{
-    (void)j; (void)d_msgs; (void)d_off; (void)msg_len;
-    RUN_DONE(genpub_on(e, d_out, d_in[0], m, st));
-}
-static int run_xbase(RUN_ARGS)
-{
-    (void)j; (void)d_msgs; (void)d_off; (void)msg_len;
-    RUN_DONE(xbase_on(e, d_out, d_in[0], m, st));
-}
-static int run_pk_to_x(RUN_ARGS)
-{
-    (void)j; (void)d_msgs; (void)d_off; (void)msg_len;
-    RUN_DONE(pk_to_x_on(e, d_out, d_in[0], m, st));
-}
-static int run_sk_to_x(RUN_ARGS)
-{
-    (void)j; (void)d_msgs; (void)d_off; (void)msg_len;
-    RUN_DONE(sk_to_x_on(e, d_out, d_in[0], m, st));
-}
+/* the operations of one 32-byte input and one 32-byte output */
+#define RUN_1IN(name_, on_) static int name_(struct engine *e, const struct hjob *j, const struct chunk *c) \
+    { (void)j; return run_done(on_(e, c->d_out, c->d_in[0], c->m, c->st), c); }
+RUN_1IN(run_genpub, genpub_on)
+RUN_1IN(run_xbase, xbase_on)
+RUN_1IN(run_pk_to_x, pk_to_x_on)
+RUN_1IN(run_sk_to_x, sk_to_x_on)
 
-static struct hjob job_verify(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs,
-                              const uint64_t *msg_off, size_t msg_len)
+/* The table of operations.  Verify - measured (tools/pipe_sweep.py, 2^20 items from malloc memory): the three kernels of a
+ * verify chunk leave ramps and tails that the neighbouring chunks' kernels fill when the lanes run side by side (95.7 M/s;
+ * in chunk order 79-86), and the small first chunk gets the chip working 0.2 ms after the call.  The batch verification
+ * makes one combination per 2^20 items; it and the records form are never merged by the combiner. */
+enum { OP_VERIFY, OP_VERIFY_RLC, OP_VERIFY_RECORDS, OP_SIGN, OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X };
+static const struct op g_ops[] = {
+    [OP_VERIFY] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify, .wipe = WIPE_NONE, .chain = 0,
+                    .kind = KIND_VERIFY, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
+    [OP_VERIFY_RLC] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_rlc, .wipe = WIPE_NONE, .chain = 0,
+                    .kind = KIND_NONE, .chunk = CHUNK_MAX, .first_chunk = CHUNK_MAX, .reports = 1 },
+    [OP_VERIFY_RECORDS] = { .n_in = 1, .in_w = { 0, 0, 0 }, .out_w = 1, .has_msgs = 0, .run = run_verify_records, .wipe = WIPE_NONE, .chain = 0,
+                    .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
+    [OP_SIGN] = { .n_in = 2, .in_w = { 32, 32, 0 }, .out_w = 64, .has_msgs = 1, .run = run_sign, .wipe = WIPE_IN0, .chain = 1, .kind = KIND_SIGN },
+    [OP_X25519] = { .n_in = 2, .in_w = { 32, 32, 0 }, .out_w = 32, .run = run_x25519, .wipe = WIPE_IN0 | WIPE_OUT, .chain = 1, .kind = KIND_X25519 },
+    [OP_GENPUB] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_genpub, .wipe = WIPE_IN0, .chain = 1, .kind = KIND_GENPUB },
+    [OP_XBASE] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_xbase, .wipe = WIPE_IN0, .chain = 1, .kind = KIND_XBASE },
+    [OP_PK_TO_X] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_pk_to_x, .wipe = WIPE_NONE, .chain = 1, .kind = KIND_PK_TO_X },
+    [OP_SK_TO_X] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_sk_to_x, .wipe = WIPE_IN0 | WIPE_OUT, .chain = 1, .kind = KIND_SK_TO_X },
+};
+
+/* a call of operation `id` (in1, msgs, msg_off: NULL where the operation has none) */
+static struct hjob job(int id, uint8_t *out, const uint8_t *in0, const uint8_t *in1, const uint8_t *msgs,
+                       const uint64_t *msg_off, size_t msg_len)
 {
-    /* Measured (tools/pipe_sweep.py, 2^20 items from malloc memory): the three kernels of a verify chunk leave ramps and
-     * tails that the neighbouring chunks' kernels fill when the lanes run side by side (95.7 M/s; in chunk order 79-86),
-     * and the small first chunk gets the chip working 0.2 ms after the call. */
-    const struct hjob j = { .n_in = 2, .in = { sigs, pubs, NULL }, .in_w = { 64, 32, 0 }, .has_msgs = 1, .msgs = msgs,
-                            .msg_off = msg_off, .msg_len = msg_len, .out = ok, .out_w = 1, .run = run_verify,
-                            .chunk = PIPE_CHUNK_VERIFY, .wipe = WIPE_NONE, .first_chunk = PIPE_FIRST_CHUNK_VERIFY,
-                            .chain = 0, .kind = 1 };
-    return j;
-}
-static struct hjob job_sign(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
-                            const uint64_t *msg_off, size_t msg_len)
-{
-    const struct hjob j = { .n_in = 2, .in = { secs, pubs, NULL }, .in_w = { 32, 32, 0 }, .has_msgs = 1, .msgs = msgs,
-                            .msg_off = msg_off, .msg_len = msg_len, .out = sigs, .out_w = 64, .run = run_sign,
-                            .wipe = WIPE_IN0, .chain = 1, .kind = 2 };
-    return j;
-}
-static struct hjob job_x25519(uint8_t *out, const uint8_t *scalars, const uint8_t *points)
-{
-    const struct hjob j = { .n_in = 2, .in = { scalars, points, NULL }, .in_w = { 32, 32, 0 }, .out = out, .out_w = 32,
-                            .run = run_x25519, .wipe = WIPE_IN0 | WIPE_OUT, .chain = 1, .kind = 3 };
-    return j;
-}
-static struct hjob job_1in(int (*run)(RUN_ARGS), uint8_t *out, const uint8_t *in, int wipe, int kind)
-{
-    const struct hjob j = { .n_in = 1, .in = { in, NULL, NULL }, .in_w = { 32, 0, 0 }, .out = out, .out_w = 32, .run = run,
-                            .wipe = wipe, .chain = 1, .kind = kind };
+    const struct hjob j = { .op = &g_ops[id], .in = { in0, in1, NULL }, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len, .out = out };
     return j;
 }
 
@@ -992,20 +982,16 @@ static struct hjob job_1in(int (*run)(RUN_ARGS), uint8_t *out, const uint8_t *in
 int ed25519_verify_batch(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs,
                          const uint64_t *msg_off, size_t msg_len, size_t n)
 {
-    struct hjob j = job_verify(ok, sigs, pubs, msgs, msg_off, msg_len);
-    return pipe_run(&j, n);
+    return pipe_run(job(OP_VERIFY, ok, sigs, pubs, msgs, msg_off, msg_len), n);
 }
 
 int ed25519_verify_batch_rlc(uint8_t *ok, uint32_t stats[4], const uint8_t *sigs, const uint8_t *pubs,
                              const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n)
 {
     uint32_t local[4] = { 0, 0, 0, 0 };
-    struct hjob j = job_verify(ok, sigs, pubs, msgs, msg_off, msg_len);
-    j.run = run_verify_rlc;
-    j.chunk = j.first_chunk = CHUNK_MAX;   /* one combination per 2^20 items */
+    struct hjob j = job(OP_VERIFY_RLC, ok, sigs, pubs, msgs, msg_off, msg_len);
     j.stats = local;
-    j.kind = 0;
-    int rc = pipe_run(&j, n);
+    int rc = pipe_run(j, n);
     if (stats) memcpy(stats, local, sizeof(local));
     return rc;
 }
@@ -1014,45 +1000,23 @@ int ed25519_verify_records(uint8_t *ok, const uint8_t *records, size_t stride, s
                            size_t msg_off, size_t msg_len, size_t n)
 {
     if (!records_ok(stride, sig_off, pub_off, msg_off, msg_len)) return -(int)hipErrorInvalidValue;
-    const struct hjob j = { .n_in = 1, .in = { records, NULL, NULL }, .in_w = { stride, 0, 0 }, .msg_len = msg_len, .out = ok,
-                            .out_w = 1, .run = run_verify_records, .rec_sig = sig_off, .rec_pub = pub_off, .rec_msg = msg_off,
-                            .chunk = PIPE_CHUNK_VERIFY, .wipe = WIPE_NONE, .first_chunk = PIPE_FIRST_CHUNK_VERIFY };
-    return pipe_run(&j, n);
+    struct hjob j = job(OP_VERIFY_RECORDS, ok, records, NULL, NULL, NULL, msg_len);
+    j.stride = stride; j.rec_sig = sig_off; j.rec_pub = pub_off; j.rec_msg = msg_off;
+    return pipe_run(j, n);
 }
 
 int ed25519_sign_batch(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
                        const uint64_t *msg_off, size_t msg_len, size_t n)
 {
-    struct hjob j = job_sign(sigs, secs, pubs, msgs, msg_off, msg_len);
-    return pipe_run(&j, n);
+    return pipe_run(job(OP_SIGN, sigs, secs, pubs, msgs, msg_off, msg_len), n);
 }
 
-int x25519_batch(uint8_t *out, const uint8_t *scalars, const uint8_t *points, size_t n)
-{
-    struct hjob j = job_x25519(out, scalars, points);
-    return pipe_run(&j, n);
-}
+int x25519_batch(uint8_t *out, const uint8_t *scalars, const uint8_t *points, size_t n) { return pipe_run(job(OP_X25519, out, scalars, points, NULL, NULL, 0), n); }
 
-int ed25519_genpub_batch(uint8_t *pubs, const uint8_t *secs, size_t n)
-{
-    struct hjob j = job_1in(run_genpub, pubs, secs, WIPE_IN0, 4);
-    return pipe_run(&j, n);
-}
-int x25519_base_batch(uint8_t *out, const uint8_t *scalars, size_t n)
-{
-    struct hjob j = job_1in(run_xbase, out, scalars, WIPE_IN0, 5);
-    return pipe_run(&j, n);
-}
-int pk_ed25519_to_x25519_batch(uint8_t *out, const uint8_t *in, size_t n)
-{
-    struct hjob j = job_1in(run_pk_to_x, out, in, WIPE_NONE, 6);
-    return pipe_run(&j, n);
-}
-int sk_ed25519_to_x25519_batch(uint8_t *out, const uint8_t *in, size_t n)
-{
-    struct hjob j = job_1in(run_sk_to_x, out, in, WIPE_IN0 | WIPE_OUT, 7);
-    return pipe_run(&j, n);
-}
+int ed25519_genpub_batch(uint8_t *pubs, const uint8_t *secs, size_t n) { return pipe_run(job(OP_GENPUB, pubs, secs, NULL, NULL, NULL, 0), n); }
+int x25519_base_batch(uint8_t *out, const uint8_t *scalars, size_t n) { return pipe_run(job(OP_XBASE, out, scalars, NULL, NULL, NULL, 0), n); }
+int pk_ed25519_to_x25519_batch(uint8_t *out, const uint8_t *in, size_t n) { return pipe_run(job(OP_PK_TO_X, out, in, NULL, NULL, NULL, 0), n); }
+int sk_ed25519_to_x25519_batch(uint8_t *out, const uint8_t *in, size_t n) { return pipe_run(job(OP_SK_TO_X, out, in, NULL, NULL, NULL, 0), n); }
 
 /* ------------------------------------------------------------------------------------------
  * several devices in one process, host-pointer forms: thread d runs the ordinary pipeline of device d
@@ -1067,18 +1031,19 @@ static void *shard_thread(void *arg)
     struct call c;
     s->rc = enter(&c, s->device);
     if (s->rc) return NULL;
-    s->rc = pipe_run_on(c.e, &s->j, s->n);
+    s->rc = pipe_run_on(c.e, &s->j, s->n, 0);
     leave(&c);
     return NULL;
 }
 
 /* split job j over the device set: item ranges for the fixed-width arrays, message bytes for ragged ones */
-static int multi_run(const struct hjob *j, size_t n)
+static int multi_run(const struct hjob whole, size_t n)
 {
+    const struct hjob *j = &whole;
     struct shard_job jobs[MAX_DEVICES];
     pthread_t th[MAX_DEVICES];
-    uint64_t *offs[MAX_DEVICES];
-    int started[MAX_DEVICES];
+    uint64_t *offs[MAX_DEVICES] = { NULL };
+    int started[MAX_DEVICES] = { 0 };
     int rc = 0, g;
     pthread_rwlock_rdlock(&g_table);
     g = g_multi.n;
@@ -1086,23 +1051,21 @@ static int multi_run(const struct hjob *j, size_t n)
     pthread_rwlock_unlock(&g_table);
     if (g == 0) return -(int)hipErrorNotInitialized;
     if (n == 0) return 0;
-    memset(offs, 0, sizeof(offs));
-    memset(started, 0, sizeof(started));
     for (int d = 0; d < g; d++) {
         size_t lo, hi;
         eddsa_amd_shard_bounds(n, d, g, &lo, &hi);
         jobs[d].j = *j;
         jobs[d].n = hi - lo;
         jobs[d].rc = 0;
-        for (int i = 0; i < j->n_in; i++) jobs[d].j.in[i] = j->in[i] + lo * j->in_w[i];
-        jobs[d].j.out = j->out + lo * j->out_w;
-        if (j->has_msgs && j->msg_off) {            /* ragged: the shard's own offset table, rebased to 0 */
+        for (int i = 0; i < j->op->n_in; i++) jobs[d].j.in[i] = j->in[i] + lo * in_w(j, i);
+        jobs[d].j.out = j->out + lo * j->op->out_w;
+        if (j->op->has_msgs && j->msg_off) {        /* ragged: the shard's own offset table, rebased to 0 */
             offs[d] = (uint64_t *)malloc((hi - lo + 1) * sizeof(uint64_t));
             if (!offs[d]) { rc = -(int)hipErrorOutOfMemory; break; }
-            for (size_t k = 0; k <= hi - lo; k++) offs[d][k] = j->msg_off[lo + k] - j->msg_off[lo];
+            offsets_rebase(offs[d], j->msg_off + lo, hi - lo);
             jobs[d].j.msg_off = offs[d];
             jobs[d].j.msgs = j->msgs + j->msg_off[lo];
-        } else if (j->has_msgs) {
+        } else if (j->op->has_msgs) {
             jobs[d].j.msgs = j->msgs + lo * j->msg_len;
         }
     }
@@ -1121,22 +1084,16 @@ static int multi_run(const struct hjob *j, size_t n)
 int ed25519_verify_batch_multi(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs,
                                const uint64_t *msg_off, size_t msg_len, size_t n)
 {
-    struct hjob j = job_verify(ok, sigs, pubs, msgs, msg_off, msg_len);
-    return multi_run(&j, n);
+    return multi_run(job(OP_VERIFY, ok, sigs, pubs, msgs, msg_off, msg_len), n);
 }
 
 int ed25519_sign_batch_multi(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
                              const uint64_t *msg_off, size_t msg_len, size_t n)
 {
-    struct hjob j = job_sign(sigs, secs, pubs, msgs, msg_off, msg_len);
-    return multi_run(&j, n);
+    return multi_run(job(OP_SIGN, sigs, secs, pubs, msgs, msg_off, msg_len), n);
 }
 
-int x25519_batch_multi(uint8_t *out, const uint8_t *scalars, const uint8_t *points, size_t n)
-{
-    struct hjob j = job_x25519(out, scalars, points);
-    return multi_run(&j, n);
-}
+int x25519_batch_multi(uint8_t *out, const uint8_t *scalars, const uint8_t *points, size_t n) { return multi_run(job(OP_X25519, out, scalars, points, NULL, NULL, 0), n); }
 
 /* ------------------------------------------------------------------------------------------
  * the eddsa.h surface: batches of one.  No error channel in these signatures, so fail loudly.
@@ -1150,42 +1107,21 @@ static void must(int rc, const char *what)
     abort();
 }
 
-void ed25519_genpub(uint8_t pub[32], const uint8_t sec[32])
-{
-    must(ed25519_genpub_batch(pub, sec, 1), "ed25519_genpub");
-}
-
+void ed25519_genpub(uint8_t pub[32], const uint8_t sec[32]) { must(ed25519_genpub_batch(pub, sec, 1), "ed25519_genpub"); }
 void ed25519_sign(uint8_t sig[64], const uint8_t sec[32], const uint8_t pub[32], const uint8_t *data, size_t len)
 {
     must(ed25519_sign_batch(sig, sec, pub, data, NULL, len, 1), "ed25519_sign");
 }
-
 bool ed25519_verify(const uint8_t sig[64], const uint8_t pub[32], const uint8_t *data, size_t len)
 {
     uint8_t ok = 0;
     must(ed25519_verify_batch(&ok, sig, pub, data, NULL, len, 1), "ed25519_verify");
     return ok != 0;
 }
-
-void x25519_base(uint8_t out[32], const uint8_t scalar[32])
-{
-    must(x25519_base_batch(out, scalar, 1), "x25519_base");
-}
-
-void x25519(uint8_t out[32], const uint8_t scalar[32], const uint8_t point[32])
-{
-    must(x25519_batch(out, scalar, point, 1), "x25519");
-}
-
-void pk_ed25519_to_x25519(uint8_t out[32], const uint8_t in[32])
-{
-    must(pk_ed25519_to_x25519_batch(out, in, 1), "pk_ed25519_to_x25519");
-}
-
-void sk_ed25519_to_x25519(uint8_t out[32], const uint8_t in[32])
-{
-    must(sk_ed25519_to_x25519_batch(out, in, 1), "sk_ed25519_to_x25519");
-}
+void x25519_base(uint8_t out[32], const uint8_t scalar[32]) { must(x25519_base_batch(out, scalar, 1), "x25519_base"); }
+void x25519(uint8_t out[32], const uint8_t scalar[32], const uint8_t point[32]) { must(x25519_batch(out, scalar, point, 1), "x25519"); }
+void pk_ed25519_to_x25519(uint8_t out[32], const uint8_t in[32]) { must(pk_ed25519_to_x25519_batch(out, in, 1), "pk_ed25519_to_x25519"); }
+void sk_ed25519_to_x25519(uint8_t out[32], const uint8_t in[32]) { must(sk_ed25519_to_x25519_batch(out, in, 1), "sk_ed25519_to_x25519"); }
 
 /* reference lib/ed25519-sha512.c:270-324 and lib/x25519.c:232-243: the obsolete names */
 void eddsa_genpub(uint8_t pub[32], const uint8_t sec[32]) { ed25519_genpub(pub, sec); }
@@ -1200,3 +1136,67 @@ bool eddsa_verify(const uint8_t sig[64], const uint8_t pub[32], const uint8_t *d
 void DH(uint8_t out[32], const uint8_t sec[32], const uint8_t point[32]) { x25519(out, sec, point); }
 void eddsa_pk_eddsa_to_dh(uint8_t out[32], const uint8_t in[32]) { pk_ed25519_to_x25519(out, in); }
 void eddsa_sk_eddsa_to_dh(uint8_t out[32], const uint8_t in[32]) { sk_ed25519_to_x25519(out, in); }
+
+/* ------------------------------------------------------------------------------------------
+ * measurement aids and test hooks (include/eddsa_amd_debug.h): only libeddsa_amd_debug.so has them
+ * ---------------------------------------------------------------------------------------- */
+#ifdef EDDSA_AMD_DEBUG_BUILD
+void eddsa_amd_set_pipeline_chain(int mode)
+{
+    pthread_rwlock_wrlock(&g_table);
+    g_pipe_chain = mode;
+    pthread_rwlock_unlock(&g_table);
+}
+
+/* tuning: items of the first chunk of a host-pointer call and of its later stages (0 = default).  A measurement aid. */
+void eddsa_amd_set_pipeline(size_t first_chunk, size_t stage_chunk)
+{
+    pthread_rwlock_wrlock(&g_table);
+    g_pipe_first = first_chunk;
+    g_pipe_stage = stage_chunk;
+    pthread_rwlock_unlock(&g_table);
+}
+
+/* on != 0: record host-side time stamps in every host-pointer call from now on; returns the number of stamps of the last
+ * call and copies up to `max` of them: tag (0 call start, 1 lane drained, 2 inputs staged and queued, 3 kernels queued,
+ * 4 download queued, 5 all lanes drained, 6 call end; of a combined launch also 7 leader elected, 8 callers gathered,
+ * 9 requests packed, 10 results handed back), chunk index, milliseconds since the call started.  on = 2: recording stops
+ * by itself after the 20th combined launch of 32 calls or more, so that a typical launch under load can be read */
+int eddsa_amd_debug_pipe_trace(int on, int *tags, unsigned *chunks, double *ms, int max)
+{
+    pthread_rwlock_wrlock(&g_table);       /* no call in flight: nobody is stamping */
+    int n = __atomic_load_n(&g_trace.n, __ATOMIC_RELAXED);
+    n = n > TRACE_MAX ? TRACE_MAX : n;
+    n = n < max ? n : max;
+    for (int i = 0; i < n; i++) {
+        tags[i] = __atomic_load_n(&g_trace.tag[i], __ATOMIC_RELAXED); chunks[i] = __atomic_load_n(&g_trace.chunk[i], __ATOMIC_RELAXED);
+        ms[i] = 1e-6 * (double)(__atomic_load_n(&g_trace.t_ns[i], __ATOMIC_RELAXED) - __atomic_load_n(&g_trace.t_ns[0], __ATOMIC_RELAXED));
+    }
+    __atomic_store_n(&g_trace.on, on, __ATOMIC_RELAXED);
+    __atomic_store_n(&g_trace.seen, 0, __ATOMIC_RELAXED);
+    pthread_rwlock_unlock(&g_table);
+    return n;
+}
+
+/* test hook (inert unless armed): the next host-pointer call fails (hipErrorUnknown) after its inputs were staged and its
+ * kernels launched, so that the error path's clean-up (the staging copies of secrets are wiped there too) can be exercised */
+int eddsa_amd_debug_fail_next_host_call(void)
+{
+    if (!__atomic_load_n(&g_hooks_armed, __ATOMIC_ACQUIRE)) return EDDSA_AMD_HOOKS_OFF;
+    __atomic_store_n(&g_fail_next_host_call, 1, __ATOMIC_RELEASE);
+    return 0;
+}
+
+/* diagnostic: combined launches and the items they carried on the default device since its engine was built */
+int eddsa_amd_combiner_stats(uint64_t out[2])
+{
+    struct call c;
+    int rc = enter(&c, -1);
+    if (rc) return rc;
+    pthread_mutex_lock(&c.e->comb_q.lk);
+    out[0] = c.e->comb_q.batches; out[1] = c.e->comb_q.items;
+    pthread_mutex_unlock(&c.e->comb_q.lk);
+    leave(&c);
+    return 0;
+}
+#endif /* the debug build */

@@ -4,7 +4,7 @@
  *
  *   1. multi-chunk pipelines on small batches (eddsa_amd_set_pipeline(48, 96): three lanes, drains, secrets wiped) for
  *      verify with RAGGED messages (the chunks' offset tables are rebased), the opt-in batch verification, sign and
- *      x25519 - same bytes as one chunk;
+ *      x25519 - same bytes as one chunk; and page-locked arrays of 1 MiB, which the pipeline uses in place (no staging copy);
  *   2. the fault hooks: inert until armed; a failed host-pointer call and a failed HIP call inside a verify pass come
  *      back as negative values, the next call works, no secret is left in a staging buffer;
  *   3. threads that issue chunked batches and single-item calls (merged by the combiner) while another thread switches the
@@ -103,6 +103,41 @@ static void *shutter(void *arg)
     return NULL;
 }
 
+/* Page-locked arrays large enough for the pipeline to ask (2^15 items of 32 bytes: exactly 1 MiB) are used in place: no
+ * staging copy on the way in, the download straight into the caller's memory.  sk_ed25519_to_x25519_batch has secret
+ * input and output: as one chunk and as four chunks over three lanes, same bytes as from malloc memory, nothing secret left
+ * in a staging buffer.  Called on a fresh engine (the residue counters look at whole buffers). */
+static int pinned_in_place(void)
+{
+    enum { NP = 1 << 15 };
+    const size_t bytes = (size_t)32 * NP;
+    uint8_t *in = malloc(bytes), *want = malloc(bytes), *got = malloc(bytes);
+    uint8_t *pin = eddsa_amd_host_alloc(bytes), *pout = eddsa_amd_host_alloc(bytes);
+    uint64_t res[4];
+    CHECK(in && want && got && pin && pout, "allocation of the 1 MiB arrays");
+    uint64_t x = 0x9e3779b97f4a7c15ull;
+    for (size_t i = 0; i < bytes; i++) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; in[i] = (uint8_t)(x >> 32); }
+    memcpy(pin, in, bytes);
+    for (int chunked = 0; chunked < 2; chunked++) {
+        if (chunked) eddsa_amd_set_pipeline(8192, 8192);            /* four chunks over three lanes */
+        else eddsa_amd_set_pipeline(0, 0);                          /* one chunk */
+        RC(sk_ed25519_to_x25519_batch(want, in, NP));               /* the same call on malloc memory */
+        memset(pout, 0xa5, bytes);
+        RC(sk_ed25519_to_x25519_batch(pout, pin, NP));              /* both arrays page-locked */
+        CHECK(memcmp(pout, want, bytes) == 0, "page-locked arrays (%s): other bytes than from malloc memory", chunked ? "four chunks" : "one chunk");
+        RC(eddsa_amd_secret_residue(res));
+        CHECK(res[2] == 0 && res[3] == 0, "page-locked arrays left secrets behind: %llu %llu", (unsigned long long)res[2], (unsigned long long)res[3]);
+        memset(got, 0xa5, bytes);
+        RC(sk_ed25519_to_x25519_batch(got, pin, NP));               /* page-locked input, malloc output */
+        CHECK(memcmp(got, want, bytes) == 0, "page-locked input, malloc output (%s): other bytes", chunked ? "four chunks" : "one chunk");
+        RC(eddsa_amd_secret_residue(res));
+        CHECK(res[2] == 0 && res[3] == 0, "page-locked input left secrets behind: %llu %llu", (unsigned long long)res[2], (unsigned long long)res[3]);
+    }
+    eddsa_amd_host_free(pin); eddsa_amd_host_free(pout);
+    free(in); free(want); free(got);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 4) { fprintf(stderr, "usage: %s ed25519_table.bin ed25519_msgs.bin x25519_table.bin [threads [rounds]]\n", argv[0]); return 2; }
@@ -139,6 +174,11 @@ int main(int argc, char **argv)
     uint64_t off5[NE + 1];
     memcpy(shifted + 5, g_mm, sizeof(g_mm));
     for (int i = 0; i <= NE; i++) off5[i] = g_off[i] + 5;
+    /* ---- 1a. page-locked arrays, in place (one thread; its own fresh engine, and it sets the pipeline back) ---- */
+    eddsa_amd_shutdown();
+    RC(eddsa_amd_debug_init(0, EDDSA_AMD_TEST_HOOKS));
+    if (pinned_in_place()) return 1;
+    eddsa_amd_set_pipeline(48, 96);
     /* (the secret-bearing operations first, on a fresh engine: the residue counters look at whole staging buffers, and a
      * verify call leaves its - public - signatures in them) */
     eddsa_amd_shutdown();
