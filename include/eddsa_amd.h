@@ -9,6 +9,8 @@
  *   ed25519_verify_records the same over fixed-size (sig, pub, msg) records
  *   ed25519_verify_batch_rlc  the same verdicts by batch verification (opt-in; the reference's TODO,
  *                          lib/ed25519-sha512.c:13-14)
+ *   ed25519_verify_digests the same loop for callers that already hold SHA-512(R || A || M): 64 digest bytes per item instead
+ *                          of the message (also _rlc, _multi and the device-pointer forms; see the declarations)
  *   ed25519_sign_batch     loop of ed25519_sign          reference lib/eddsa.h:47
  *   ed25519_genpub_batch   loop of ed25519_genpub        reference lib/eddsa.h:44
  *   x25519_batch           loop of x25519                reference lib/eddsa.h:67
@@ -172,6 +174,29 @@ EDDSA_AMD_DECL int ed25519_verify_records(uint8_t *ok, const uint8_t *records, s
 EDDSA_AMD_DECL int ed25519_verify_batch_rlc(uint8_t *ok, uint32_t stats[4], const uint8_t *sigs,
                                             const uint8_t *pubs, const uint8_t *msgs,
                                             const uint64_t *msg_off, size_t msg_len, size_t n);
+/* Verification from CALLER-SUPPLIED DIGESTS.  The reference's ed25519_verify uses the message for one thing only,
+ * t = SHA-512(R || A || M) mod l (lib/ed25519-sha512.c:165-171); a caller who has hashed already - on the thread that received
+ * the message, incrementally while a large block streamed by - hands over the digest and no message byte is uploaded or hashed
+ * on the device (a lane hashes 10-13 MB/s: one 1 MiB message stretches a pass of 2^16 short ones from 0.8 ms to 65 ms).
+ * digests: packed, 64 bytes per item, in the order SHA-512 emits them (what hashlib.sha512(R + A + M).digest() returns), no
+ * alignment required.  Item i is accepted exactly when the reference's ed25519_verify accepts (sigs[i], pubs[i], M) for an M
+ * with SHA-512(R_i || A_i || M) = digests[i].  The digest's only use is t = (the 64 bytes as a little-endian integer) mod l,
+ * the sc_import(t, h, 64) of lib/ed25519-sha512.c:171; any 64 bytes are legal input.  Everything else is ed25519_verify_batch's,
+ * byte for byte: S is not range-checked, off-curve keys follow eddsa_amd_set_offcurve_mode, EDDSA_AMD_STALLED is reported as
+ * there; return values, ownership, device selection, threading and page-locked memory follow the rules at the top.
+ * THE CALLER VOUCHES that digests[i] was computed over the R bytes (sigs[i][0..32)) and the A bytes (pubs[i]) of THIS call,
+ * followed by the message.  A digest computed over other bytes verifies a different statement, and the library cannot tell:
+ * it never sees the message.
+ * The _rlc forms are ed25519_verify_batch_rlc's combination with the same rules (groups of 8192, per-item fallback,
+ * eddsa_amd_set_rlc_min_items, stats, one synchronisation of `stream` in the device-pointer form); the item's leaf of the batch
+ * hash tree is taken from the digest bytes.  _multi shards over the device set like ed25519_verify_batch_multi.
+ * These calls are never merged by the small-call combiner (like the records form): each call is a pass of its own. */
+EDDSA_AMD_DECL int ed25519_verify_digests(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs,
+                                          const uint8_t *digests, size_t n);
+EDDSA_AMD_DECL int ed25519_verify_digests_rlc(uint8_t *ok, uint32_t stats[4], const uint8_t *sigs,
+                                              const uint8_t *pubs, const uint8_t *digests, size_t n);
+EDDSA_AMD_DECL int ed25519_verify_digests_multi(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs,
+                                                const uint8_t *digests, size_t n);
 EDDSA_AMD_DECL int ed25519_sign_batch(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs,
                                       const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len,
                                       size_t n);
@@ -192,6 +217,12 @@ EDDSA_AMD_DECL int ed25519_verify_batch_rlc_dev(uint8_t *ok, uint32_t *stats /* 
                                                 const uint8_t *sigs, const uint8_t *pubs,
                                                 const uint8_t *msgs, const uint64_t *msg_off,
                                                 size_t msg_len, size_t n, void *stream);
+/* caller-supplied digests (see ed25519_verify_digests): digests in HBM, 64 bytes per item, any alignment */
+EDDSA_AMD_DECL int ed25519_verify_digests_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs,
+                                              const uint8_t *digests, size_t n, void *stream);
+EDDSA_AMD_DECL int ed25519_verify_digests_rlc_dev(uint8_t *ok, uint32_t *stats /* device, 4 words, or NULL */,
+                                                  const uint8_t *sigs, const uint8_t *pubs,
+                                                  const uint8_t *digests, size_t n, void *stream);
 EDDSA_AMD_DECL int ed25519_sign_batch_dev(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs,
                                           const uint8_t *msgs, const uint64_t *msg_off,
                                           size_t msg_len, size_t n, void *stream);

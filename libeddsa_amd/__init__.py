@@ -35,6 +35,9 @@ from .api import (  # noqa: F401
     ed25519_verify_batch_multi,
     ed25519_verify_batch_rlc,
     ed25519_verify_batch_multi_dev,
+    ed25519_verify_digests,
+    ed25519_verify_digests_multi,
+    ed25519_verify_digests_rlc,
     ed25519_sign_batch_multi,
     x25519_batch_multi,
     init_devices,

@@ -443,6 +443,32 @@ def _run_msgs(fn_host, fn_dev, what, first, first_w, first_name, pubs, msgs, msg
     return (out, tuple(int(x) for x in counts)) if stats else out
 
 
+def _run_digests(fn_host, fn_dev, what, sigs, pubs, digests, stats=None):
+    """common driver for the calls that take caller-supplied digests instead of messages: sigs (64 bytes per item), pubs (32)
+    and digests (64) -> (n,) uint8.  fn_dev None: host pointers only.  stats: as in _run_msgs."""
+    inputs = [(sigs, 64, "sigs"), (pubs, 32, "pubs"), (digests, 64, "digests")]
+    on_device = bool(fn_dev) and _is_torch(sigs)
+    arrs = [_torch_check(a, w, nm) if on_device else _as_np(a, w, nm) for a, w, nm in inputs]
+    counts_of = [(a.numel() if on_device else a.size) // w for a, (_, w, _) in zip(arrs, inputs)]
+    n = counts_of[0]
+    if counts_of[1] != n or counts_of[2] != n:
+        raise ValueError(f"{what}: sigs, pubs and digests disagree on the batch size ({counts_of[0]}, {counts_of[1]}, {counts_of[2]} items)")
+    lib = library()
+    if on_device:
+        import torch
+        out = torch.empty((n,), dtype=torch.uint8, device=arrs[0].device)
+        counts = torch.zeros((4,), dtype=torch.int32, device=arrs[0].device) if stats else None
+        args = [out] + ([counts] if stats is not None else []) + arrs
+        args = [_c_ptr(t.data_ptr()) if t is not None else None for t in args] + [_c_size(n), _stream()]
+        _check(getattr(lib, fn_dev)(*args), what)
+        return (out, tuple(int(x) for x in counts.cpu())) if stats else out
+    out = np.zeros((n,), dtype=np.uint8)
+    counts = (ctypes.c_uint32 * 4)()
+    args = [_np_ptr(out)] + ([counts] if stats is not None else []) + [_np_ptr(a) for a in arrs]
+    _check(getattr(lib, fn_host)(*args, _c_size(n)), what)
+    return (out, tuple(int(x) for x in counts)) if stats else out
+
+
 # ---------------------------------------------------------------------------------------------
 # batched entry points (include/eddsa_amd.h)
 # ---------------------------------------------------------------------------------------------
@@ -495,6 +521,19 @@ def ed25519_verify_batch_rlc(sigs, pubs, msgs, msg_off=None, msg_len=None, retur
                      sigs, 64, "sigs", pubs, msgs, msg_off, msg_len, (), stats=bool(return_stats))
 
 
+def ed25519_verify_digests(sigs, pubs, digests):
+    """loop of ed25519_verify for callers that already hold digests[i] = SHA-512(R_i || A_i || M_i) (64 bytes per item, as
+    hashlib.sha512(...).digest() returns them): no message is uploaded or hashed -> (n,) uint8, 1 = accept.  The caller vouches
+    that each digest was computed over the R and A bytes of this call's sigs[i] and pubs[i] (include/eddsa_amd.h)."""
+    return _run_digests("ed25519_verify_digests", "ed25519_verify_digests_dev", "ed25519_verify_digests", sigs, pubs, digests)
+
+
+def ed25519_verify_digests_rlc(sigs, pubs, digests, return_stats=False):
+    """ed25519_verify_batch_rlc from caller-supplied digests (see ed25519_verify_digests): same verdicts, same statistics"""
+    return _run_digests("ed25519_verify_digests_rlc", "ed25519_verify_digests_rlc_dev", "ed25519_verify_digests_rlc",
+                        sigs, pubs, digests, stats=bool(return_stats))
+
+
 def ed25519_verify_records(records, sig_off, pub_off, msg_off, msg_len):
     """loop of ed25519_verify over fixed-size records: `records` is an (n, stride) uint8 array (numpy:
     host path, one upload; CUDA tensor: device path) holding each item's 64-byte signature at
@@ -534,6 +573,11 @@ def ed25519_verify_batch_multi(sigs, pubs, msgs, msg_off=None, msg_len=None):
     """ed25519_verify_batch over the device set: contiguous shards, one host thread per device"""
     return _run_msgs("ed25519_verify_batch_multi", None, "ed25519_verify_batch_multi",
                      sigs, 64, "sigs", pubs, msgs, msg_off, msg_len, ())
+
+
+def ed25519_verify_digests_multi(sigs, pubs, digests):
+    """ed25519_verify_digests over the device set (host arrays): contiguous shards, one host thread per device"""
+    return _run_digests("ed25519_verify_digests_multi", None, "ed25519_verify_digests_multi", sigs, pubs, digests)
 
 
 def ed25519_sign_batch_multi(secs, pubs, msgs, msg_off=None, msg_len=None):

@@ -643,7 +643,7 @@ static int leave_with(struct call *c, int rc) { leave(c); return rc; }
 int ed25519_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs,
                              const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL };
+    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0 };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -662,7 +662,7 @@ int ed25519_verify_records_dev(uint8_t *ok, const uint8_t *records, size_t strid
 {
     if (!records_ok(stride, sig_off, pub_off, msg_off, msg_len)) return -(int)hipErrorInvalidValue;
     const edk_verify_src src = { records + sig_off, records + pub_off, records + msg_off, NULL, msg_len,
-                                 stride, stride, stride, NULL };
+                                 stride, stride, stride, NULL, 0 };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -672,7 +672,28 @@ int ed25519_verify_records_dev(uint8_t *ok, const uint8_t *records, size_t strid
 int ed25519_verify_batch_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *sigs, const uint8_t *pubs,
                                  const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL };
+    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0 };
+    struct call c;
+    int rc = 0;
+    if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
+    return leave_with(&c, rlc_on(c.e, ok, stats, &src, n, (hipStream_t)stream));
+}
+
+/* caller-supplied digests (include/eddsa_amd.h): the two calls above with the 64 bytes of SHA-512(R || A || M) per item in the
+ * message slot and the flag that selects the kernels that do not hash */
+int ed25519_verify_digests_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n, void *stream)
+{
+    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1 };
+    struct call c;
+    int rc = 0;
+    if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
+    return leave_with(&c, verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
+}
+
+int ed25519_verify_digests_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests,
+                                   size_t n, void *stream)
+{
+    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1 };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -830,7 +851,7 @@ int ed25519_verify_batch_multi_dev(uint8_t *const ok_full[], const uint8_t *cons
         size_t lo, hi;
         eddsa_amd_shard_bounds(n_total, d, g, &lo, &hi);
         if (hi - lo != n_total / (size_t)g) even = 0;
-        const edk_verify_src src = { sigs[d], pubs[d], msgs[d], NULL, msg_len, 64, 32, msg_len, NULL };
+        const edk_verify_src src = { sigs[d], pubs[d], msgs[d], NULL, msg_len, 64, 32, msg_len, NULL, 0 };
         TRY(hipSetDevice(g_multi.dev[d]));
         rc = verify_on(g_eng[g_multi.dev[d]], ok_full[d] + lo, &src, hi - lo, (hipStream_t)streams[d], NULL, 0);
     }

@@ -82,7 +82,24 @@ typedef struct {
   size_t msg_len, sig_stride, pub_stride, msg_stride;
   const uint64_t* msg_end;   /* ragged messages: the LAST entry of the call's offset table = the size of the message buffer; every
                                 item's span is clamped into it (lanes.h: msg_span).  verify_on / rlc_on fill it in. */
+  int digest;                /* != 0 (ed25519_verify_digests*): the message slot holds the caller's SHA-512(R || A || M), 64 bytes per
+                                item (msg_len 64, no offset table); the hashing kernels' digest forms take t from it unhashed */
 } edk_verify_src;
+
+/* What the kernels take BY VALUE: the nine fields of edk_verify_src that lanes read, 72 bytes as before the flag existed.  The flag stays
+ * on the host side (it selects the kernel): a by-value argument that grows moves every argument behind it, and with the layout of
+ * k_verify_prepare's arguments went its scalar register allocation (104 SGPRs, 14 of them spilled to 36 bytes of scratch per lane,
+ * where it has 106, 6 and none: profiles/digest_verify.txt). */
+typedef struct {
+  const uint8_t *sigs, *pubs, *msgs;
+  const uint64_t* msg_off;
+  size_t msg_len, sig_stride, pub_stride, msg_stride;
+  const uint64_t* msg_end;
+} edk_verify_items;
+static inline edk_verify_items edk_items_of(const edk_verify_src* s) {
+  const edk_verify_items it = { s->sigs, s->pubs, s->msgs, s->msg_off, s->msg_len, s->sig_stride, s->pub_stride, s->msg_stride, s->msg_end };
+  return it;
+}
 
 /* bulk_done (or NULL): recorded on `stream` once every kernel that fills the chip has been queued, before the stream
  * waits for the exact path's side stream (bulk_early != 0: already before the main kernel, so that a following pass on

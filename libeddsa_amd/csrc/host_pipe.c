@@ -916,18 +916,33 @@ static int pipe_run(const struct hjob j, size_t n)
 static int run_done(int rc, const struct chunk *c) { return !rc && hipEventRecord(c->kdone, c->st) != hipSuccess ? -(int)hipErrorUnknown : rc; }
 static int run_verify(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL };
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0 };
     return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
 }
 static int run_verify_rlc(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL };
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0 };
+    return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
+}
+/* caller-supplied digests: the 64 bytes of SHA-512(R || A || M) per item travel in the message slot (EDDSA_DIGEST_BYTES wide, staged
+ * like any fixed-length message); the flag selects the kernels that do not hash (eddsa_kernels.h: edk_verify_src) */
+#define EDDSA_DIGEST_BYTES 64
+static int run_verify_digests(struct engine *e, const struct hjob *j, const struct chunk *c)
+{
+    (void)j;
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1 };
+    return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
+}
+static int run_verify_digests_rlc(struct engine *e, const struct hjob *j, const struct chunk *c)
+{
+    (void)j;
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1 };
     return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
 }
 static int run_verify_records(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     const edk_verify_src src = { c->d_in[0] + j->rec_sig, c->d_in[0] + j->rec_pub, c->d_in[0] + j->rec_msg, NULL, j->msg_len,
-                                 j->stride, j->stride, j->stride, NULL };
+                                 j->stride, j->stride, j->stride, NULL, 0 };
     return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
 }
 static int run_sign(struct engine *e, const struct hjob *j, const struct chunk *c)
@@ -950,8 +965,9 @@ RUN_1IN(run_sk_to_x, sk_to_x_on)
 /* The table of operations.  Verify - measured (tools/pipe_sweep.py, 2^20 items from malloc memory): the three kernels of a
  * verify chunk leave ramps and tails that the neighbouring chunks' kernels fill when the lanes run side by side (95.7 M/s;
  * in chunk order 79-86), and the small first chunk gets the chip working 0.2 ms after the call.  The batch verification
- * makes one combination per 2^20 items; it and the records form are never merged by the combiner. */
-enum { OP_VERIFY, OP_VERIFY_RLC, OP_VERIFY_RECORDS, OP_SIGN, OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X };
+ * makes one combination per 2^20 items; it, the records form and the digest forms (their
+ * message counterparts with the digests in the message slot, 64 bytes per item) are never merged by the combiner. */
+enum { OP_VERIFY, OP_VERIFY_RLC, OP_VERIFY_RECORDS, OP_VERIFY_DIGESTS, OP_VERIFY_DIGESTS_RLC, OP_SIGN, OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X };
 static const struct op g_ops[] = {
     [OP_VERIFY] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify, .wipe = WIPE_NONE, .chain = 0,
                     .kind = KIND_VERIFY, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
@@ -959,6 +975,10 @@ static const struct op g_ops[] = {
                     .kind = KIND_NONE, .chunk = CHUNK_MAX, .first_chunk = CHUNK_MAX, .reports = 1 },
     [OP_VERIFY_RECORDS] = { .n_in = 1, .in_w = { 0, 0, 0 }, .out_w = 1, .has_msgs = 0, .run = run_verify_records, .wipe = WIPE_NONE, .chain = 0,
                     .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
+    [OP_VERIFY_DIGESTS] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_digests, .wipe = WIPE_NONE, .chain = 0,
+                    .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
+    [OP_VERIFY_DIGESTS_RLC] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_digests_rlc, .wipe = WIPE_NONE, .chain = 0,
+                    .kind = KIND_NONE, .chunk = CHUNK_MAX, .first_chunk = CHUNK_MAX, .reports = 1 },
     [OP_SIGN] = { .n_in = 2, .in_w = { 32, 32, 0 }, .out_w = 64, .has_msgs = 1, .run = run_sign, .wipe = WIPE_IN0, .chain = 1, .kind = KIND_SIGN },
     [OP_X25519] = { .n_in = 2, .in_w = { 32, 32, 0 }, .out_w = 32, .run = run_x25519, .wipe = WIPE_IN0 | WIPE_OUT, .chain = 1, .kind = KIND_X25519 },
     [OP_GENPUB] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_genpub, .wipe = WIPE_IN0, .chain = 1, .kind = KIND_GENPUB },
@@ -990,6 +1010,21 @@ int ed25519_verify_batch_rlc(uint8_t *ok, uint32_t stats[4], const uint8_t *sigs
 {
     uint32_t local[4] = { 0, 0, 0, 0 };
     struct hjob j = job(OP_VERIFY_RLC, ok, sigs, pubs, msgs, msg_off, msg_len);
+    j.stats = local;
+    int rc = pipe_run(j, n);
+    if (stats) memcpy(stats, local, sizeof(local));
+    return rc;
+}
+
+int ed25519_verify_digests(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n)
+{
+    return pipe_run(job(OP_VERIFY_DIGESTS, ok, sigs, pubs, digests, NULL, EDDSA_DIGEST_BYTES), n);
+}
+
+int ed25519_verify_digests_rlc(uint8_t *ok, uint32_t stats[4], const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n)
+{
+    uint32_t local[4] = { 0, 0, 0, 0 };
+    struct hjob j = job(OP_VERIFY_DIGESTS_RLC, ok, sigs, pubs, digests, NULL, EDDSA_DIGEST_BYTES);
     j.stats = local;
     int rc = pipe_run(j, n);
     if (stats) memcpy(stats, local, sizeof(local));
@@ -1085,6 +1120,11 @@ int ed25519_verify_batch_multi(uint8_t *ok, const uint8_t *sigs, const uint8_t *
                                const uint64_t *msg_off, size_t msg_len, size_t n)
 {
     return multi_run(job(OP_VERIFY, ok, sigs, pubs, msgs, msg_off, msg_len), n);
+}
+
+int ed25519_verify_digests_multi(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n)
+{
+    return multi_run(job(OP_VERIFY_DIGESTS, ok, sigs, pubs, digests, NULL, EDDSA_DIGEST_BYTES), n);
 }
 
 int ed25519_sign_batch_multi(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,

@@ -29,7 +29,7 @@ constexpr int BLOCK = 256;
 
 // one verify item: R, S, A as words and the message span (packed arrays or fixed-size records)
 ED_DEV void verify_item(uint32_t rw[8], uint32_t sw[8], uint32_t aw[8], const uint8_t*& m, size_t& mlen,
-                        const edk_verify_src& s, size_t item) {
+                        const edk_verify_items& s, size_t item) {
   load32(rw, s.sigs, item, s.sig_stride);
   load32(sw, s.sigs + 32, item, s.sig_stride);
   load32(aw, s.pubs, item, s.pub_stride);
@@ -183,20 +183,32 @@ __global__ void __launch_bounds__(BLOCK) k_len_place(uint32_t* perm, uint32_t* b
 //   offlist[..], offcount              items whose A is off the curve, for k_verify_exact_quad
 // ---------------------------------------------------------------------------------------------
 
+// DIGEST: the caller supplied SHA-512(R || A || M) (ed25519_verify_digests*): the item's 64 bytes lie in the message slot of
+// src and nothing is hashed.  Which instantiation runs is the launcher's choice (src.digest), never a lane's.
+template <bool DIGEST>
 __global__ void __launch_bounds__(BLOCK, 2)
-k_verify_prepare(edk_verify_src src, size_t n, uint32_t* digits,
+k_verify_prepare(edk_verify_items src, size_t n, uint32_t* digits,
                  uint32_t* table, uint8_t* flags, uint32_t* onlist, uint32_t* offlist, uint32_t* offcount, int all_exact, const uint32_t* perm) {
   const size_t g = (size_t)blockIdx.x * BLOCK + threadIdx.x;
   // position g of the grid works on item perm[g] (ragged messages in order of length, above) or on item g
   const size_t item = perm ? perm[g < n ? g : n - 1] : (g < n ? g : n - 1);
   const size_t i = g < n ? item : g;             // its slot of the workspace: the item's own; idle lanes redo the last item into a slot past the pass
-  uint32_t rw[8], aw[8], sw[8], tw[8];
-  const uint8_t* m; size_t mlen;
-  load32(rw, src.sigs, item, src.sig_stride);
-  load32(aw, src.pubs, item, src.pub_stride);
-  msg_span(m, mlen, src.msgs, src.msg_off, src.msg_end, src.msg_len, src.msg_stride, item);
+  uint32_t aw[8], sw[8], tw[8];
+  if constexpr (DIGEST) {
+    uint32_t dw[16];
+    load32(aw, src.pubs, item, src.pub_stride);
+    load32(dw, src.msgs, item, src.msg_stride);
+    load32(dw + 8, src.msgs + 32, item, src.msg_stride);
+    verify_digest_lane(tw, dw);
+  } else {
+    uint32_t rw[8];
+    const uint8_t* m; size_t mlen;
+    load32(rw, src.sigs, item, src.sig_stride);
+    load32(aw, src.pubs, item, src.pub_stride);
+    msg_span(m, mlen, src.msgs, src.msg_off, src.msg_end, src.msg_len, src.msg_stride, item);
+    verify_hash_lane(tw, rw, aw, m, mlen);
+  }
   uint4* d = reinterpret_cast<uint4*>(digits + 16 * i);
-  verify_hash_lane(tw, rw, aw, m, mlen);
   d[0] = make_uint4(tw[0], tw[1], tw[2], tw[3]); d[1] = make_uint4(tw[4], tw[5], tw[6], tw[7]);
   load32(sw, src.sigs + 32, item, src.sig_stride);       // S is fetched only now: nothing to hold across the hash
   verify_s_lane(sw);
@@ -998,9 +1010,9 @@ k_sk_to_x(uint8_t* out, const uint8_t* in, size_t n) {
 // a single item's 0.13 ms became 0.09) - and k_verify_main_half_quad is verify_half_main_lane with a coordinate per
 // lane (quad_lanes.h).  Two kernels, 132 doublings and no inversion instead of three, 252 and one.
 // ---------------------------------------------------------------------------------------------
-template <int BITS>
+template <int BITS, bool DIGEST>
 __global__ void __launch_bounds__(BLOCK, 2)
-k_verify_prepare_pair(edk_verify_src src, size_t n, uint32_t* digits, uint32_t* hdigits, uint32_t* table, uint32_t* rtable,
+k_verify_prepare_pair(edk_verify_items src, size_t n, uint32_t* digits, uint32_t* hdigits, uint32_t* table, uint32_t* rtable,
                       uint8_t* flags, uint32_t* onlist, uint32_t* offlist, uint32_t* offcount, int all_exact, unsigned point_blocks,
                       const uint32_t* perm) {
   if (blockIdx.x >= point_blocks) {
@@ -1009,10 +1021,19 @@ k_verify_prepare_pair(edk_verify_src src, size_t n, uint32_t* digits, uint32_t* 
     const size_t g = (size_t)(blockIdx.x - point_blocks) * BLOCK + threadIdx.x;
     if (g >= n) return;
     const size_t i = perm ? perm[g] : g;         // (ragged messages in order of length)
-    uint32_t rw[8], aw[8], sw[8], tw[8], hd[HALF_DIGIT_WORDS];
-    const uint8_t* m; size_t mlen;
-    verify_item(rw, sw, aw, m, mlen, src, i);
-    verify_hash_lane(tw, rw, aw, m, mlen);
+    uint32_t sw[8], tw[8], hd[HALF_DIGIT_WORDS];
+    if constexpr (DIGEST) {                      // (the caller's SHA-512(R || A || M): the 64 bytes in the message slot)
+      uint32_t dw[16];
+      load32(dw, src.msgs, i, src.msg_stride);
+      load32(dw + 8, src.msgs + 32, i, src.msg_stride);
+      load32(sw, src.sigs + 32, i, src.sig_stride);
+      verify_digest_lane(tw, dw);
+    } else {
+      uint32_t rw[8], aw[8];
+      const uint8_t* m; size_t mlen;
+      verify_item(rw, sw, aw, m, mlen, src, i);
+      verify_hash_lane(tw, rw, aw, m, mlen);
+    }
     verify_s_lane(sw);
     verify_half_scalars_lane<BITS>(hd, tw, sw);
     uint4* d = reinterpret_cast<uint4*>(digits + 16 * i);
@@ -1117,6 +1138,25 @@ static unsigned finish_k(size_t n) {
   return FINISH_K;
 }
 
+// the first kernel of a verify pass: the three-lane preparation with pairs up to 2^pair_bits, or (pair_bits == 0) the one-lane one.
+// DIGEST: the forms that take t from the caller's digest (edk_verify_src.digest)
+template <bool DIGEST>
+static hipError_t launch_prepare(const edk_verify_items& src, size_t n, const edk_verify_ws* ws, int pair_bits, const uint32_t* perm, hipStream_t stream) {
+  const unsigned blocks = (unsigned)((n + BLOCK - 1) / BLOCK), pair_point_blocks = (unsigned)((2 * n + BLOCK - 1) / BLOCK);
+  if (pair_bits == HALF_BITS_SMALL)
+    EDK_LAUNCH((k_verify_prepare_pair<HALF_BITS_SMALL, DIGEST>), dim3(pair_point_blocks + blocks), dim3(BLOCK), 0, stream, src, n,
+               ws->digits, ws->hdigits, ws->table, ws->rtable, ws->flags, ws->onlist, ws->offlist, ws->offcount, ws->exact_offcurve == 2,
+               pair_point_blocks, perm);
+  else if (pair_bits == HALF_BITS)
+    EDK_LAUNCH((k_verify_prepare_pair<HALF_BITS, DIGEST>), dim3(pair_point_blocks + blocks), dim3(BLOCK), 0, stream, src, n,
+               ws->digits, ws->hdigits, ws->table, ws->rtable, ws->flags, ws->onlist, ws->offlist, ws->offcount, ws->exact_offcurve == 2,
+               pair_point_blocks, perm);
+  else
+    EDK_LAUNCH(k_verify_prepare<DIGEST>, dim3(blocks), dim3(BLOCK), 0, stream, src, n, ws->digits, ws->table, ws->flags, ws->onlist, ws->offlist,
+               ws->offcount, ws->exact_offcurve == 2, perm);
+  return hipSuccess;
+}
+
 extern "C" {
 
 hipError_t edk_init_tables(uint32_t* base16, uint32_t* comb, uint32_t* comb_img, hipStream_t stream) {
@@ -1203,25 +1243,18 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
   const bool pair_one = n < PAIR_ONE_MAX_N && (algo == 3 || (algo == 0 && n > PAIR_ONE_MIN_N));
   const bool half = !pair_one && (algo == 2 || (algo == 0 && !small_half));
   const bool half_quad = !pair_one && algo == 0 && small_half;
-  const unsigned pair_point_blocks = (unsigned)((2 * n + BLOCK - 1) / BLOCK);
   // The four-lane evaluation runs 64 windows in the wave of an item without a short pair, and the pass waits for that wave:
   // with pairs up to 2^134 (8.5 items in 10^5) a pass of 2048 items has such an item one time in six, one of 2^14 three
   // times in four.  Above QUAD_WIDE_MIN_N items the search goes up to 2^138 (2 in 10^7) for a 35th window in every item.
   const bool quad_wide = half_quad && n > QUAD_WIDE_MIN_N;
   // ragged messages: the hashing kernels take their items in order of length
   const uint32_t* perm = nullptr;
-  EDK_DO(edk_msg_order(&perm, ws, src.msg_off, src.msg_end, n, stream));
-  if (pair_one || quad_wide)
-    EDK_LAUNCH(k_verify_prepare_pair<HALF_BITS_SMALL>, dim3(pair_point_blocks + blocks), dim3(BLOCK), 0, stream, src, n,
-               ws->digits, ws->hdigits, ws->table, ws->rtable, ws->flags, ws->onlist, ws->offlist, ws->offcount, ws->exact_offcurve == 2,
-               pair_point_blocks, perm);
-  else if (half_quad)
-    EDK_LAUNCH(k_verify_prepare_pair<HALF_BITS>, dim3(pair_point_blocks + blocks), dim3(BLOCK), 0, stream, src, n,
-               ws->digits, ws->hdigits, ws->table, ws->rtable, ws->flags, ws->onlist, ws->offlist, ws->offcount, ws->exact_offcurve == 2,
-               pair_point_blocks, perm);
-  else
-    EDK_LAUNCH(k_verify_prepare, dim3(blocks), dim3(BLOCK), 0, stream, src, n, ws->digits, ws->table, ws->flags, ws->onlist, ws->offlist,
-               ws->offcount, ws->exact_offcurve == 2, perm);
+  if (!src.digest) EDK_DO(edk_msg_order(&perm, ws, src.msg_off, src.msg_end, n, stream));
+  // caller-supplied digests (ed25519_verify_digests*): the same three preparations without the hash; everything after them
+  // reads t from the workspace and does not know
+  const int pair_bits = pair_one || quad_wide ? HALF_BITS_SMALL : half_quad ? HALF_BITS : 0;
+  const hipError_t prepared = src.digest ? launch_prepare<true>(edk_items_of(&src), n, ws, pair_bits, perm, stream) : launch_prepare<false>(edk_items_of(&src), n, ws, pair_bits, perm, stream);
+  if (prepared != hipSuccess) return prepared;
   // Below HALF_WIDE_MIN_N items the pass searches pairs up to 2^138 and runs 35 windows (2 t in 10^7 without a pair instead
   // of 8.5 in 10^5; 3 % more instructions in the main kernel): an item without a short pair goes through the exact path's
   // chain, and beside a main kernel of one or two rounds of resident blocks that chain costs the pass 0.3-0.4 ms (the

@@ -263,16 +263,22 @@ ED_DEV void cached_load(ge_cached& c, const uint32_t* tab, uint32_t entry) {
 
 // The three steps of the prepare kernel, separate so that the kernel can load S only when it is needed
 // (held across the hash it cost a spill) and store each result as soon as it exists:
-// t = SHA-512(R || A || M) mod l as digit words (nibble - 8 is the signed digit)
+// t = (the 64 digest bytes as a little-endian integer) mod l as digit words (nibble - 8 is the signed digit): sc_import(t, h, 64)
+// of ed25519-sha512.c:171.  dw = the digest as sixteen little-endian words, in the order SHA-512 emits its bytes: what
+// sha512_prefix_msg leaves, or what the caller of ed25519_verify_digests* supplies (any 64 bytes are legal)
+ED_DEV void verify_digest_lane(uint32_t tw[8], const uint32_t dw[16]) {
+  sc t;
+  sc_from_words<16>(t, dw);
+  sc_to_words(tw, t);
+  words_add_pattern(tw, 0x88888888u);
+}
+// t = SHA-512(R || A || M) mod l as digit words
 ED_DEV void verify_hash_lane(uint32_t tw[8], const uint32_t rw[8], const uint32_t aw[8], const uint8_t* m, size_t mlen) {
   uint32_t pre[16], dig[16];
 #pragma unroll
   for (int k = 0; k < 8; k++) { pre[k] = rw[k]; pre[8 + k] = aw[k]; }
   sha512_prefix_msg<16>(dig, pre, m, mlen);
-  sc t;
-  sc_from_words<16>(t, dig);
-  sc_to_words(tw, t);
-  words_add_pattern(tw, 0x88888888u);
+  verify_digest_lane(tw, dig);
 }
 // S mod l (not range-checked: sc.c:191-214) as digit words (halfword - 32768 is the signed digit)
 ED_DEV void verify_s_lane(uint32_t sw[8]) {

@@ -106,7 +106,7 @@ ED_DEV void load_words8(uint32_t w[8], const uint8_t* p) {
 // R1: per item, t and S mod l (ed25519-sha512.c:162-172) and the item's leaf of the batch hash tree
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(RLC_BLOCK, 2)
-k_rlc_hash(edk_verify_src src, size_t n, uint32_t* ts, uint32_t* leaf, const uint32_t* perm) {
+k_rlc_hash(edk_verify_items src, size_t n, uint32_t* ts, uint32_t* leaf, const uint32_t* perm) {
   const size_t g = (size_t)blockIdx.x * RLC_BLOCK + threadIdx.x;
   if (g >= n) return;
   const size_t i = perm ? perm[g] : g;           // ragged messages: a wave hashes items of one length (edk_msg_order)
@@ -117,6 +117,23 @@ k_rlc_hash(edk_verify_src src, size_t n, uint32_t* ts, uint32_t* leaf, const uin
   const uint8_t* m; size_t mlen;
   msg_span(m, mlen, src.msgs, src.msg_off, src.msg_end, src.msg_len, src.msg_stride, i);
   rlc_hash_lane(tw, sw, lf, rw, aw, src.sigs + i * src.sig_stride + 32, m, mlen);
+  uint4* o = reinterpret_cast<uint4*>(ts + 16 * i);
+  o[0] = make_uint4(tw[0], tw[1], tw[2], tw[3]); o[1] = make_uint4(tw[4], tw[5], tw[6], tw[7]);
+  o[2] = make_uint4(sw[0], sw[1], sw[2], sw[3]); o[3] = make_uint4(sw[4], sw[5], sw[6], sw[7]);
+  uint4* l = reinterpret_cast<uint4*>(leaf + 8 * i);
+  l[0] = make_uint4(lf[0], lf[1], lf[2], lf[3]); l[1] = make_uint4(lf[4], lf[5], lf[6], lf[7]);
+}
+// the same for caller-supplied digests (ed25519_verify_digests_rlc*): item i's 64 bytes of SHA-512(R || A || M) lie in the message
+// slot of src; nothing but the leaf is hashed
+__global__ void __launch_bounds__(RLC_BLOCK, 2)
+k_rlc_hash_digest(edk_verify_items src, size_t n, uint32_t* ts, uint32_t* leaf) {
+  const size_t i = (size_t)blockIdx.x * RLC_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  uint32_t dw[16], sw[8], tw[8], lf[8];
+  load_words8(dw, src.msgs + i * src.msg_stride);
+  load_words8(dw + 8, src.msgs + i * src.msg_stride + 32);
+  load_words8(sw, src.sigs + i * src.sig_stride + 32);
+  rlc_digest_lane(tw, sw, lf, dw, src.sigs + i * src.sig_stride + 32);
   uint4* o = reinterpret_cast<uint4*>(ts + 16 * i);
   o[0] = make_uint4(tw[0], tw[1], tw[2], tw[3]); o[1] = make_uint4(tw[4], tw[5], tw[6], tw[7]);
   o[2] = make_uint4(sw[0], sw[1], sw[2], sw[3]); o[3] = make_uint4(sw[4], sw[5], sw[6], sw[7]);
@@ -144,7 +161,7 @@ k_rlc_tree(const uint32_t* in, uint32_t* out, size_t count) {
 // R3: per item, -A and -R as affine niels points; the routing flags
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(RLC_BLOCK, 2)
-k_rlc_points(edk_verify_src src, size_t n, uint32_t* niels_a, uint32_t* niels_r, uint8_t* flags, uint32_t* gflags) {
+k_rlc_points(edk_verify_items src, size_t n, uint32_t* niels_a, uint32_t* niels_r, uint8_t* flags, uint32_t* gflags) {
   const size_t i = (size_t)blockIdx.x * RLC_BLOCK + threadIdx.x;
   if (i >= n) return;
   uint32_t w[8];
@@ -628,9 +645,14 @@ extern "C" hipError_t edk_verify_rlc(uint8_t* ok, uint32_t* stats, const edk_ver
   hipError_t e;
 
   EDK_DO(hipMemsetAsync(gflags, 0, groups * RLC_GROUP_WORDS * 4, stream));
-  const uint32_t* perm = nullptr;
-  EDK_DO(edk_msg_order(&perm, ws, src.msg_off, src.msg_end, n, stream));
-  EDK_LAUNCH(k_rlc_hash, dim3(blocks), dim3(RLC_BLOCK), 0, stream, src, n, ts, leaf, perm);
+  const edk_verify_items items = edk_items_of(&src);
+  if (src.digest) {
+    EDK_LAUNCH(k_rlc_hash_digest, dim3(blocks), dim3(RLC_BLOCK), 0, stream, items, n, ts, leaf);
+  } else {
+    const uint32_t* perm = nullptr;
+    EDK_DO(edk_msg_order(&perm, ws, src.msg_off, src.msg_end, n, stream));
+    EDK_LAUNCH(k_rlc_hash, dim3(blocks), dim3(RLC_BLOCK), 0, stream, items, n, ts, leaf, perm);
+  }
   // the batch seed: a SHA-512 tree of fan-in 64 over the leaves, on the side stream beside k_rlc_points
   EDK_DO(hipEventRecord(ws->ev_prepared, stream));
   EDK_DO(hipStreamWaitEvent(ws->side, ws->ev_prepared, 0));
@@ -647,7 +669,7 @@ extern "C" hipError_t edk_verify_rlc(uint8_t* ok, uint32_t* stats, const edk_ver
   } while (count > 1);
   const uint32_t* seed = level;
   EDK_DO(hipEventRecord(ws->ev_exact, ws->side));
-  EDK_LAUNCH(k_rlc_points, dim3(blocks), dim3(RLC_BLOCK), 0, stream, src, n, niels_a, niels_r, flags, gflags);
+  EDK_LAUNCH(k_rlc_points, dim3(blocks), dim3(RLC_BLOCK), 0, stream, items, n, niels_a, niels_r, flags, gflags);
   EDK_DO(hipStreamWaitEvent(stream, ws->ev_exact, 0));
   EDK_LAUNCH(k_rlc_scalars, dim3((unsigned)(groups * (RLC_G / RLC_BLOCK))), dim3(RLC_BLOCK), 0, stream, n, ts, seed, flags, dig, bsum);
   EDK_LAUNCH(k_rlc_group_scalar, dim3((unsigned)((groups + 63) / 64)), dim3(64), 0, stream, n, bsum, bdig);

@@ -74,14 +74,12 @@ ED_DEV uint8_t rlc_decode_r_lane(ge_niels& nl, const uint32_t rw[8]) {
   return fl;
 }
 
-// t = SHA-512(R || A || M) mod l and S mod l (ed25519-sha512.c:162-172) as words, and the item's leaf
-// SHA-512(SHA-512(R || A || M) || S)[0..32) of the batch hash tree; s_bytes = the 32 bytes of S
-ED_DEV void rlc_hash_lane(uint32_t tw[8], uint32_t sw[8], uint32_t leaf[8], const uint32_t rw[8], const uint32_t aw[8],
-                          const uint8_t* s_bytes, const uint8_t* m, size_t mlen) {
-  uint32_t pre[16], dig[16], lf[16];
-#pragma unroll
-  for (int k = 0; k < 8; k++) { pre[k] = rw[k]; pre[8 + k] = aw[k]; }
-  sha512_prefix_msg<16>(dig, pre, m, mlen);
+// t = digest mod l and S mod l (ed25519-sha512.c:162-172) as words, and the item's leaf SHA-512(digest || S)[0..32) of the
+// batch hash tree, from the digest itself: dig = the 64 bytes of SHA-512(R || A || M) as little-endian words (what
+// rlc_hash_lane computes, or what the caller of ed25519_verify_digests_rlc supplies); s_bytes = the 32 bytes of S.  The leaf
+// depends on the digest BYTES, not on t
+ED_DEV void rlc_digest_lane(uint32_t tw[8], uint32_t sw[8], uint32_t leaf[8], const uint32_t dig[16], const uint8_t* s_bytes) {
+  uint32_t lf[16];
   sha512_prefix_msg<16>(lf, dig, s_bytes, 32);
   sc t, s;
   sc_from_words<16>(t, dig);
@@ -90,6 +88,15 @@ ED_DEV void rlc_hash_lane(uint32_t tw[8], uint32_t sw[8], uint32_t leaf[8], cons
   sc_to_words(sw, s);
 #pragma unroll
   for (int k = 0; k < 8; k++) leaf[k] = lf[k];
+}
+// the same with digest = SHA-512(R || A || M) computed here
+ED_DEV void rlc_hash_lane(uint32_t tw[8], uint32_t sw[8], uint32_t leaf[8], const uint32_t rw[8], const uint32_t aw[8],
+                          const uint8_t* s_bytes, const uint8_t* m, size_t mlen) {
+  uint32_t pre[16], dig[16];
+#pragma unroll
+  for (int k = 0; k < 8; k++) { pre[k] = rw[k]; pre[8 + k] = aw[k]; }
+  sha512_prefix_msg<16>(dig, pre, m, mlen);
+  rlc_digest_lane(tw, sw, leaf, dig, s_bytes);
 }
 
 // l as eight little-endian words
