@@ -69,7 +69,8 @@ typedef struct edk_verify_ws {
                          stores EDK_STATUS_STALLED there; the host side turns it into EDDSA_AMD_STALLED (eddsa_amd.c: take_async_error) */
   hipStream_t side;   /* the exact path runs here, beside the main kernel */
   hipEvent_t ev_prepared, ev_exact;
-  int algo;           /* 0: half-length scalars (four lanes per item up to 24 576 items, one above); 1: always full-length; 2: half-length, one lane per item; 3: the mid-size arrangement below 2^18 items */
+  int algo;           /* 0: half-length scalars (four lanes per item up to 24 576 items, one above); 1: always full-length; 2: half-length, one lane per item;
+                         3: the mid-size arrangement below 2^18 items, full-length from there on.  The table: kernels.hip, verify_route_of */
   int exact_offcurve; /* 1: replay the reference's chain for off-curve keys (default); 0: reject them; 2: replay for every item */
 } edk_verify_ws;
 

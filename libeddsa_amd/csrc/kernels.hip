@@ -251,9 +251,6 @@ constexpr int QUAD_BLOCK = 256;                  // k_verify_main_quad
 constexpr int QUAD_CHAIN_BLOCK = 64;             // k_verify_exact_quad: one wave, up to 16 items
 constexpr int QUAD_CHAIN_ITEMS = QUAD_CHAIN_BLOCK / 4;
 constexpr int QUAD_SPREAD_WAVES = 256;           // a short work list is spread over this many waves, a long one packed 16 items to the wave
-constexpr size_t EXACT_DENSE_MIN_N = (size_t)1 << 16;   // passes from this size on pack the chain's items 16 to the wave whatever their number
-constexpr size_t EXACT_LANE_MIN_LISTED = (size_t)1 << 13;   // (the threshold's table: profiles/r05_exact_lane.txt, 5.) work lists from this length on go to k_verify_exact_lane_* ...
-constexpr size_t EXACT_LANE_MIN_N = (size_t)1 << 16;      // ... in passes of at least this many items
 static_assert((size_t)EDK_EXACT_SLOTS * QUAD_ITEM_WORDS * 4 <= EDK_EXACT_PAD_BYTES, "scratchpad too small");
 static_assert(EDK_EXACT_SLOTS % QUAD_CHAIN_ITEMS == 0, "whole waves");
 
@@ -658,17 +655,6 @@ struct verify_finish_policy {
 };
 
 // small passes: four lanes per item (quad_lanes.h: verify_main_quad); writes the same workspace
-constexpr size_t QUAD_MAIN_MAX_N = (size_t)1 << 14;   // measured: 0.57 vs 0.86 ms at 2^14, equal at 2^15 (tools/verify_sizes.py)
-// the upper bound of k_verify_prepare_pair + k_verify_main_half_quad when the mid-size arrangement below is switched off
-// (algo 0 takes that one above PAIR_ONE_MIN_N items, so the four-lane evaluation serves passes of up to 24 576 items)
-constexpr size_t HALF_QUAD_MAX_N = (size_t)1 << 15;
-// Between 24 576 and 2^18 items: k_verify_prepare_pair, then the ONE-lane evaluation with the long loop in place.  Measured
-// (tools/verify_mid.py, valid signatures, ms): 2^15 0.68 (four-lane evaluation) / 0.70 (one lane per item throughout) -> 0.58,
-// 2^16 0.71-0.76 -> 0.66, 2^17 1.30 -> 1.28; the config-2 mix, whose floor is the exact path: 2^16 1.16 -> 1.11, else equal.
-constexpr size_t PAIR_ONE_MIN_N = (size_t)3 << 13;   // the four-lane evaluation steps up with every 8192 items (0.35 / 0.51 / 0.69 ms: tools/verify_cross.py), this one stays at 0.58
-constexpr size_t QUAD_WIDE_MIN_N = 256;               // four-lane passes above this search pairs up to 2^138 as well (see edk_verify)
-constexpr size_t PAIR_ONE_MAX_N = (size_t)1 << 18;    // the mid-size arrangement (three-lane preparation, one-lane evaluation with the long loop in place) ends here
-constexpr size_t HALF_WIDE_MIN_N = (size_t)1 << 19;   // one-lane passes below this search pairs up to 2^138 (see edk_verify)
 __global__ void __launch_bounds__(QUAD_BLOCK, 2)
 k_verify_main_quad(const uint32_t* digits, const uint32_t* table, const uint32_t* base16, uint32_t* accout, size_t n) {
   const size_t i = ((size_t)blockIdx.x * QUAD_BLOCK + threadIdx.x) >> 2;       // quads are all-or-nothing
@@ -1128,32 +1114,152 @@ k_verify_main_sums_quad(uint8_t* ok, const uint32_t* hdigits, const uint32_t* su
 
 using namespace ed;
 
+constexpr unsigned blocks_of(size_t lanes, size_t block = BLOCK) { return (unsigned)((lanes + block - 1) / block); }
+
+// ---- which kernels a verify pass runs: the thresholds, and verify_route_of, the one function that reads them ----
+constexpr size_t QUAD_MAIN_MAX_N = (size_t)1 << 14;   // measured: 0.57 vs 0.86 ms at 2^14, equal at 2^15 (tools/verify_sizes.py)
+// the upper bound of k_verify_prepare_pair + k_verify_main_half_quad when the mid-size arrangement below is switched off
+// (algo 0 takes that one above PAIR_ONE_MIN_N items, so the four-lane evaluation serves passes of up to 24 576 items)
+constexpr size_t HALF_QUAD_MAX_N = (size_t)1 << 15;
+// Between 24 576 and 2^18 items: k_verify_prepare_pair, then the ONE-lane evaluation with the long loop in place.  Measured
+// (tools/verify_mid.py, valid signatures, ms): 2^15 0.68 (four-lane evaluation) / 0.70 (one lane per item throughout) -> 0.58,
+// 2^16 0.71-0.76 -> 0.66, 2^17 1.30 -> 1.28; the config-2 mix, whose floor is the exact path: 2^16 1.16 -> 1.11, else equal.
+constexpr size_t PAIR_ONE_MIN_N = (size_t)3 << 13;   // the four-lane evaluation steps up with every 8192 items (0.35 / 0.51 / 0.69 ms: tools/verify_cross.py), this one stays at 0.58
+constexpr size_t QUAD_WIDE_MIN_N = 256;               // four-lane passes above this search pairs up to 2^138 as well (see verify_route_of)
+constexpr size_t PAIR_ONE_MAX_N = (size_t)1 << 18;    // the mid-size arrangement (three-lane preparation, one-lane evaluation with the long loop in place) ends here
+constexpr size_t HALF_WIDE_MIN_N = (size_t)1 << 19;   // one-lane passes below this search pairs up to 2^138 (see edk_verify)
+constexpr size_t EXACT_DENSE_MIN_N = (size_t)1 << 16;   // passes from this size on pack the chain's items 16 to the wave whatever their number
+constexpr size_t EXACT_LANE_MIN_LISTED = (size_t)1 << 13;   // (the threshold's table: profiles/r05_exact_lane.txt, 5.) work lists from this length on go to k_verify_exact_lane_* ...
+constexpr size_t EXACT_LANE_MIN_N = (size_t)1 << 16;      // ... in passes of at least this many items
+static_assert(EXACT_LANE_MIN_LISTED <= (size_t)EDK_EXACT_SLOTS && EXACT_LANE_MIN_N <= (size_t)EDK_EXACT_SLOTS, "the four-lane chain's list fits its scratchpad");
+
+enum verify_prepare { PREPARE_ONE, PREPARE_PAIR };     // k_verify_prepare | k_verify_prepare_pair (three lanes per item)
+enum verify_eval { EVAL_FULL_ONE, EVAL_FULL_QUAD,      // k_verify_main | k_verify_main_quad, then k_verify_finish
+                   EVAL_HALF_ONE, EVAL_HALF_ONE_LONG,  // k_verify_main_half | the same with the long loop in place (WITH_LONG)
+                   EVAL_HALF_QUAD, EVAL_SUMS_QUAD };   // k_verify_main_half_quad | k_verify_window_sums + k_verify_main_sums_quad
+struct verify_route {
+  verify_prepare prepare;
+  bool halve;           // k_verify_halve runs
+  bool wide;            // pairs up to 2^HALF_BITS_SMALL in HALF_WINDOWS_SMALL windows instead of HALF_BITS / HALF_WINDOWS, wherever either is a template argument
+  verify_eval eval;
+  uint32_t lane_min;    // the exact path.  != 0: the one-lane kernels are launched too and take the work lists of this many entries or more
+  int dense;            // k_verify_exact_quad packs its items 16 to the wave whatever their number
+  uint32_t main_cost;   // what runs beside k_verify_exact_lane_chain: executed instructions per item, thousands ...
+  int main_all;         // ... over the whole pass (1) or over the on-curve list (0)
+};
+static_assert(HALF_WINDOWS_SMALL == HALF_BITS_SMALL / 4 + 1 && HALF_WINDOWS == HALF_BITS / 4 + 1, "a bound is chosen together with its count of signed four-bit windows");
+
+// algo (eddsa_amd_set_verify_algo) 0: by size, as listed; 1: full-length windows; 2: half-length, one lane per item; 3: the
+// mid-size arrangement - below PAIR_ONE_MAX_N items: a larger pass has no such arrangement and takes the full-length route.
+// Reject mode (exact_offcurve == 0) takes the full-length route whatever the algo: the half-length one relies on the exact
+// path for its give-ups.      n                   prepare   halve  pairs / windows  evaluation
+//   algo 0                    <= 256              pair      -      2^134 / 34       window sums + four-lane chain
+//                             257 .. 2048         pair      -      2^138 / 35       window sums + four-lane chain
+//                             2049 .. 24 576      pair      -      2^138 / 35       half-length, four lanes
+//   algo 0 (3: from 1)        24 577 .. 2^18 - 1  pair      -      2^138 / 35       half-length, one lane, long loop in place
+//   algo 0 (2: from 1)        2^18 .. 2^19 - 1    one lane  yes    2^138 / 35       half-length, one lane
+//   algo 0, 2                 >= 2^19             one lane  yes    2^134 / 34       half-length, one lane
+//   algo 1; 3 from 2^18; reject mode              one lane  -      -                full-length: four lanes up to 2^14 items, one above
+constexpr verify_route verify_route_of(size_t n, int algo, int exact_offcurve) {
+  if (!exact_offcurve) algo = 1;
+  verify_route r = {PREPARE_ONE, false, false, n <= QUAD_MAIN_MAX_N ? EVAL_FULL_QUAD : EVAL_FULL_ONE, 0, 0, 0, 0};
+  // mid-size passes: the three-lane preparation of the small route (its blocks fill the SIMDs that one lane per item leaves
+  // with a single wave) and the one-lane evaluation; algo 3 forces it for measurements
+  if ((algo == 3 || (algo == 0 && n > PAIR_ONE_MIN_N)) && n < PAIR_ONE_MAX_N)
+    r = {PREPARE_PAIR, false, true, EVAL_HALF_ONE_LONG, 0, 0, 0, 0};
+  // The four-lane evaluation runs 64 windows in the wave of an item without a short pair, and the pass waits for that wave:
+  // with pairs up to 2^134 (8.5 items in 10^5) a pass of 2048 items has such an item one time in six, one of 2^14 three
+  // times in four.  Above QUAD_WIDE_MIN_N items the search goes up to 2^138 (2 in 10^7) for a 35th window in every item.
+  else if (algo == 0 && n <= HALF_QUAD_MAX_N)
+    r = {PREPARE_PAIR, false, n > QUAD_WIDE_MIN_N, n <= EDK_SUMS_MAX_ITEMS ? EVAL_SUMS_QUAD : EVAL_HALF_QUAD, 0, 0, 0, 0};
+  else if (algo == 0 || algo == 2)
+    r = {PREPARE_ONE, true, n < HALF_WIDE_MIN_N, EVAL_HALF_ONE, 0, 0, 0, 0};
+  // Passes of EXACT_LANE_MIN_N items or more hand a work list of EXACT_LANE_MIN_LISTED entries or more to the one-lane
+  // kernels; which form runs is decided on the device (the host does not know the list's length): the other ends at once.
+  r.lane_min = n >= EXACT_LANE_MIN_N ? (uint32_t)EXACT_LANE_MIN_LISTED : 0u;
+  r.dense = n >= EXACT_DENSE_MIN_N;
+  // (beside the chain: the half-length evaluation over the on-curve list, 226 k instructions per item, or the full-length one
+  // over the whole pass, 323 k: profiles/pmc_summary.json)
+  const bool half_main = r.eval == EVAL_HALF_ONE || r.eval == EVAL_HALF_ONE_LONG;
+  r.main_cost = half_main ? 226u : 323u;
+  r.main_all = half_main ? 0 : 1;
+  return r;
+}
+constexpr bool route_is(const verify_route& r, verify_prepare prepare, bool halve, bool wide, verify_eval eval) {
+  return r.prepare == prepare && r.halve == halve && r.wide == wide && r.eval == eval;
+}
+static_assert(route_is(verify_route_of(256, 0, 1), PREPARE_PAIR, false, false, EVAL_SUMS_QUAD) && route_is(verify_route_of(257, 0, 1), PREPARE_PAIR, false, true, EVAL_SUMS_QUAD), "QUAD_WIDE_MIN_N");
+static_assert(route_is(verify_route_of(2048, 0, 1), PREPARE_PAIR, false, true, EVAL_SUMS_QUAD) && route_is(verify_route_of(2049, 0, 1), PREPARE_PAIR, false, true, EVAL_HALF_QUAD), "EDK_SUMS_MAX_ITEMS");
+static_assert(route_is(verify_route_of(24576, 0, 1), PREPARE_PAIR, false, true, EVAL_HALF_QUAD) && route_is(verify_route_of(24577, 0, 1), PREPARE_PAIR, false, true, EVAL_HALF_ONE_LONG), "PAIR_ONE_MIN_N");
+static_assert(route_is(verify_route_of((1 << 18) - 1, 0, 1), PREPARE_PAIR, false, true, EVAL_HALF_ONE_LONG) && route_is(verify_route_of(1 << 18, 0, 1), PREPARE_ONE, true, true, EVAL_HALF_ONE), "PAIR_ONE_MAX_N");
+static_assert(route_is(verify_route_of((1 << 19) - 1, 0, 1), PREPARE_ONE, true, true, EVAL_HALF_ONE) && route_is(verify_route_of(1 << 19, 0, 1), PREPARE_ONE, true, false, EVAL_HALF_ONE), "HALF_WIDE_MIN_N");
+static_assert(route_is(verify_route_of(1 << 14, 1, 1), PREPARE_ONE, false, false, EVAL_FULL_QUAD) && route_is(verify_route_of((1 << 14) + 1, 1, 1), PREPARE_ONE, false, false, EVAL_FULL_ONE), "QUAD_MAIN_MAX_N");
+static_assert(route_is(verify_route_of((1 << 18) - 1, 3, 1), PREPARE_PAIR, false, true, EVAL_HALF_ONE_LONG) && route_is(verify_route_of(1 << 18, 3, 1), PREPARE_ONE, false, false, EVAL_FULL_ONE), "algo 3 ends at PAIR_ONE_MAX_N");
+static_assert(route_is(verify_route_of(1, 3, 1), PREPARE_PAIR, false, true, EVAL_HALF_ONE_LONG) && route_is(verify_route_of(1, 2, 1), PREPARE_ONE, true, true, EVAL_HALF_ONE), "algo 2 and 3 from one item on");
+static_assert(route_is(verify_route_of(2048, 0, 0), PREPARE_ONE, false, false, EVAL_FULL_QUAD) && route_is(verify_route_of(1 << 17, 3, 0), PREPARE_ONE, false, false, EVAL_FULL_ONE) && route_is(verify_route_of(1 << 19, 2, 0), PREPARE_ONE, false, false, EVAL_FULL_ONE), "reject mode");
+static_assert(verify_route_of((1 << 16) - 1, 0, 1).lane_min == 0 && !verify_route_of((1 << 16) - 1, 0, 1).dense && verify_route_of(1 << 16, 0, 1).lane_min == 8192 && verify_route_of(1 << 16, 0, 1).dense, "EXACT_LANE_MIN_N, EXACT_DENSE_MIN_N");
+static_assert(verify_route_of(1 << 16, 0, 1).main_cost == 226 && verify_route_of(1 << 16, 0, 1).main_all == 0 && verify_route_of(1 << 16, 1, 1).main_cost == 323 && verify_route_of(1 << 16, 1, 1).main_all == 1, "the chain's hint follows the evaluation");
+
+// the first kernel of a verify pass: the three-lane preparation or the one-lane one.
+// DIGEST: the forms that take t from the caller's digest (edk_verify_src.digest)
+template <bool DIGEST>
+static hipError_t launch_prepare(const edk_verify_items& src, size_t n, const edk_verify_ws* ws, const verify_route& r, const uint32_t* perm, hipStream_t stream) {
+  const unsigned blocks = blocks_of(n), pair_point_blocks = blocks_of(2 * n);
+  if (r.prepare == PREPARE_PAIR) {
+    const auto k = r.wide ? k_verify_prepare_pair<HALF_BITS_SMALL, DIGEST> : k_verify_prepare_pair<HALF_BITS, DIGEST>;
+    EDK_LAUNCH(k, dim3(pair_point_blocks + blocks), dim3(BLOCK), 0, stream, src, n, ws->digits, ws->hdigits, ws->table, ws->rtable, ws->flags,
+               ws->onlist, ws->offlist, ws->offcount, ws->exact_offcurve == 2, pair_point_blocks, perm);
+  } else
+    EDK_LAUNCH(k_verify_prepare<DIGEST>, dim3(blocks), dim3(BLOCK), 0, stream, src, n, ws->digits, ws->table, ws->flags, ws->onlist, ws->offlist,
+               ws->offcount, ws->exact_offcurve == 2, perm);
+  return hipSuccess;
+}
+
+// ---- the fixed-base operations: the shapes of their two kernels ----
 // Items per lane that share one inversion in the finish kernels: FINISH_K (8) in a pass that fills the chip; in a smaller
 // pass as few as it takes to keep one block of 256 lanes per CU - a lane with one item runs 31 k dependent instructions,
 // with eight 70 k, and a pass of 2^12 items would otherwise occupy two CUs.
-static unsigned finish_k(size_t n) {
-  const size_t tiles = (n + BLOCK - 1) / BLOCK;
-  for (unsigned k = 1; k < (unsigned)FINISH_K; k *= 2)
-    if ((tiles + k - 1) / k <= 256) return k;
-  return FINISH_K;
+struct finish_shape { unsigned grid; int k; };
+constexpr finish_shape finish_shape_of(size_t n) {
+  unsigned k = 1;
+  while (k < (unsigned)FINISH_K && (blocks_of(n) + k - 1) / k > 256) k *= 2;
+  return {(blocks_of(n) + k - 1) / k, (int)k};
 }
 
-// the first kernel of a verify pass: the three-lane preparation with pairs up to 2^pair_bits, or (pair_bits == 0) the one-lane one.
-// DIGEST: the forms that take t from the caller's digest (edk_verify_src.digest)
-template <bool DIGEST>
-static hipError_t launch_prepare(const edk_verify_items& src, size_t n, const edk_verify_ws* ws, int pair_bits, const uint32_t* perm, hipStream_t stream) {
-  const unsigned blocks = (unsigned)((n + BLOCK - 1) / BLOCK), pair_point_blocks = (unsigned)((2 * n + BLOCK - 1) / BLOCK);
-  if (pair_bits == HALF_BITS_SMALL)
-    EDK_LAUNCH((k_verify_prepare_pair<HALF_BITS_SMALL, DIGEST>), dim3(pair_point_blocks + blocks), dim3(BLOCK), 0, stream, src, n,
-               ws->digits, ws->hdigits, ws->table, ws->rtable, ws->flags, ws->onlist, ws->offlist, ws->offcount, ws->exact_offcurve == 2,
-               pair_point_blocks, perm);
-  else if (pair_bits == HALF_BITS)
-    EDK_LAUNCH((k_verify_prepare_pair<HALF_BITS, DIGEST>), dim3(pair_point_blocks + blocks), dim3(BLOCK), 0, stream, src, n,
-               ws->digits, ws->hdigits, ws->table, ws->rtable, ws->flags, ws->onlist, ws->offlist, ws->offcount, ws->exact_offcurve == 2,
-               pair_point_blocks, perm);
-  else
-    EDK_LAUNCH(k_verify_prepare<DIGEST>, dim3(blocks), dim3(BLOCK), 0, stream, src, n, ws->digits, ws->table, ws->flags, ws->onlist, ws->offlist,
-               ws->offcount, ws->exact_offcurve == 2, perm);
+// Point kernels stage the comb in LDS per block, one block per CU.  A pass that fills the chip runs blocks of POINT_BLOCK
+// lanes (two waves per SIMD).  A smaller pass runs smaller blocks: a block of 512 lanes puts two waves on every SIMD of
+// ONE CU, which then take turns (a single ed25519_genpub ran its one useful wave beside seven idle-lane waves redoing
+// the same item: 0.23 ms in the point kernel against 0.12 with a wave to itself), and 4096 items occupied 8 CUs of 256.
+// So: the smallest block that covers the pass with one block per CU - one, two or four waves, each with a SIMD to itself.
+// Passes of up to POINT_SPLIT_MAX_N items spend four lanes on an item (lanes.h: scale_base_lane<4>, k_genpub_point above): the 44 additions of
+// the comb in a row were the latency of the pass (a single ed25519_sign: 0.17 ms in k_sign_point, now 0.09).  A pass with more
+// tiles than CUs runs POINT_MAX_BLOCKS persistent blocks whose waves draw their tiles from ws->tiles (point_tile above); a smaller
+// one a block per tile, without the counter.
+constexpr size_t POINT_SPLIT_MAX_N = (size_t)1 << 14;
+struct point_shape { int lanes_per_item; unsigned block, grid; bool persistent; };
+constexpr point_shape point_shape_of(size_t n) {
+  if (n <= POINT_SPLIT_MAX_N) return {POINT_SPLIT, POINT_SPLIT * 64, blocks_of(n, POINT_SPLIT_ITEMS), false};
+  const unsigned block = n <= (size_t)64 * 256 ? 64 : n <= (size_t)128 * 256 ? 128 : n <= (size_t)256 * 256 ? 256 : POINT_BLOCK;
+  const unsigned tiles = blocks_of(n, block);
+  return {1, block, tiles > POINT_MAX_BLOCKS ? POINT_MAX_BLOCKS : tiles, tiles > POINT_MAX_BLOCKS};
+}
+constexpr bool shape_is(const point_shape& s, int lanes_per_item, unsigned block, unsigned grid, bool persistent) {
+  return s.lanes_per_item == lanes_per_item && s.block == block && s.grid == grid && s.persistent == persistent;
+}
+static_assert(shape_is(point_shape_of(1 << 14), 4, 256, 256, false) && shape_is(point_shape_of((1 << 14) + 1), 1, 128, 129, false), "POINT_SPLIT_MAX_N");
+static_assert(shape_is(point_shape_of(1 << 15), 1, 128, 256, false) && shape_is(point_shape_of((1 << 15) + 1), 1, 256, 129, false), "two waves, four waves");
+static_assert(shape_is(point_shape_of(1 << 16), 1, 256, 256, false) && shape_is(point_shape_of((1 << 16) + 1), 1, POINT_BLOCK, blocks_of((1 << 16) + 1, POINT_BLOCK), false), "four waves, POINT_BLOCK");
+static_assert(shape_is(point_shape_of((size_t)POINT_MAX_BLOCKS * POINT_BLOCK), 1, POINT_BLOCK, POINT_MAX_BLOCKS, false) &&
+              shape_is(point_shape_of((size_t)POINT_MAX_BLOCKS * POINT_BLOCK + 1), 1, POINT_BLOCK, POINT_MAX_BLOCKS, true), "more tiles than resident blocks: persistent");
+
+// the point kernel of a pass of n items in the form its shape asks for (split: PARTS = POINT_SPLIT, whole: PARTS = 1); args: the
+// kernel's arguments without its last, the tile counter.  Unchecked like every fixed-base launch: the caller asks hipGetLastError
+template <class K, class... A>
+static hipError_t launch_point(K split, K whole, size_t n, const edk_fixed_ws* ws, hipStream_t stream, A... args) {
+  const point_shape s = point_shape_of(n);
+  if (s.persistent)
+    if (const hipError_t e = hipMemsetAsync(ws->tiles, 0, sizeof(uint32_t), stream); e != hipSuccess) return e;
+  hipLaunchKernelGGL(s.lanes_per_item == POINT_SPLIT ? split : whole, dim3(s.grid), dim3(s.block), 0, stream, args..., s.persistent ? ws->tiles : (uint32_t*)nullptr);
   return hipSuccess;
 }
 
@@ -1166,16 +1272,14 @@ hipError_t edk_init_tables(uint32_t* base16, uint32_t* comb, uint32_t* comb_img,
   return hipGetLastError();
 }
 
-hipError_t edk_x25519(uint8_t* out, const uint8_t* scalars, const uint8_t* points, size_t n,
-                      const edk_fixed_ws* ws, hipStream_t stream) {
+hipError_t edk_x25519(uint8_t* out, const uint8_t* scalars, const uint8_t* points, size_t n, const edk_fixed_ws* ws, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  const unsigned blocks = (unsigned)((n + BLOCK - 1) / BLOCK);
+  const finish_shape f = finish_shape_of(n);
   if (n <= X25519_QUAD_MAX_N)
-    hipLaunchKernelGGL(k_x25519_ladder_quad, dim3((unsigned)((4 * n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, ws->acc,
-                       scalars, points, n);
+    hipLaunchKernelGGL(k_x25519_ladder_quad, dim3(blocks_of(4 * n)), dim3(BLOCK), 0, stream, ws->acc, scalars, points, n);
   else
-    hipLaunchKernelGGL(k_x25519_ladder, dim3(blocks), dim3(BLOCK), 0, stream, ws->acc, scalars, points, n);
-  hipLaunchKernelGGL(k_x25519_finish, dim3((blocks + finish_k(n) - 1) / finish_k(n)), dim3(BLOCK), 0, stream, out, ws->acc, n, (int)finish_k(n));
+    hipLaunchKernelGGL(k_x25519_ladder, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, ws->acc, scalars, points, n);
+  hipLaunchKernelGGL(k_x25519_finish, dim3(f.grid), dim3(BLOCK), 0, stream, out, ws->acc, n, f.k);
   return hipGetLastError();
 }
 
@@ -1198,27 +1302,25 @@ int edk_debug_fail_in(int nth) {
   return 0;
 }
 
-// perm[0..n) = the items in order of message length, longest first (k_len_*): bins = 2 * LEN_BINS words of the workspace
-static hipError_t msg_order(uint32_t* perm, uint32_t* bins, const uint64_t* msg_off, const uint64_t* msg_end, size_t n, hipStream_t stream) {
-  const unsigned blocks = (unsigned)((n + BLOCK - 1) / BLOCK);
+// *perm = buf[0..n) filled with the items in order of message length, longest first (k_len_*; bins = 2 * LEN_BINS words of the
+// workspace), or nullptr where the pass takes its items as they come: no offset table, or fewer than MSG_ORDER_MIN_N items
+static hipError_t msg_order(const uint32_t** perm, uint32_t* buf, uint32_t* bins, const uint64_t* msg_off, const uint64_t* msg_end, size_t n, hipStream_t stream) {
+  *perm = nullptr;
+  if (!msg_off || n < MSG_ORDER_MIN_N) return hipSuccess;
   hipError_t e = hipMemsetAsync(bins, 0, (size_t)LEN_BINS * sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
   static_assert(LEN_BINS % BLOCK == 0, "k_len_starts: a thread takes LEN_BINS / BLOCK bins");
-  hipLaunchKernelGGL(k_len_count, dim3(blocks), dim3(BLOCK), 0, stream, bins, msg_off, msg_end, n);
+  hipLaunchKernelGGL(k_len_count, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, bins, msg_off, msg_end, n);
   hipLaunchKernelGGL(k_len_starts, dim3(1), dim3(BLOCK), 0, stream, bins);
-  hipLaunchKernelGGL(k_len_place, dim3(blocks), dim3(BLOCK), 0, stream, perm, bins, msg_off, msg_end, n);
-  return hipGetLastError();
+  hipLaunchKernelGGL(k_len_place, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, buf, bins, msg_off, msg_end, n);
+  e = hipGetLastError();
+  if (e == hipSuccess) *perm = buf;
+  return e;
 }
 
-// the verify workspace's order for a pass of n items, or *perm = nullptr where the pass takes its items as they come
-// (no offset table, or fewer than MSG_ORDER_MIN_N items); rlc.hip's hashing kernel shares it
-hipError_t edk_msg_order(const uint32_t** perm, const edk_verify_ws* ws, const uint64_t* msg_off, const uint64_t* msg_end, size_t n,
-                         hipStream_t stream) {
-  *perm = nullptr;
-  if (!msg_off || n < MSG_ORDER_MIN_N) return hipSuccess;
-  const hipError_t e = msg_order(ws->perm, ws->lenbins, msg_off, msg_end, n, stream);
-  if (e == hipSuccess) *perm = ws->perm;
-  return e;
+// the verify workspace's order for a pass of n items; rlc.hip's hashing kernel shares it
+hipError_t edk_msg_order(const uint32_t** perm, const edk_verify_ws* ws, const uint64_t* msg_off, const uint64_t* msg_end, size_t n, hipStream_t stream) {
+  return msg_order(perm, ws->perm, ws->lenbins, msg_off, msg_end, n, stream);
 }
 
 // Every HIP call below that orders work or moves data is checked (edk_checked.h): the first failure ends the pass with
@@ -1228,194 +1330,125 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
                       const edk_verify_ws* ws, hipEvent_t* marks, hipEvent_t bulk_done, int bulk_early, hipStream_t stream) {
   const edk_verify_src src = *srcp;
   if (n == 0) return hipSuccess;
-  const unsigned blocks = (unsigned)((n + BLOCK - 1) / BLOCK);
-  EDK_DO(hipMemsetAsync(ws->offcount, 0, EDK_PASS_WORDS * sizeof(uint32_t), stream));   // both work lists' lengths, the one-lane exact path's unit counter and its stall flag
+  const verify_route r = verify_route_of(n, ws->algo, ws->exact_offcurve);
+  const unsigned blocks = blocks_of(n), quad_blocks = blocks_of(4 * n, QUAD_BLOCK);
+  // 1. reset: both work lists' lengths, the one-lane exact path's unit counter and its stall flag
+  EDK_DO(hipMemsetAsync(ws->offcount, 0, EDK_PASS_WORDS * sizeof(uint32_t), stream));
   if (marks) EDK_DO(hipEventRecord(marks[0], stream));
-  // algo 0: half-length scalars - the three-lane preparation and four lanes per item up to 24 576 items, the same preparation and one lane per item up to 2^18, one lane per item above;
-  // 3: the mid-size arrangement at any size below 2^18;
-  // 1: full-length windows (one lane per item above QUAD_MAIN_MAX_N items, quads below); 2: half-length, one lane per item
-  const bool small = n <= QUAD_MAIN_MAX_N;
-  const bool small_half = n <= HALF_QUAD_MAX_N;
-  const int algo = ws->exact_offcurve ? ws->algo : 1;   // the half-length route relies on the exact path for its give-ups
-  const bool wide = n < HALF_WIDE_MIN_N;
-  // mid-size passes: the three-lane preparation of the small route (its blocks fill the SIMDs that one lane per item leaves
-  // with a single wave) and the one-lane evaluation; algo 3 forces it for measurements
-  const bool pair_one = n < PAIR_ONE_MAX_N && (algo == 3 || (algo == 0 && n > PAIR_ONE_MIN_N));
-  const bool half = !pair_one && (algo == 2 || (algo == 0 && !small_half));
-  const bool half_quad = !pair_one && algo == 0 && small_half;
-  // The four-lane evaluation runs 64 windows in the wave of an item without a short pair, and the pass waits for that wave:
-  // with pairs up to 2^134 (8.5 items in 10^5) a pass of 2048 items has such an item one time in six, one of 2^14 three
-  // times in four.  Above QUAD_WIDE_MIN_N items the search goes up to 2^138 (2 in 10^7) for a 35th window in every item.
-  const bool quad_wide = half_quad && n > QUAD_WIDE_MIN_N;
-  // ragged messages: the hashing kernels take their items in order of length
+  // 2. message order: the hashing kernels take ragged messages in order of length
   const uint32_t* perm = nullptr;
   if (!src.digest) EDK_DO(edk_msg_order(&perm, ws, src.msg_off, src.msg_end, n, stream));
-  // caller-supplied digests (ed25519_verify_digests*): the same three preparations without the hash; everything after them
-  // reads t from the workspace and does not know
-  const int pair_bits = pair_one || quad_wide ? HALF_BITS_SMALL : half_quad ? HALF_BITS : 0;
-  const hipError_t prepared = src.digest ? launch_prepare<true>(edk_items_of(&src), n, ws, pair_bits, perm, stream) : launch_prepare<false>(edk_items_of(&src), n, ws, pair_bits, perm, stream);
+  // 3. prepare.  Caller-supplied digests (ed25519_verify_digests*): the same preparations without the hash; everything after
+  // them reads t from the workspace and does not know
+  const hipError_t prepared = src.digest ? launch_prepare<true>(edk_items_of(&src), n, ws, r, perm, stream) : launch_prepare<false>(edk_items_of(&src), n, ws, r, perm, stream);
   if (prepared != hipSuccess) return prepared;
-  // Below HALF_WIDE_MIN_N items the pass searches pairs up to 2^138 and runs 35 windows (2 t in 10^7 without a pair instead
-  // of 8.5 in 10^5; 3 % more instructions in the main kernel): an item without a short pair goes through the exact path's
-  // chain, and beside a main kernel of one or two rounds of resident blocks that chain costs the pass 0.3-0.4 ms (the
+  // 4. halve.  Below HALF_WIDE_MIN_N items the pass searches pairs up to 2^138 and runs 35 windows (2 t in 10^7 without a pair
+  // instead of 8.5 in 10^5; 3 % more instructions in the main kernel): an item without a short pair goes through the exact
+  // path's chain, and beside a main kernel of one or two rounds of resident blocks that chain costs the pass 0.3-0.4 ms (the
   // SIMDs its waves sit on finish their tiles that much later and the grid has no slack: profiles/r04_small_grid.txt)
-  if (half && wide)
-    EDK_LAUNCH(k_verify_halve<HALF_BITS_SMALL>, dim3(blocks), dim3(BLOCK), 0, stream, src.sigs, src.sig_stride, ws->digits,
-               ws->hdigits, ws->rtable, ws->flags, ws->onlist, ws->offlist, ws->offcount);
-  else if (half)
-    EDK_LAUNCH(k_verify_halve<HALF_BITS>, dim3(blocks), dim3(BLOCK), 0, stream, src.sigs, src.sig_stride, ws->digits,
-               ws->hdigits, ws->rtable, ws->flags, ws->onlist, ws->offlist, ws->offcount);
+  if (r.halve) {
+    const auto k = r.wide ? k_verify_halve<HALF_BITS_SMALL> : k_verify_halve<HALF_BITS>;
+    EDK_LAUNCH(k, dim3(blocks), dim3(BLOCK), 0, stream, src.sigs, src.sig_stride, ws->digits, ws->hdigits, ws->rtable, ws->flags, ws->onlist, ws->offlist, ws->offcount);
+  }
   if (marks) EDK_DO(hipEventRecord(marks[1], stream));
   if (bulk_done && bulk_early) EDK_DO(hipEventRecord(bulk_done, stream));   // the next pass may start beside this one's main kernel
-  // the exact path depends only on what came before: it runs beside the main kernel on the side stream
+  // 5. the exact path depends only on what came before: it runs beside the main kernel on the side stream
   if (ws->exact_offcurve) {
-    // Passes of EXACT_LANE_MIN_N items or more hand a work list of EXACT_LANE_MIN_LISTED entries or more to the one-lane
-    // kernels; which form runs is decided on the device (the host does not know the list's length): the other ends at once.
-    const uint32_t lane_min = n >= EXACT_LANE_MIN_N ? (uint32_t)EXACT_LANE_MIN_LISTED : 0u;
     EDK_DO(hipEventRecord(ws->ev_prepared, stream));
     EDK_DO(hipStreamWaitEvent(ws->side, ws->ev_prepared, 0));
     // The one-lane kernels go FIRST on the side stream: when the list is short they end at once, and they must do so while
     // the chip still has room for their (large) blocks - queued behind the four-lane chain they reached the dispatcher a
     // millisecond into a full k_verify_main_half, where each of their 512 idle blocks had to wait for two wave slots of one
     // SIMD to fall free together (profiles/r05_exact_lane.txt: same-box A/B, 107.2 -> 107.9 M/s on config 2).
-    if (lane_min != 0) {
+    if (r.lane_min != 0) {
       const unsigned lane_blocks = blocks < EXACT_LANE_BLOCKS ? blocks : EXACT_LANE_BLOCKS;
       // (the scratchpad of the four-lane chain is free when these run: it holds their per-tile counts)
       EDK_LAUNCH(k_verify_exact_lane_setup, dim3(lane_blocks), dim3(BLOCK), 0, ws->side, ws->digits, ws->table, ws->rtable, ws->offlist,
-                 ws->offcount, base16, ws->exact_pad, lane_min);
-      // (what runs beside it: the half-length evaluation over the on-curve list, 226 k instructions per item, or the
-      // full-length one over the whole pass, 323 k: profiles/pmc_summary.json)
-      const bool half_main = half || pair_one;
+                 ws->offcount, base16, ws->exact_pad, r.lane_min);
       EDK_LAUNCH(k_verify_exact_lane_chain, dim3(lane_blocks), dim3(BLOCK), 0, ws->side, ok, src.sigs, src.sig_stride, ws->table, ws->rtable,
-                 ws->offlist, ws->offcount, ws->exact_pad, lane_min, n, half_main ? 226u : 323u, half_main ? 0 : 1, ws->status);
+                 ws->offlist, ws->offcount, ws->exact_pad, r.lane_min, n, r.main_cost, r.main_all, ws->status);
     }
-    {
-      // one launch: a list it would serve has fewer entries than the scratchpad has slots (lane_min != 0: fewer than lane_min;
-      // else the pass itself is smaller than EXACT_LANE_MIN_N)
-      static_assert(EXACT_LANE_MIN_LISTED <= (size_t)EDK_EXACT_SLOTS && EXACT_LANE_MIN_N <= (size_t)EDK_EXACT_SLOTS, "the four-lane chain's list fits its scratchpad");
-      const size_t qi = lane_min != 0 ? (size_t)lane_min : n;
-      const size_t dense = (qi + QUAD_CHAIN_ITEMS - 1) / QUAD_CHAIN_ITEMS, spread = qi < (size_t)QUAD_SPREAD_WAVES ? qi : (size_t)QUAD_SPREAD_WAVES;
-      EDK_LAUNCH(k_verify_exact_quad, dim3((unsigned)(dense > spread ? dense : spread)), dim3(QUAD_CHAIN_BLOCK), 0, ws->side, ok,
-                 src.sigs, src.sig_stride, ws->digits, ws->table, ws->offlist, ws->offcount, base16, ws->exact_pad,
-                 (int)(n >= EXACT_DENSE_MIN_N), lane_min);
-    }
+    // one launch of the four-lane chain: a list it would serve has fewer entries than the scratchpad has slots (lane_min != 0:
+    // fewer than lane_min; else the pass itself is smaller than EXACT_LANE_MIN_N)
+    const size_t qi = r.lane_min != 0 ? (size_t)r.lane_min : n;
+    const size_t dense = (qi + QUAD_CHAIN_ITEMS - 1) / QUAD_CHAIN_ITEMS, spread = qi < (size_t)QUAD_SPREAD_WAVES ? qi : (size_t)QUAD_SPREAD_WAVES;
+    EDK_LAUNCH(k_verify_exact_quad, dim3((unsigned)(dense > spread ? dense : spread)), dim3(QUAD_CHAIN_BLOCK), 0, ws->side, ok, src.sigs,
+               src.sig_stride, ws->digits, ws->table, ws->offlist, ws->offcount, base16, ws->exact_pad, r.dense, r.lane_min);
     EDK_DO(hipEventRecord(ws->ev_exact, ws->side));
   }
-  if (half_quad && n <= EDK_SUMS_MAX_ITEMS) {
-    static_assert(QUAD_BLOCK == 4 * HALF_LONG_WINDOWS, "a block of k_verify_window_sums is the windows of one item");
-    if (quad_wide) {
-      EDK_LAUNCH(k_verify_window_sums<HALF_WINDOWS_SMALL>, dim3((unsigned)n), dim3(QUAD_BLOCK), 0, stream, ws->sums, ws->hdigits, ws->table, ws->rtable, base16);
-      EDK_LAUNCH(k_verify_main_sums_quad<HALF_WINDOWS_SMALL>, dim3((unsigned)((4 * n + QUAD_BLOCK - 1) / QUAD_BLOCK)), dim3(QUAD_BLOCK), 0, stream,
-                 ok, ws->hdigits, ws->sums, ws->flags, n, ws->exact_offcurve);
-    } else {
-      EDK_LAUNCH(k_verify_window_sums<HALF_WINDOWS>, dim3((unsigned)n), dim3(QUAD_BLOCK), 0, stream, ws->sums, ws->hdigits, ws->table, ws->rtable, base16);
-      EDK_LAUNCH(k_verify_main_sums_quad<HALF_WINDOWS>, dim3((unsigned)((4 * n + QUAD_BLOCK - 1) / QUAD_BLOCK)), dim3(QUAD_BLOCK), 0, stream,
-                 ok, ws->hdigits, ws->sums, ws->flags, n, ws->exact_offcurve);
-    }
-    if (marks) { EDK_DO(hipEventRecord(marks[2], stream)); EDK_DO(hipEventRecord(marks[3], stream)); }
-  } else if (half_quad) {
-    if (quad_wide)
-      EDK_LAUNCH(k_verify_main_half_quad<HALF_WINDOWS_SMALL>, dim3((unsigned)((4 * n + QUAD_BLOCK - 1) / QUAD_BLOCK)), dim3(QUAD_BLOCK), 0, stream,
-                 ok, ws->hdigits, ws->table, ws->rtable, base16, ws->flags, n, ws->exact_offcurve);
-    else
-      EDK_LAUNCH(k_verify_main_half_quad<HALF_WINDOWS>, dim3((unsigned)((4 * n + QUAD_BLOCK - 1) / QUAD_BLOCK)), dim3(QUAD_BLOCK), 0, stream,
-                 ok, ws->hdigits, ws->table, ws->rtable, base16, ws->flags, n, ws->exact_offcurve);
-    if (marks) { EDK_DO(hipEventRecord(marks[2], stream)); EDK_DO(hipEventRecord(marks[3], stream)); }
-  } else if (half || pair_one) {
-    constexpr unsigned half_lds = MAIN_LDS_RESERVE;
-    static_assert(HALF_DIGIT_WORDS * MAIN_HALF_BLOCK * 4 <= half_lds, "k_verify_main_half keeps its digit words in the block's LDS");
-    const unsigned hblocks = (blocks * BLOCK + MAIN_HALF_BLOCK - 1) / MAIN_HALF_BLOCK;
-    if (pair_one)
-      EDK_LAUNCH((k_verify_main_half<HALF_WINDOWS_SMALL, true>), dim3(hblocks), dim3(MAIN_HALF_BLOCK), half_lds, stream, ok, ws->hdigits,
-                 ws->table, ws->rtable, base16, ws->flags, ws->onlist, ws->offcount);
-    else if (wide)
-      EDK_LAUNCH(k_verify_main_half<HALF_WINDOWS_SMALL>, dim3(hblocks), dim3(MAIN_HALF_BLOCK), half_lds, stream, ok, ws->hdigits,
-                 ws->table, ws->rtable, base16, ws->flags, ws->onlist, ws->offcount);
-    else
-      EDK_LAUNCH(k_verify_main_half<HALF_WINDOWS>, dim3(hblocks), dim3(MAIN_HALF_BLOCK), half_lds, stream, ok, ws->hdigits,
-                 ws->table, ws->rtable, base16, ws->flags, ws->onlist, ws->offcount);
-    if (marks) { EDK_DO(hipEventRecord(marks[2], stream)); EDK_DO(hipEventRecord(marks[3], stream)); }
-  } else {
-    if (small)
-      EDK_LAUNCH(k_verify_main_quad, dim3((unsigned)((4 * n + QUAD_BLOCK - 1) / QUAD_BLOCK)), dim3(QUAD_BLOCK), 0,
-                 stream, ws->digits, ws->table, base16, ws->acc, n);
-    else
-      EDK_LAUNCH(k_verify_main, dim3(blocks), dim3(BLOCK), MAIN_LDS_RESERVE, stream, ws->digits, ws->table, base16, ws->acc);
-    if (marks) EDK_DO(hipEventRecord(marks[2], stream));
-    EDK_LAUNCH(k_verify_finish, dim3((blocks + finish_k(n) - 1) / finish_k(n)), dim3(BLOCK), 0, stream, ok, src.sigs,
-               src.sig_stride, ws->acc, ws->flags, n, ws->exact_offcurve, (int)finish_k(n));
-    if (marks) EDK_DO(hipEventRecord(marks[3], stream));
+  // 6. evaluation; the half-length ones have no finish kernel: both marks at their end
+  switch (r.eval) {
+    case EVAL_SUMS_QUAD: {
+      static_assert(QUAD_BLOCK == 4 * HALF_LONG_WINDOWS, "a block of k_verify_window_sums is the windows of one item");
+      const auto sums = r.wide ? k_verify_window_sums<HALF_WINDOWS_SMALL> : k_verify_window_sums<HALF_WINDOWS>;
+      const auto chain = r.wide ? k_verify_main_sums_quad<HALF_WINDOWS_SMALL> : k_verify_main_sums_quad<HALF_WINDOWS>;
+      EDK_LAUNCH(sums, dim3((unsigned)n), dim3(QUAD_BLOCK), 0, stream, ws->sums, ws->hdigits, ws->table, ws->rtable, base16);
+      EDK_LAUNCH(chain, dim3(quad_blocks), dim3(QUAD_BLOCK), 0, stream, ok, ws->hdigits, ws->sums, ws->flags, n, ws->exact_offcurve);
+    } break;
+    case EVAL_HALF_QUAD: {
+      const auto k = r.wide ? k_verify_main_half_quad<HALF_WINDOWS_SMALL> : k_verify_main_half_quad<HALF_WINDOWS>;
+      EDK_LAUNCH(k, dim3(quad_blocks), dim3(QUAD_BLOCK), 0, stream, ok, ws->hdigits, ws->table, ws->rtable, base16, ws->flags, n, ws->exact_offcurve);
+    } break;
+    case EVAL_HALF_ONE: case EVAL_HALF_ONE_LONG: {
+      constexpr unsigned half_lds = MAIN_LDS_RESERVE;
+      static_assert(HALF_DIGIT_WORDS * MAIN_HALF_BLOCK * 4 <= half_lds, "k_verify_main_half keeps its digit words in the block's LDS");
+      const unsigned hblocks = (blocks * BLOCK + MAIN_HALF_BLOCK - 1) / MAIN_HALF_BLOCK;
+      const auto k = r.eval == EVAL_HALF_ONE_LONG ? k_verify_main_half<HALF_WINDOWS_SMALL, true> : r.wide ? k_verify_main_half<HALF_WINDOWS_SMALL> : k_verify_main_half<HALF_WINDOWS>;
+      EDK_LAUNCH(k, dim3(hblocks), dim3(MAIN_HALF_BLOCK), half_lds, stream, ok, ws->hdigits, ws->table, ws->rtable, base16, ws->flags, ws->onlist, ws->offcount);
+    } break;
+    case EVAL_FULL_QUAD: EDK_LAUNCH(k_verify_main_quad, dim3(quad_blocks), dim3(QUAD_BLOCK), 0, stream, ws->digits, ws->table, base16, ws->acc, n); break;
+    case EVAL_FULL_ONE: EDK_LAUNCH(k_verify_main, dim3(blocks), dim3(BLOCK), MAIN_LDS_RESERVE, stream, ws->digits, ws->table, base16, ws->acc); break;
   }
+  if (marks) EDK_DO(hipEventRecord(marks[2], stream));
+  if (r.eval == EVAL_FULL_ONE || r.eval == EVAL_FULL_QUAD) {
+    const finish_shape f = finish_shape_of(n);
+    EDK_LAUNCH(k_verify_finish, dim3(f.grid), dim3(BLOCK), 0, stream, ok, src.sigs, src.sig_stride, ws->acc, ws->flags, n, ws->exact_offcurve, f.k);
+  }
+  if (marks) EDK_DO(hipEventRecord(marks[3], stream));
   // everything that fills the chip has been queued; what follows on this stream only waits for the exact path's few
   // latency-bound waves: a caller that pipelines passes over several workspaces starts the next pass from here
   if (bulk_done && !bulk_early) EDK_DO(hipEventRecord(bulk_done, stream));
-  if (ws->exact_offcurve) EDK_DO(hipStreamWaitEvent(stream, ws->ev_exact, 0));   // complete when both paths are
+  // 7. the join: complete when both paths are
+  if (ws->exact_offcurve) EDK_DO(hipStreamWaitEvent(stream, ws->ev_exact, 0));
   return hipSuccess;
 }
 
-#define EDK_GRID(n) dim3((unsigned)(((n) + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream
-
-// Point kernels stage the comb in LDS per block, one block per CU.  A pass that fills the chip runs blocks of POINT_BLOCK
-// lanes (two waves per SIMD).  A smaller pass runs smaller blocks: a block of 512 lanes puts two waves on every SIMD of
-// ONE CU, which then take turns (a single ed25519_genpub ran its one useful wave beside seven idle-lane waves redoing
-// the same item: 0.23 ms in the point kernel against 0.12 with a wave to itself), and 4096 items occupied 8 CUs of 256.
-// So: the smallest block that covers the pass with one block per CU - one, two or four waves, each with a SIMD to itself.
-#define POINT_LANES(n) ((n) <= (size_t)64 * 256 ? 64 : (n) <= (size_t)128 * 256 ? 128 : (n) <= (size_t)256 * 256 ? 256 : POINT_BLOCK)
-#define POINT_GRID_BLOCKS(n) ((unsigned)(((n) + POINT_LANES(n) - 1) / POINT_LANES(n)))
-// Passes of up to POINT_SPLIT_MAX_N items spend four lanes on an item (lanes.h: scale_base_lane<4>, k_genpub_point above): the 44 additions of
-// the comb in a row were the latency of the pass (a single ed25519_sign: 0.17 ms in k_sign_point, now 0.09).  A pass with more
-// tiles than CUs runs POINT_MAX_BLOCKS persistent blocks whose waves draw their tiles from ws->tiles (point_tile above); a smaller
-// one a block per tile, without the counter.
-constexpr size_t POINT_SPLIT_MAX_N = (size_t)1 << 14;
-#define EDK_POINT_LAUNCH(kernel, n, ...) do { \
-    if ((n) <= POINT_SPLIT_MAX_N) hipLaunchKernelGGL((kernel<POINT_SPLIT>), dim3((unsigned)(((n) + POINT_SPLIT_ITEMS - 1) / POINT_SPLIT_ITEMS)), \
-                                                     dim3(POINT_SPLIT * 64), 0, stream, __VA_ARGS__, (uint32_t*)nullptr); \
-    else if (POINT_GRID_BLOCKS(n) > POINT_MAX_BLOCKS) { \
-      const hipError_t z_ = hipMemsetAsync(ws->tiles, 0, sizeof(uint32_t), stream); if (z_ != hipSuccess) return z_; \
-      hipLaunchKernelGGL((kernel<1>), dim3(POINT_MAX_BLOCKS), dim3(POINT_LANES(n)), 0, stream, __VA_ARGS__, ws->tiles); } \
-    else hipLaunchKernelGGL((kernel<1>), dim3(POINT_GRID_BLOCKS(n)), dim3(POINT_LANES(n)), 0, stream, __VA_ARGS__, (uint32_t*)nullptr); } while (0)
-#define EDK_FINISH_GRID(n) dim3((unsigned)((((n) + BLOCK - 1) / BLOCK + finish_k(n) - 1) / finish_k(n))), dim3(BLOCK), 0, stream
-
-hipError_t edk_genpub(uint8_t* pubs, const uint8_t* secs, size_t n, const uint32_t* comb,
-                      const edk_fixed_ws* ws, hipStream_t stream) {
+hipError_t edk_genpub(uint8_t* pubs, const uint8_t* secs, size_t n, const uint32_t* comb, const edk_fixed_ws* ws, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  EDK_POINT_LAUNCH(k_genpub_point, n, ws->acc, secs, n, comb);
-  hipLaunchKernelGGL(k_encode_finish, EDK_FINISH_GRID(n), pubs, ws->acc, n, (int)finish_k(n));
+  const finish_shape f = finish_shape_of(n);
+  if (const hipError_t e = launch_point(k_genpub_point<POINT_SPLIT>, k_genpub_point<1>, n, ws, stream, ws->acc, secs, n, comb); e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_encode_finish, dim3(f.grid), dim3(BLOCK), 0, stream, pubs, ws->acc, n, f.k);
   return hipGetLastError();
 }
 
-hipError_t edk_sign(uint8_t* sigs, const uint8_t* secs, const uint8_t* pubs, const uint8_t* msgs,
-                    const uint64_t* msg_off, const uint64_t* msg_end, size_t msg_len, size_t n, const uint32_t* comb,
-                    const edk_fixed_ws* ws, hipStream_t stream) {
+hipError_t edk_sign(uint8_t* sigs, const uint8_t* secs, const uint8_t* pubs, const uint8_t* msgs, const uint64_t* msg_off, const uint64_t* msg_end,
+                    size_t msg_len, size_t n, const uint32_t* comb, const edk_fixed_ws* ws, hipStream_t stream) {
   if (n == 0) return hipSuccess;
+  const finish_shape f = finish_shape_of(n);
   const uint32_t* perm = nullptr;                  // ragged messages: both kernels hash, both take their items in order of length
-  if (msg_off && n >= MSG_ORDER_MIN_N) {
-    const hipError_t e = msg_order(ws->perm, ws->lenbins, msg_off, msg_end, n, stream);
-    if (e != hipSuccess) return e;
-    perm = ws->perm;
-  }
-  EDK_POINT_LAUNCH(k_sign_point, n, ws->acc, ws->aux, secs, msgs, msg_off, msg_end, msg_len, n, comb, perm);
-  hipLaunchKernelGGL(k_sign_finish, EDK_FINISH_GRID(n), sigs, ws->acc, ws->aux, pubs, msgs, msg_off, msg_end, msg_len, n, (int)finish_k(n), perm);
+  if (const hipError_t e = msg_order(&perm, ws->perm, ws->lenbins, msg_off, msg_end, n, stream); e != hipSuccess) return e;
+  if (const hipError_t e = launch_point(k_sign_point<POINT_SPLIT>, k_sign_point<1>, n, ws, stream, ws->acc, ws->aux, secs, msgs, msg_off, msg_end, msg_len, n, comb, perm); e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_sign_finish, dim3(f.grid), dim3(BLOCK), 0, stream, sigs, ws->acc, ws->aux, pubs, msgs, msg_off, msg_end, msg_len, n, f.k, perm);
   return hipGetLastError();
 }
 
-hipError_t edk_x25519_base(uint8_t* out, const uint8_t* scalars, size_t n, const uint32_t* comb,
-                           const edk_fixed_ws* ws, hipStream_t stream) {
+hipError_t edk_x25519_base(uint8_t* out, const uint8_t* scalars, size_t n, const uint32_t* comb, const edk_fixed_ws* ws, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  EDK_POINT_LAUNCH(k_x25519_base_point, n, ws->acc, scalars, n, comb);
-  hipLaunchKernelGGL(k_x25519_base_finish, EDK_FINISH_GRID(n), out, ws->acc, n, (int)finish_k(n));
+  const finish_shape f = finish_shape_of(n);
+  if (const hipError_t e = launch_point(k_x25519_base_point<POINT_SPLIT>, k_x25519_base_point<1>, n, ws, stream, ws->acc, scalars, n, comb); e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_x25519_base_finish, dim3(f.grid), dim3(BLOCK), 0, stream, out, ws->acc, n, f.k);
   return hipGetLastError();
 }
 
 hipError_t edk_pk_to_x(uint8_t* out, const uint8_t* in, size_t n, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_pk_to_x, EDK_GRID(n), out, in, n);
+  hipLaunchKernelGGL(k_pk_to_x, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, out, in, n);
   return hipGetLastError();
 }
 
 hipError_t edk_sk_to_x(uint8_t* out, const uint8_t* in, size_t n, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_sk_to_x, EDK_GRID(n), out, in, n);
+  hipLaunchKernelGGL(k_sk_to_x, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, out, in, n);
   return hipGetLastError();
 }
 

@@ -370,8 +370,10 @@ def test_verify_records(engine, oracle, stride, sig_off, pub_off, msg_off, mlen)
 
 
 def test_route_boundaries_agree(engine, oracle):
-    """the same items decided by the four-lane kernels (pass of 2^14 items) and by the one-lane kernels
-    (pass of 2^14 + 1 items) get the same verdicts, equal to the oracle's; keys on and off the curve"""
+    """the same items as a pass of 2^14 items and as one of 2^14 + 1 get the same verdicts, equal to the oracle's; keys on and
+    off the curve.  (2^14 is the boundary between four lanes and one lane per item of the FULL-LENGTH route only - algo 1 and
+    reject mode; the default route takes both passes through the same half-length four-lane kernels, and its own boundaries
+    are those of test_small_route_edges_agree_with_the_oracle below and of tests/test_gpu_fuzz.py)"""
     n = (1 << 14) + 1
     rng = np.random.default_rng(99)
     sk = rng.integers(0, 256, (n, 32), dtype=np.uint8)
@@ -384,6 +386,76 @@ def test_route_boundaries_agree(engine, oracle):
     big = engine.ed25519_verify_batch(dev(sig), dev(pk), dev(msg), msg_len=32).cpu().numpy()
     small = engine.ed25519_verify_batch(dev(sig[:-1]), dev(pk[:-1]), dev(msg[:-1]), msg_len=32).cpu().numpy()
     assert np.array_equal(big, want) and np.array_equal(small, want[:-1]) and 0 < want.sum() < n
+
+
+@pytest.fixture(scope="module")
+def route_edge_items(engine, oracle):
+    """2^18 items signed on the device, one signature in five corrupt and one key in nine random bytes (half of those are no
+    curve points), with the oracle's verdicts - computed once: a pass of n items takes the first n"""
+    n = 1 << 18
+    rng = np.random.default_rng(2718)
+    sk = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    msg = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    pk = engine.ed25519_genpub_batch(dev(sk))
+    sig = engine.ed25519_sign_batch(dev(sk), pk, dev(msg)).cpu().numpy()
+    pk = pk.cpu().numpy()
+    sig[::5, 40] ^= 8
+    pk[2::9] = rng.integers(0, 256, (len(pk[2::9]), 32), dtype=np.uint8)
+    return sig, pk, msg, oracle.verify_batch(sig, pk, msg, 32)
+
+
+@pytest.mark.parametrize("algo,n", [(0, 256), (0, 257), (0, 2048), (0, 2049), (0, 24576), (0, 24577), (1, 16384), (1, 16385),
+                                    (3, 262144)])
+def test_small_route_edges_agree_with_the_oracle(engine, route_edge_items, algo, n):
+    """both sides of every boundary below 2^18 items of the table in csrc/kernels.hip: verify_route_of - the default route's
+    256 | 257 (pairs up to 2^134 | 2^138), 2048 | 2049 (window sums | the four-lane half-length evaluation), 24 576 | 24 577
+    (four lanes | the mid-size arrangement); the full-length route's 2^14 | 2^14 + 1 (four lanes | one); and algo 3 at 2^18
+    items, where the mid-size arrangement ends and the pass takes the full-length route: every verdict as the oracle's"""
+    sig, pk, msg, want = (a[:n] for a in route_edge_items)
+    assert 0 < want.sum() < n
+    engine.set_verify_algo(algo)
+    try:
+        got = engine.ed25519_verify_batch(dev(sig), dev(pk), dev(msg), msg_len=32).cpu().numpy()
+    finally:
+        engine.set_verify_algo(0)
+    assert np.array_equal(got, want)
+
+
+@pytest.fixture(scope="module")
+def fixed_base_in_small_passes(engine):
+    """2^18 + 1 secret keys, 32-byte messages and X25519 scalars, and what the three fixed-base operations give for them in
+    device passes of 4096 items (four lanes per item, one block per 64 items) - computed once: a pass of n items takes the first n"""
+    import torch
+    n, step = (1 << 18) + 1, 4096
+    rng = np.random.default_rng(3141)
+    sk, msg, sc = (rng.integers(0, 256, (n, 32), dtype=np.uint8) for _ in range(3))
+    d_sk, d_msg, d_sc = dev(sk), dev(msg), dev(sc)
+    cuts = [slice(at, min(at + step, n)) for at in range(0, n, step)]
+    pk = torch.cat([engine.ed25519_genpub_batch(d_sk[c]) for c in cuts])
+    sig = torch.cat([engine.ed25519_sign_batch(d_sk[c], pk[c], d_msg[c]) for c in cuts])
+    xb = torch.cat([engine.x25519_base_batch(d_sc[c]) for c in cuts])
+    return sk, msg, sc, pk.cpu().numpy(), sig.cpu().numpy(), xb.cpu().numpy()
+
+
+@pytest.mark.parametrize("n", [16384, 16385, 32769, 65537, 131072, 131073, 262145])
+def test_fixed_base_launch_shapes(engine, oracle, fixed_base_in_small_passes, n):
+    """ed25519_genpub_batch, ed25519_sign_batch and x25519_base_batch as ONE device pass of n items, on both sides of every
+    change of the launch shape (csrc/kernels.hip: point_shape_of, finish_shape_of): 2^14 | 2^14 + 1 four lanes per item | one, in
+    blocks of 128 lanes; 2^15 + 1 blocks of 256; 2^16 + 1 blocks of 512 and two items per lane in the finish kernels; 2^17 |
+    2^17 + 1 a block per tile | persistent blocks that draw their tiles, and four items per lane; 2^18 + 1 eight.  Every byte as
+    in passes of 4096 items, and the first and last 256 items as the oracle's"""
+    sk, msg, sc, pk_small, sig_small, xb_small = (a[:n] for a in fixed_base_in_small_passes)
+    pk = engine.ed25519_genpub_batch(dev(sk))
+    sig = engine.ed25519_sign_batch(dev(sk), pk, dev(msg)).cpu().numpy()
+    pk = pk.cpu().numpy()
+    xb = engine.x25519_base_batch(dev(sc)).cpu().numpy()
+    assert np.array_equal(pk, pk_small) and np.array_equal(sig, sig_small) and np.array_equal(xb, xb_small)
+    for ends in (slice(0, 256), slice(n - 256, n)):
+        e_sk, e_msg = np.ascontiguousarray(sk[ends]), np.ascontiguousarray(msg[ends])
+        e_pk = oracle.genpub_batch(e_sk)
+        assert np.array_equal(pk[ends], e_pk)
+        assert np.array_equal(sig[ends], oracle.sign_batch(e_sk, e_pk, e_msg, 32))
+        assert [bytes(r) for r in xb[ends]] == [oracle.x25519_base(bytes(s)) for s in sc[ends]]
 
 
 def test_unaligned_device_buffers(engine, oracle):
