@@ -139,8 +139,8 @@ static int fws_reserve(struct vslot *v, size_t items, hipStream_t st)
     TRY(hipMemsetAsync(v->fws.aux, 0, fws_aux_bytes(cap), st));
     TRY(hipMalloc((void **)&v->fws.perm, cap * sizeof(uint32_t)));
     TRY(hipMalloc((void **)&v->fws.lenbins, 2 * EDK_LEN_BINS * sizeof(uint32_t)));
-    TRY(hipMalloc((void **)&v->fws.tiles, 256));
-    TRY(hipMemsetAsync(v->fws.tiles, 0, 256, st));
+    TRY(hipMalloc((void **)&v->fws.tiles, EDK_TILES_BYTES));
+    TRY(hipMemsetAsync(v->fws.tiles, 0, EDK_TILES_BYTES, st));
     v->fws.capacity = cap;
 out:
     if (rc) fws_release(v);
@@ -156,18 +156,18 @@ static int ws_reserve(struct vslot *v, size_t items)
     /* the old buffers may still be in use by enqueued kernels */
     TRY(hipEventSynchronize(v->free));
     ws_release(v);
-    TRY(hipMalloc((void **)&v->ws.digits, cap * 16 * sizeof(uint32_t)));
+    TRY(hipMalloc((void **)&v->ws.digits, cap * VERIFY_DIGIT_WORDS * sizeof(uint32_t)));
     TRY(hipMalloc((void **)&v->ws.table, cap / VERIFY_TILE * (size_t)VERIFY_TABLE_WORDS_PER_TILE * sizeof(uint32_t)));
     TRY(hipMalloc((void **)&v->ws.acc, cap * ACC_WORDS * sizeof(uint32_t)));
-    TRY(hipMalloc((void **)&v->ws.hdigits, cap * EDK_HALF_DIGIT_WORDS * sizeof(uint32_t)));
+    TRY(hipMalloc((void **)&v->ws.hdigits, cap * HALF_DIGIT_WORDS * sizeof(uint32_t)));
     TRY(hipMalloc((void **)&v->ws.rtable, cap / VERIFY_TILE * (size_t)VERIFY_TABLE_WORDS_PER_TILE * sizeof(uint32_t)));
     TRY(hipMalloc((void **)&v->ws.flags, cap));
     TRY(hipMalloc((void **)&v->ws.offlist, cap * sizeof(uint32_t)));
     TRY(hipMalloc((void **)&v->ws.onlist, cap * sizeof(uint32_t)));
     TRY(hipMalloc((void **)&v->ws.perm, cap * sizeof(uint32_t)));
     TRY(hipMalloc((void **)&v->ws.lenbins, 2 * EDK_LEN_BINS * sizeof(uint32_t)));
-    TRY(hipMalloc((void **)&v->ws.offcount, 256));
-    TRY(hipMemset(v->ws.offcount, 0, 256));
+    TRY(hipMalloc((void **)&v->ws.offcount, EDK_OFFCOUNT_BYTES));
+    TRY(hipMemset(v->ws.offcount, 0, EDK_OFFCOUNT_BYTES));
     TRY(hipStreamSynchronize(NULL));      /* the pass's stream does not wait for the null stream */
     TRY(hipMalloc((void **)&v->ws.exact_pad, EDK_EXACT_PAD_BYTES));
     TRY(hipMalloc((void **)&v->ws.sums, EDK_SUMS_BYTES));

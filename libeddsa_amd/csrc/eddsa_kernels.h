@@ -5,33 +5,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#ifndef TABLE_BASE16_ENTRIES      /* also defined, identically, by lanes.h for the device side */
-#define TABLE_BASE16_ENTRIES 32769 /* k*B, k = 0..32768; the table holds twice that: k*2^128*B follows */
-#define COMB_W 6                  /* signed window width of the fixed-base comb (the reference's is 4, ed.c:397-430) */
-#define COMB_HALF (1 << (COMB_W - 1))          /* digits d in [-COMB_HALF, COMB_HALF - 1] */
-#define COMB_DIGITS (COMB_W == 4 ? 64 : COMB_W == 5 ? 52 : 44)   /* digits of x + offset: 64 x 4, 52 x 5 or 44 x 6 bits */
-#define COMB_ROWS (COMB_DIGITS / 2)            /* even digits and odd digits share a row */
-#define TABLE_COMB_ENTRIES (COMB_ROWS * COMB_HALF) /* comb[i][k] = (k+1) * 2^(2*COMB_W*i) * B, k < COMB_HALF */
-#define TABLE_ENTRY_WORDS 32      /* 3 x 10 limbs + 2 padding words */
-#define VERIFY_TABLE_ENTRIES 9    /* 0..8 times -A, cached form */
-#define VERIFY_ENTRY_WORDS 32     /* ymx | ypx | t2d | z2, 255 bits packed into eight words each: one 128-byte line */
-#define COMB_IMG_ENTRIES COMB_HALF       /* LDS image of a comb row: entry m - 1 = m * 2^(2*COMB_W*i) * B, m = 1..COMB_HALF */
-#define COMB_IMG_ENTRY_WORDS 36
-#define COMB_IMG_WORDS (COMB_ROWS * COMB_IMG_ENTRIES * COMB_IMG_ENTRY_WORDS)
-#endif
-#define VERIFY_TABLE_WORDS_PER_TILE (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS * 256)
-#define VERIFY_TILE 256            /* items per tile = threads per block */
-#define EDK_HALF_DIGIT_WORDS 28     /* = HALF_DIGIT_WORDS of lanes.h */
+#include "edk_layout.h"             /* the tables' sizes, the per-item slots of the workspaces, the words of offcount */
+
 #define EDK_LEN_BINS 2048           /* bins of the per-pass counting sort of ragged messages by length (kernels.hip: k_len_*) */
-#define EDK_REFUSED_WORD 8
-#define EDK_ONLIST_WORD 1           /* word of edk_verify_ws.offcount: the length of onlist */
-#define EDK_EXACT_UNIT_WORD 2        /* word of edk_verify_ws.offcount: the next unit of work of k_verify_exact_lane_chain */
-#define EDK_STALL_WORD 3             /* ... set by a wave of that kernel that gave up waiting for a hand-off: the others then leave too */
-#define EDK_PASS_WORDS 4             /* words 0..3 are zeroed by every pass */
-#define EDK_WITHHOLD_WORD 9          /* test hook (eddsa_amd_debug_withhold_handoff): tile + 1 whose first hand-off is never published; 0: none */
 #define EDK_EXACT_PATIENCE (1u << 21) /* polls (a microsecond or two each) a wave of k_verify_exact_lane_chain spends on one hand-off */
-#define EDK_BENTRY_WORD 32          /* words 32..63 of edk_verify_ws.offcount: the base point as a packed cached entry (lanes.h: exact_bentry_store) */
-#define ACC_WORDS 40               /* point workspace per item: X, Y, Z and one slot for the finish kernels' prefix products */
 
 #ifdef __cplusplus
 extern "C" {
@@ -48,21 +25,19 @@ hipError_t edk_init_tables(uint32_t* base16, uint32_t* comb, uint32_t* comb_img,
 /* verify workspace for up to `capacity` items (a multiple of VERIFY_TILE), all in HBM */
 typedef struct edk_verify_ws {
   size_t capacity;
-  uint32_t* digits;   /* capacity * 16 words */
+  uint32_t* digits;   /* capacity * VERIFY_DIGIT_WORDS words */
   uint32_t* table;    /* capacity / 256 tiles * VERIFY_TABLE_WORDS_PER_TILE words */
   uint32_t* acc;      /* capacity * ACC_WORDS words */
-  uint32_t* hdigits;  /* capacity * EDK_HALF_DIGIT_WORDS words: the half-length scalars (kernels.hip k_verify_halve) */
+  uint32_t* hdigits;  /* capacity * HALF_DIGIT_WORDS words: the half-length scalars (kernels.hip k_verify_halve) */
   uint32_t* rtable;   /* like table: 0..8 times -R' */
-  uint8_t* flags;     /* capacity bytes */
+  uint8_t* flags;     /* capacity bytes: kernel_io.h, VERIFY_WINDOWED ... */
   uint32_t* offlist;  /* capacity words: the exact path's work list (keys off the curve; large passes: items without a short pair) */
   uint32_t* onlist;   /* capacity words: the items the windowed evaluation decides (every other item); the half-length route's
                          k_verify_halve / k_verify_main_half run over this list */
   uint32_t* perm;     /* capacity words: ragged passes: the items in order of message length (kernels.hip: msg_order) */
   uint32_t* lenbins;  /* 2 * EDK_LEN_BINS words: that sort's counts and cursors */
-  uint32_t* offcount; /* 64 words, zeroed at allocation: [0] the length of offlist, [EDK_ONLIST_WORD] the length of onlist, [EDK_EXACT_UNIT_WORD],
-                         [EDK_STALL_WORD] (all four zeroed by every pass), [EDK_REFUSED_WORD] half-length pairs that the exact check of lanes.h:
-                         verify_half_scalars_lane refused since allocation (diagnostic), [EDK_WITHHOLD_WORD] (test hook), [EDK_BENTRY_WORD..] the
-                         shared entry of the one-lane exact path */
+  uint32_t* offcount; /* EDK_OFFCOUNT_WORDS words, zeroed at allocation: the lengths of the two lists, the one-lane exact path's counters and
+                         shared entry, hooks (edk_layout.h: EDK_*_WORD) */
   uint32_t* exact_pad;/* EDK_EXACT_PAD_BYTES: scratchpad of k_verify_exact_quad: the addends of the items in flight, one slot per quad */
   uint32_t* sums;     /* EDK_SUMS_BYTES: the windows' sums of a small pass */
   uint32_t* status;   /* one word of page-locked host memory shared by the engine's workspaces (or NULL): a kernel that had to give up
@@ -116,7 +91,7 @@ typedef struct edk_fixed_ws {
   uint32_t* aux;      /* capacity * 16 words: sign's secret scalars a, r between its two kernels (zeroed after use) */
   uint32_t* perm;     /* capacity words, and */
   uint32_t* lenbins;  /* 2 * EDK_LEN_BINS words: sign's ragged messages in order of length, as in edk_verify_ws */
-  uint32_t* tiles;    /* 64 words; [0] the next 64-item tile a wave of a persistent point kernel takes (zeroed by the launcher before
+  uint32_t* tiles;    /* EDK_TILES_WORDS words; [0] the next 64-item tile a wave of a persistent point kernel takes (zeroed by the launcher before
                          every such launch): kernels.hip, point_tile */
 } edk_fixed_ws;
 

@@ -25,7 +25,7 @@
 
 namespace ed {
 
-constexpr int BLOCK = 256;
+constexpr int BLOCK = VERIFY_TILE;         // a block is a tile of the workspaces (kernel_io.h)
 
 // one verify item: R, S, A as words and the message span (packed arrays or fixed-size records)
 ED_DEV void verify_item(uint32_t rw[8], uint32_t sw[8], uint32_t aw[8], const uint8_t*& m, size_t& mlen,
@@ -65,9 +65,9 @@ k_x25519_ladder(uint32_t* accout, const uint8_t* scalars, const uint8_t* points,
   fe x2, z2;
   x25519_ladder_lane(x2, z2, s, pt);
   if (i >= n) return;                            // an idle lane must not leave a copy of the last item's secret
-  uint32_t* o = accout + (size_t)blockIdx.x * (ACC_WORDS * BLOCK) + threadIdx.x;
+  uint32_t* o = acc_column(accout, blockIdx.x, threadIdx.x);
 #pragma unroll
-  for (int j = 0; j < 10; j++) { o[j * BLOCK] = x2.v[j]; o[(20 + j) * BLOCK] = z2.v[j]; }
+  for (int j = 0; j < 10; j++) { o[acc_at(ACC_X, j)] = x2.v[j]; o[acc_at(ACC_Z, j)] = z2.v[j]; }
 }
 
 // small passes: four lanes per item (quad_lanes.h: x25519_ladder_quad); writes the same workspace slots
@@ -83,9 +83,7 @@ k_x25519_ladder_quad(uint32_t* accout, const uint8_t* scalars, const uint8_t* po
   fe r;
   x25519_ladder_quad(r, s, pt, q);
   if (q > 1) return;                             // lane 0: x2 -> the X slot, lane 1: z2 -> the Z slot
-  uint32_t* o = accout + (i / BLOCK) * (ACC_WORDS * BLOCK) + (i % BLOCK) + (q == 0 ? 0 : 20) * BLOCK;
-#pragma unroll
-  for (int j = 0; j < 10; j++) o[j * BLOCK] = r.v[j];
+  acc_put(acc_column(accout, i / BLOCK, i % BLOCK), q == 0 ? ACC_X : ACC_Z, r);
 }
 
 __global__ void __launch_bounds__(64) k_init_tables(uint32_t* base16, uint32_t* comb) {
@@ -175,12 +173,12 @@ __global__ void __launch_bounds__(BLOCK) k_len_place(uint32_t* perm, uint32_t* b
 //   k_verify_exact_quad (side stream, beside main) the reference's own chain for the items whose key is not a curve
 //                     point; owns their verdict bytes
 // Workspace (HBM; tile = 256 items):
-//   digits [item][16]                  t + 0x88.., S + 0x80.. as little-endian words
-//   table  [item][entry 9][word 32]    1152 contiguous bytes per item; an entry = ymx | ypx | t2d | z2 packed into 255 bits each
-//                                      (fe_pack), one 128-byte line
-//   acc    [tile][word 30][lane 256]   X, Y, Z of the result
-//   flags  [item]                      bit 0: A decoded to a curve point; bit 1: Z usable (set by finish)
+//   digits [item]                      t + 0x88.., S + 0x80.. as little-endian words
+//   table  [item][entry][word]         an entry = ymx | ypx | t2d | z2 packed into 255 bits each (fe_pack), one 128-byte line
+//   acc    [tile][word][lane]          X, Y, Z of the result
+//   flags  [item]                      VERIFY_WINDOWED: A decoded to a curve point; VERIFY_Z_USABLE (set by finish)
 //   offlist[..], offcount              items whose A is off the curve, for k_verify_exact_quad
+// (the sizes: edk_layout.h; the slots' accessors and the flag bits: kernel_io.h)
 // ---------------------------------------------------------------------------------------------
 
 // DIGEST: the caller supplied SHA-512(R || A || M) (ed25519_verify_digests*): the item's 64 bytes lie in the message slot of
@@ -208,23 +206,23 @@ k_verify_prepare(edk_verify_items src, size_t n, uint32_t* digits,
     msg_span(m, mlen, src.msgs, src.msg_off, src.msg_end, src.msg_len, src.msg_stride, item);
     verify_hash_lane(tw, rw, aw, m, mlen);
   }
-  uint4* d = reinterpret_cast<uint4*>(digits + 16 * i);
-  d[0] = make_uint4(tw[0], tw[1], tw[2], tw[3]); d[1] = make_uint4(tw[4], tw[5], tw[6], tw[7]);
+  uint32_t* d = digits + digit_slot(i);
+  store8(d, tw);
   load32(sw, src.sigs + 32, item, src.sig_stride);       // S is fetched only now: nothing to hold across the hash
   verify_s_lane(sw);
-  d[2] = make_uint4(sw[0], sw[1], sw[2], sw[3]); d[3] = make_uint4(sw[4], sw[5], sw[6], sw[7]);
-  const bool oncurve = verify_table_lane(table + i * (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS), aw);
+  store8(d + 8, sw);
+  const bool oncurve = verify_table_lane(table + table_slot(i), aw);
   // keys that are not curve points go to the exact (reference-order) kernels: append to their work
   // list (all_exact, a self-check mode: every item does, and the windowed result is not used)
   const bool windowed = oncurve && !all_exact;
-  flags[i] = (uint8_t)windowed;
+  flags[i] = (uint8_t)(windowed ? VERIFY_WINDOWED : 0);
   // Two work lists: the items the windowed evaluation decides (the half-length route's k_verify_halve and
   // k_verify_main_half run over THIS list, not over the pass: a caller who sends nothing but garbage keys then pays for
   // the exact path only, not for a windowed evaluation whose result is discarded on top), and the exact path's.
   const bool live = g < n;
   const uint32_t on_slot = wave_append(offcount + EDK_ONLIST_WORD, live && windowed);
   if (live && windowed) onlist[on_slot] = (uint32_t)i;
-  const uint32_t off_slot = wave_append(offcount, live && !windowed);
+  const uint32_t off_slot = wave_append(offcount + EDK_OFFLIST_WORD, live && !windowed);
   if (live && !windowed) offlist[off_slot] = (uint32_t)i;
 }
 
@@ -285,7 +283,7 @@ k_verify_exact_quad(uint8_t* ok, const uint8_t* sigs, size_t sig_stride, const u
   const size_t i = offlist[g];
   uint32_t* item = pad + g * QUAD_ITEM_WORDS;
   uint32_t* dig = lds_dig + quad * QUAD_DIGIT_WORDS;
-  verify_exact_setup_quad(digits + 16 * i, table + i * (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS), base16 + TABLE_ENTRY_WORDS, item, dig, q);
+  verify_exact_setup_quad(digits + digit_slot(i), table + table_slot(i), base16 + TABLE_ENTRY_WORDS, item, dig, q);
   __syncthreads();                               // one wave: orders the quad's stores (LDS digits, HBM addends) before the other lanes' loads
   uint32_t rw[8];
   load32(rw, sigs, i, sig_stride);
@@ -313,6 +311,7 @@ k_verify_exact_quad(uint8_t* ok, const uint8_t* sigs, size_t sig_stride, const u
 constexpr uint32_t EXACT_CHAIN_COST = 594;       // executed instructions per item of k_verify_exact_lane_chain, thousands
 constexpr unsigned EXACT_LANE_BLOCKS = 512;      // two resident blocks per CU
 constexpr int EXACT_DIGITS_AT = 0, EXACT_STATE_AT = 64;   // words of the item's rtable slot: the digit string; the accumulator between stretches (lines of its own)
+static_assert(EXACT_STATE_AT + EXACT_STATE_WORDS + 2 <= VERIFY_ITEM_TABLE_WORDS, "the accumulator and the walk (lanes.h: exact_walk_store) fit the slot");
 __global__ void __launch_bounds__(BLOCK, 2)
 k_verify_exact_lane_setup(const uint32_t* digits, uint32_t* table, uint32_t* rtable, const uint32_t* offlist, uint32_t* offcount,
                           const uint32_t* base16, uint32_t* tile_done, uint32_t min_listed) {
@@ -322,8 +321,7 @@ k_verify_exact_lane_setup(const uint32_t* digits, uint32_t* table, uint32_t* rta
   for (size_t g = (size_t)blockIdx.x * BLOCK + threadIdx.x; g < listed; g += (size_t)gridDim.x * BLOCK) {
     if ((g & 63) == 0) tile_done[g >> 6] = 0;
     const size_t i = offlist[g];
-    verify_exact_setup_table_lane(table + i * (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS),
-                                  rtable + i * (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS) + EXACT_DIGITS_AT, 1, digits + 16 * i, base16 + TABLE_ENTRY_WORDS);
+    verify_exact_setup_table_lane(table + table_slot(i), rtable + table_slot(i) + EXACT_DIGITS_AT, 1, digits + digit_slot(i), base16 + TABLE_ENTRY_WORDS);
   }
 }
 
@@ -395,21 +393,20 @@ k_verify_exact_lane_chain(uint8_t* ok, const uint8_t* sigs, size_t sig_stride, c
     const size_t ga = (size_t)tile * 128 + lane, gb = ga + 64;
     const bool live_a = ga < listed, live_b = gb < listed;
     const uint32_t ia = offlist[live_a ? ga : listed - 1], ib = offlist[live_b ? gb : listed - 1];   // (an idle half walks nothing and stores nothing)
-    constexpr uint32_t SLOT = VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS;
     ge ra, rb;
     exact_walk wa, wb;
     if (seg == 0) {
       ge_neutral(ra); ge_neutral(rb);
-      wa = exact_walk_start(rtable + (size_t)ia * SLOT + EXACT_DIGITS_AT, 1, live_a);
-      wb = exact_walk_start(rtable + (size_t)ib * SLOT + EXACT_DIGITS_AT, 1, live_b);
+      wa = exact_walk_start(rtable + table_slot(ia) + EXACT_DIGITS_AT, 1, live_a);
+      wb = exact_walk_start(rtable + table_slot(ib) + EXACT_DIGITS_AT, 1, live_b);
     } else {
-      exact_walk_load(ra, wa, rtable + (size_t)ia * SLOT + EXACT_STATE_AT);
-      exact_walk_load(rb, wb, rtable + (size_t)ib * SLOT + EXACT_STATE_AT);
+      exact_walk_load(ra, wa, rtable + table_slot(ia) + EXACT_STATE_AT);
+      exact_walk_load(rb, wb, rtable + table_slot(ib) + EXACT_STATE_AT);
       if (!live_a) { wa.i = -1; wa.pend = false; }
       if (!live_b) { wb.i = -1; wb.pend = false; }
     }
     const bool last = seg == (unsigned)EXACT_SEGS - 1;
-    exact_pair_iterations(ra, wa, rb, wb, table, rtable + EXACT_DIGITS_AT, SLOT, ia, ib, offcount + EDK_BENTRY_WORD, last ? -1 : EXACT_PAIR_ITERS);
+    exact_pair_iterations(ra, wa, rb, wb, table, rtable + EXACT_DIGITS_AT, VERIFY_ITEM_TABLE_WORDS, ia, ib, offcount + EDK_BENTRY_WORD, last ? -1 : EXACT_PAIR_ITERS);
     if (last) {
       uint32_t rwa[8], rwb[8];
       load32(rwa, sigs, ia, sig_stride);
@@ -419,8 +416,8 @@ k_verify_exact_lane_chain(uint8_t* ok, const uint8_t* sigs, size_t sig_stride, c
       if (live_a) ok[ia] = (uint8_t)same_a;
       if (live_b) ok[ib] = (uint8_t)same_b;
     } else {
-      if (live_a) exact_walk_store(rtable + (size_t)ia * SLOT + EXACT_STATE_AT, ra, wa);
-      if (live_b) exact_walk_store(rtable + (size_t)ib * SLOT + EXACT_STATE_AT, rb, wb);
+      if (live_a) exact_walk_store(rtable + table_slot(ia) + EXACT_STATE_AT, ra, wa);
+      if (live_b) exact_walk_store(rtable + table_slot(ib) + EXACT_STATE_AT, rb, wb);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");         // every lane's accumulators are out before the count says so
       // (test hook: the first hand-off of tile EDK_WITHHOLD_WORD - 1 is never published; the word is 0 unless a test set it)
       if (lane == 0 && !(seg == 0 && offcount[EDK_WITHHOLD_WORD] == tile + 1u))
@@ -434,12 +431,8 @@ k_verify_main(const uint32_t* digits, const uint32_t* table, const uint32_t* bas
   const size_t tile = blockIdx.x;
   const size_t i = tile * BLOCK + threadIdx.x;   // < workspace capacity
   ge acc;
-  verify_main_lane(acc, digits + 16 * i, table + i * (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS), base16);
-  uint32_t* o = accout + tile * (ACC_WORDS * BLOCK) + threadIdx.x;
-#pragma unroll
-  for (int j = 0; j < 10; j++) {
-    o[j * BLOCK] = acc.X.v[j]; o[(10 + j) * BLOCK] = acc.Y.v[j]; o[(20 + j) * BLOCK] = acc.Z.v[j];
-  }
+  verify_main_lane(acc, digits + digit_slot(i), table + table_slot(i), base16);
+  acc_put_xyz(acc_column(accout, tile, threadIdx.x), acc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -450,8 +443,8 @@ k_verify_main(const uint32_t* digits, const uint32_t* table, const uint32_t* bas
 //   k_verify_main_half  132 doublings + 68 + 16 additions, neutral-element test, verdict byte
 // No finish kernel: "is the neutral element" needs no inversion.  Items the pair search gives up on join the
 // off-curve keys on the exact path's work list (so the list is complete only after k_verify_halve).
-// Workspace beside the one above: hdigits [item][HALF_DIGIT_WORDS], rtable [item][entry 9][word 32] (the same packed form);
-// flags bit 0: this path owns the verdict, bit 2: R is a canonical encoding of a curve point.
+// Workspace beside the one above: hdigits [item], rtable like table; flags: VERIFY_WINDOWED: this path owns the verdict,
+// VERIFY_R_CANONICAL: R is a canonical encoding of a curve point (kernel_io.h).
 // ---------------------------------------------------------------------------------------------
 template <int BITS>
 __global__ void __launch_bounds__(BLOCK, 2)
@@ -464,28 +457,22 @@ k_verify_halve(const uint8_t* sigs, size_t sig_stride, const uint32_t* digits, u
   const size_t i = onlist[slot], item = i;
   const uint8_t fl = flags[i];
   uint32_t tdig[8], sdig[8], hd[HALF_DIGIT_WORDS];
-  {
-    const uint4* d = reinterpret_cast<const uint4*>(digits + 16 * i);
-    const uint4 a = d[0], b = d[1], c = d[2], e = d[3];
-    tdig[0] = a.x; tdig[1] = a.y; tdig[2] = a.z; tdig[3] = a.w; tdig[4] = b.x; tdig[5] = b.y; tdig[6] = b.z; tdig[7] = b.w;
-    sdig[0] = c.x; sdig[1] = c.y; sdig[2] = c.z; sdig[3] = c.w; sdig[4] = e.x; sdig[5] = e.y; sdig[6] = e.z; sdig[7] = e.w;
-  }
+  load8(tdig, digits + digit_slot(i));
+  load8(sdig, digits + digit_slot(i) + 8);
   verify_half_scalars_lane<BITS>(hd, tdig, sdig);
-  if ((hd[24] & 4u) != 0) atomicAdd(offcount + EDK_REFUSED_WORD, 1u);   // a pair the exact check refused: never seen (diagnostic)
-  uint4* o = reinterpret_cast<uint4*>(hdigits + HALF_DIGIT_WORDS * i);
-#pragma unroll
-  for (int q = 0; q < HALF_DIGIT_WORDS / 4; q++) o[q] = make_uint4(hd[4 * q], hd[4 * q + 1], hd[4 * q + 2], hd[4 * q + 3]);
+  if ((hd[HALF_STATUS_WORD] & HALF_PAIR_REFUSED) != 0) atomicAdd(offcount + EDK_REFUSED_WORD, 1u);   // never seen (diagnostic)
+  hdigits_store(hdigits, i, hd);
   uint32_t rw[8];
   load32(rw, sigs, item, sig_stride);
-  const bool rvalid = verify_half_point_lane(rtable + i * (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS), rw);
+  const bool rvalid = verify_half_point_lane(rtable + table_slot(i), rw);
   // An item without a short pair ("long", lanes.h) joins the exact path's work list here: k_verify_main_half's grid
   // has no slack, and both alternatives measured slower at 2^20 items - the long loop inside that kernel for the
   // waves that contain such an item (one in 180: 7.2 -> 7.8 ms) and a separate four-lane kernel for them beside it
   // (7.4 -> 7.65 ms).  Small passes, whose waves have the chip to themselves, do run the long loop in place
   // (k_verify_main_half_quad).
-  const bool mine = (fl & 1) != 0 && (hd[24] & 2u) == 0;
-  flags[i] = (uint8_t)((mine ? 1 : 0) | (rvalid ? 4 : 0));
-  if ((fl & 1) != 0 && !mine) offlist[atomicAdd(offcount, 1u)] = (uint32_t)i;
+  const bool mine = (fl & VERIFY_WINDOWED) != 0 && (hd[HALF_STATUS_WORD] & HALF_LONG) == 0;
+  flags[i] = (uint8_t)((mine ? VERIFY_WINDOWED : 0) | (rvalid ? VERIFY_R_CANONICAL : 0));
+  if ((fl & VERIFY_WINDOWED) != 0 && !mine) offlist[atomicAdd(offcount + EDK_OFFLIST_WORD, 1u)] = (uint32_t)i;
 }
 
 // dynamic LDS the main kernels are launched with: what keeps a third block off the CU, and where k_verify_main_half keeps its digit words
@@ -503,7 +490,7 @@ k_verify_main_half(uint8_t* ok, const uint32_t* hdigits, const uint32_t* table, 
   const size_t slot = (size_t)blockIdx.x * MAIN_HALF_BLOCK + threadIdx.x;
   if (slot >= (size_t)offcount[EDK_ONLIST_WORD]) return;
   const size_t i = onlist[slot];
-  const uint32_t* hd = hdigits + HALF_DIGIT_WORDS * i;
+  const uint32_t* hd = hdigits + hdigit_slot(i);
   // The lane's digit words go to LDS once (word w of lane t at [w][t]: no bank conflicts).  Read from memory window by
   // window they were the hottest lines of L2 - one per resident item, 16 MB of its 32 - and L2 is what the table lines
   // need: its hits are worth 12 % to this kernel (profiles/r04_main_half_loads_ab.txt), and with the digits out of it the
@@ -519,20 +506,18 @@ k_verify_main_half(uint8_t* ok, const uint32_t* hdigits, const uint32_t* table, 
     }
   }
   const uint32_t* hl = digit_words + threadIdx.x;
-  const bool long_loop = WITH_LONG && __any((hl[24 * MAIN_HALF_BLOCK] & 2u) != 0);
+  const bool long_loop = WITH_LONG && __any((hl[HALF_STATUS_WORD * MAIN_HALF_BLOCK] & HALF_LONG) != 0);
   // a zero digit reads item 0's entry 0 - the neutral element, like every item's own: one line for the chip, not one per item
-  const bool neutral = verify_half_main_lane<WITH_LONG, WINDOWS>(hl, table + i * (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS),
-                                             rtable + i * (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS), base16, long_loop, MAIN_HALF_BLOCK, table);
-  const uint8_t fl = flags[i];
-  if ((fl & 1) == 0) return;                     // k_verify_halve handed the item to the exact path, which owns its verdict
-  ok[i] = (uint8_t)(neutral && (fl & 4) != 0);
+  const bool neutral = verify_half_main_lane<WITH_LONG, WINDOWS>(hl, table + table_slot(i), rtable + table_slot(i), base16, long_loop, MAIN_HALF_BLOCK, table);
+  // (an item without VERIFY_WINDOWED was handed to the exact path by k_verify_halve; reject mode never comes here)
+  half_verdict_store(ok, i, flags[i], neutral, 1);
 }
 
 // ---------------------------------------------------------------------------------------------
 // "finish" kernels: everything that needs an inversion (ed_export ed.c:161, x25519.c:192) shares
 // ONE inversion between FINISH_K items per lane (Montgomery's trick: 254 S + 11 M once, plus three
 // multiplications per item).  Lane t of block b handles lane t of tiles b*K .. b*K+K-1 of the
-// lane-interleaved point workspace acc[tile][30][256], so every access stays coalesced.
+// lane-interleaved point workspace (kernel_io.h: acc_column), so every access stays coalesced.
 // A policy P supplies  den(k, z, good): the value to invert for item k (1 when there is nothing to
 // invert: item past the end, rejected key, or a zero denominator, which must not poison the shared
 // product) and  item(k, zinv, good): the rest of the work of item k.
@@ -545,64 +530,52 @@ constexpr int FINISH_K = 8;
 
 struct finish_pos {
   size_t tile, i;            // tile index and global item index of slot k for this lane
-  const uint32_t* acc;       // this lane's column of the tile: X at [j*BLOCK], Y at [(10+j)*BLOCK], Z at [(20+j)*BLOCK]
+  const uint32_t* acc;       // this lane's column of the tile (kernel_io.h: acc_column)
 };
 ED_DEV finish_pos finish_at(int k, const uint32_t* accin, int K) {
   finish_pos p;
   p.tile = (size_t)blockIdx.x * K + k;
   p.i = p.tile * BLOCK + threadIdx.x;
-  p.acc = accin + p.tile * (ACC_WORDS * BLOCK) + threadIdx.x;
+  p.acc = acc_column(accin, p.tile, threadIdx.x);
   return p;
-}
-ED_DEV void acc_load(fe& f, const uint32_t* acc, int coord) {
-#pragma unroll
-  for (int j = 0; j < 10; j++) f.v[j] = acc[(10 * coord + j) * BLOCK];
 }
 // i = the lane's global item slot (tile i / BLOCK, lane i % BLOCK), whatever the block size
 ED_DEV void acc_store(uint32_t* accout, size_t i, const ge& p) {
-  uint32_t* o = accout + (i / BLOCK) * (ACC_WORDS * BLOCK) + (i % BLOCK);
-#pragma unroll
-  for (int j = 0; j < 10; j++) {
-    o[j * BLOCK] = p.X.v[j]; o[(10 + j) * BLOCK] = p.Y.v[j]; o[(20 + j) * BLOCK] = p.Z.v[j];
-  }
+  acc_put_xyz(acc_column(accout, i / BLOCK, i % BLOCK), p);
 }
 
 // Phase A multiplies the eight denominators together, inverts once and unwinds.  Each denominator is
-// written to its Z slot by den(), each prefix product z0 ... zk to the fourth slot (W) of item k, and
+// written to its Z slot by den(), each prefix product z0 ... zk to the fourth slot (ACC_W) of item k, and
 // both are re-read during the unwinding: with the eight prefix products in registers beside the
 // inversion's temporaries every finish kernel needed more than 256 VGPRs and spilled 660 bytes per
 // lane.  The same lane writes and later reads these slots.  Phase B is an ordinary loop over the
 // items, so the (large) per-item code exists once.
 ED_DEV void slot_store(uint32_t* acc, int k, int coord, const fe& f, int K) {
-  uint32_t* o = acc + ((size_t)blockIdx.x * K + k) * (ACC_WORDS * BLOCK) + threadIdx.x;
-#pragma unroll
-  for (int j = 0; j < 10; j++) o[(10 * coord + j) * BLOCK] = f.v[j];
+  acc_put(acc_column(acc, (size_t)blockIdx.x * K + k, threadIdx.x), coord, f);
 }
 ED_DEV void slot_load(fe& f, const uint32_t* acc, int k, int coord, int K) {
-  const uint32_t* o = acc + ((size_t)blockIdx.x * K + k) * (ACC_WORDS * BLOCK) + threadIdx.x;
-#pragma unroll
-  for (int j = 0; j < 10; j++) f.v[j] = o[(10 * coord + j) * BLOCK];
+  acc_load(f, acc_column(acc, (size_t)blockIdx.x * K + k, threadIdx.x), coord);
 }
-ED_DEV void zinv_store(uint32_t* acc, int k, const fe& zi, int K) { slot_store(acc, k, 2, zi, K); }
+ED_DEV void zinv_store(uint32_t* acc, int k, const fe& zi, int K) { slot_store(acc, k, ACC_Z, zi, K); }
 
 template <class P>
 ED_DEV void finish_batch8(const P& pol, uint32_t* acc) {
   const int K = pol.K;                           // items per lane that share the inversion: FINISH_K, fewer in small passes
   fe z, p, u, zi;
   pol.den(0, p);
-  slot_store(acc, 0, 3, p, K);
+  slot_store(acc, 0, ACC_W, p, K);
 #pragma unroll 1
   for (int k = 1; k < K; k++) {
     pol.den(k, z);
     fe_mul(p, p, z);
-    slot_store(acc, k, 3, p, K);                 // z0 ... zk
+    slot_store(acc, k, ACC_W, p, K);             // z0 ... zk
   }
   fe_inv(u, p);                                  // u = 1 / (z0 ... z(K-1))
 #pragma unroll 1
   for (int k = K - 1; k >= 1; k--) {
-    slot_load(p, acc, k - 1, 3, K);
+    slot_load(p, acc, k - 1, ACC_W, K);
     fe_mul(zi, u, p);                            // 1 / zk
-    slot_load(z, acc, k, 2, K);
+    slot_load(z, acc, k, ACC_Z, K);
     fe_mul(u, u, z);                             // 1 / (z0 ... z(k-1))
     zinv_store(acc, k, zi, K);
   }
@@ -631,10 +604,10 @@ struct verify_finish_policy {
     fe_set(z, 1);
     bool good = false;
     if (p.i < n) {
-      acc_load(z, p.acc, 2);
+      acc_load(z, p.acc, ACC_Z);
       const uint8_t fl = flags[p.i];
-      good = (fl & 1) != 0 && !fe_iszero(z);
-      flags[p.i] = (uint8_t)((fl & 1) | (good ? 2 : 0));   // phase B reads it back
+      good = (fl & VERIFY_WINDOWED) != 0 && !fe_iszero(z);
+      flags[p.i] = (uint8_t)((fl & VERIFY_WINDOWED) | (good ? VERIFY_Z_USABLE : 0));   // phase B reads it back
     }
     den_commit(z, good, acc, k, K);
   }
@@ -642,15 +615,15 @@ struct verify_finish_policy {
     const finish_pos p = finish_at(k, acc, K);
     if (p.i >= n) return;
     fe x, y, zinv;
-    acc_load(x, p.acc, 0); acc_load(y, p.acc, 1); acc_load(zinv, p.acc, 2);
+    acc_load(x, p.acc, ACC_X); acc_load(y, p.acc, ACC_Y); acc_load(zinv, p.acc, ACC_Z);
     uint32_t rw[8];
     load32(rw, sigs, p.i, sig_stride);
     const uint8_t fl = flags[p.i];
-    if ((fl & 1) == 0) {                         // off-curve key
+    if ((fl & VERIFY_WINDOWED) == 0) {           // off-curve key
       if (!exact_offcurve) ok[p.i] = 0;          // reject mode; otherwise k_verify_exact_quad owns ok[i]
       return;
     }
-    ok[p.i] = (uint8_t)(verify_encode_lane(x, y, zinv, rw) && (fl & 2) != 0);
+    ok[p.i] = (uint8_t)(verify_encode_lane(x, y, zinv, rw) && (fl & VERIFY_Z_USABLE) != 0);
   }
 };
 
@@ -661,11 +634,9 @@ k_verify_main_quad(const uint32_t* digits, const uint32_t* table, const uint32_t
   if (i >= n) return;
   const int q = (int)(threadIdx.x & 3u);
   fe r;
-  verify_main_quad(r, digits + 16 * i, table + i * (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS), base16, q);
+  verify_main_quad(r, digits + digit_slot(i), table + table_slot(i), base16, q);
   if (q == 2) return;                            // T is not part of the result
-  uint32_t* o = accout + (i / BLOCK) * (ACC_WORDS * BLOCK) + (i % BLOCK) + (q == 0 ? 0 : q == 1 ? 10 : 20) * BLOCK;
-#pragma unroll
-  for (int j = 0; j < 10; j++) o[j * BLOCK] = r.v[j];
+  acc_put(acc_column(accout, i / BLOCK, i % BLOCK), q == 0 ? ACC_X : q == 1 ? ACC_Y : ACC_Z, r);
 }
 
 __global__ void __launch_bounds__(BLOCK, 2)
@@ -683,12 +654,12 @@ struct x25519_finish_policy {
     fe_set(z, 1);
     bool good = false;
     if (p.i < n) {
-      acc_load(z, p.acc, 2);
+      acc_load(z, p.acc, ACC_Z);
       good = !fe_iszero(z);
       if (!good) {                               // remember it: X := 0 makes the product 0 whatever the "inverse"
-        uint32_t* o = acc + p.tile * (ACC_WORDS * BLOCK) + threadIdx.x;
-#pragma unroll
-        for (int j = 0; j < 10; j++) o[j * BLOCK] = 0;
+        fe zero;
+        fe_set(zero, 0);
+        acc_put(acc_column(acc, p.tile, threadIdx.x), ACC_X, zero);
       }
     }
     den_commit(z, good, acc, k, K);
@@ -696,12 +667,12 @@ struct x25519_finish_policy {
   ED_DEV void item(int k) const {
     const finish_pos p = finish_at(k, acc, K);
     fe x, zinv;
-    if (p.i < n) { acc_load(x, p.acc, 0); acc_load(zinv, p.acc, 2); }
+    if (p.i < n) { acc_load(x, p.acc, ACC_X); acc_load(zinv, p.acc, ACC_Z); }
     // (x2 : z2), 1/z2 and the prefix products of the shared inversion determine shared secrets: they
     // do not outlive the call in HBM (x25519.c:221 burnstack); slots past the end hold the committed 1
-    uint32_t* o = acc + p.tile * (ACC_WORDS * BLOCK) + threadIdx.x;
+    uint32_t* o = acc_column(acc, p.tile, threadIdx.x);
 #pragma unroll
-    for (int j = 0; j < 10; j++) { o[j * BLOCK] = 0; o[(20 + j) * BLOCK] = 0; o[(30 + j) * BLOCK] = 0; }
+    for (int j = 0; j < 10; j++) { o[acc_at(ACC_X, j)] = 0; o[acc_at(ACC_Z, j)] = 0; o[acc_at(ACC_W, j)] = 0; }
     if (p.i >= n) return;
     uint32_t w[8];
     x25519_finish_lane(w, x, zinv);
@@ -809,14 +780,14 @@ struct encode_finish_policy {
   ED_DEV void den(int k, fe& z) const {
     const finish_pos p = finish_at(k, acc, K);
     fe_set(z, 1);
-    if (p.i < n) acc_load(z, p.acc, 2);
+    if (p.i < n) acc_load(z, p.acc, ACC_Z);
     den_commit(z, true, acc, k, K);
   }
   ED_DEV void item(int k) const {
     const finish_pos p = finish_at(k, acc, K);
     if (p.i >= n) return;
     fe x, y, zinv;
-    acc_load(x, p.acc, 0); acc_load(y, p.acc, 1); acc_load(zinv, p.acc, 2);
+    acc_load(x, p.acc, ACC_X); acc_load(y, p.acc, ACC_Y); acc_load(zinv, p.acc, ACC_Z);
     uint32_t w[8];
     encode_lane(w, x, y, zinv);
     store32(out, p.i, 32, w);
@@ -853,9 +824,8 @@ k_sign_point(uint32_t* accout, uint32_t* aux, const uint8_t* secs, const uint8_t
     // its 44 additions, which is what lets a row's two lookups be issued ahead of its two additions without a spill).
     // An idle lane must not leave a copy of the last item's secrets.
     if (i < n && part == 0) {
-      uint4* d = reinterpret_cast<uint4*>(aux + 16 * i);
-      d[0] = make_uint4(aw[0], aw[1], aw[2], aw[3]); d[1] = make_uint4(aw[4], aw[5], aw[6], aw[7]);
-      d[2] = make_uint4(rw[0], rw[1], rw[2], rw[3]); d[3] = make_uint4(rw[4], rw[5], rw[6], rw[7]);
+      store8(aux + 16 * i, aw);
+      store8(aux + 16 * i + 8, rw);
     }
     ge R;
     scale_base_lane<PARTS>(R, rw, lds_comb, part);
@@ -870,7 +840,7 @@ struct sign_finish_policy {
   ED_DEV void den(int k, fe& z) const {
     const finish_pos p = finish_at(k, acc, K);
     fe_set(z, 1);
-    if (p.i < n) acc_load(z, p.acc, 2);
+    if (p.i < n) acc_load(z, p.acc, ACC_Z);
     den_commit(z, true, acc, k, K);
   }
   ED_DEV void item(int k) const {
@@ -878,7 +848,7 @@ struct sign_finish_policy {
     if (p.i >= n) return;
     const size_t it = perm ? perm[p.i] : p.i;      // the item this position carries (k_sign_point)
     fe x, y, zinv;
-    acc_load(x, p.acc, 0); acc_load(y, p.acc, 1); acc_load(zinv, p.acc, 2);
+    acc_load(x, p.acc, ACC_X); acc_load(y, p.acc, ACC_Y); acc_load(zinv, p.acc, ACC_Z);
     uint32_t Rw[8], Sw[8], pub[8];
     encode_lane(Rw, x, y, zinv);
     load32(pub, pubs, it, 32);
@@ -887,12 +857,12 @@ struct sign_finish_policy {
     sc t;
     sign_challenge_lane(t, Rw, pub, m, mlen);              // the secret scalars are fetched only after the hash
     uint32_t aw[8], rw[8];
-    uint4* d = reinterpret_cast<uint4*>(aux + 16 * p.i);
-    const uint4 a0 = d[0], a1 = d[1], r0 = d[2], r1 = d[3];
-    aw[0] = a0.x; aw[1] = a0.y; aw[2] = a0.z; aw[3] = a0.w; aw[4] = a1.x; aw[5] = a1.y; aw[6] = a1.z; aw[7] = a1.w;
-    rw[0] = r0.x; rw[1] = r0.y; rw[2] = r0.z; rw[3] = r0.w; rw[4] = r1.x; rw[5] = r1.y; rw[6] = r1.z; rw[7] = r1.w;
-    const uint4 zero = make_uint4(0, 0, 0, 0);           // the secrets do not outlive the call in HBM
-    d[0] = zero; d[1] = zero; d[2] = zero; d[3] = zero;
+    uint32_t* d = aux + 16 * p.i;
+    load8(aw, d);
+    load8(rw, d + 8);
+    const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the secrets do not outlive the call in HBM
+    store8(d, zero);
+    store8(d + 8, zero);
     sign_response_lane(Sw, t, aw, rw);
     store32(sigs, it, 64, Rw);
     store32(sigs + 32, it, 64, Sw);
@@ -937,7 +907,7 @@ struct x25519_base_finish_policy {
     bool good = false;
     if (p.i < n) {
       fe y, z;
-      acc_load(y, p.acc, 1); acc_load(z, p.acc, 2);
+      acc_load(y, p.acc, ACC_Y); acc_load(z, p.acc, ACC_Z);
       fe_sub(d, z, y);                           // 3u
       good = !fe_iszero(d);
     }
@@ -947,10 +917,10 @@ struct x25519_base_finish_policy {
     const finish_pos p = finish_at(k, acc, K);
     if (p.i >= n) return;
     fe x, y, dinv, z, d;
-    acc_load(y, p.acc, 1); acc_load(dinv, p.acc, 2);     // the Z slot now holds 1/(z - y) (or 1/1)
+    acc_load(y, p.acc, ACC_Y); acc_load(dinv, p.acc, ACC_Z);     // the Z slot now holds 1/(z - y) (or 1/1)
     // z itself was overwritten; recover the numerator z + y = (z - y) + 2y from X's slot instead:
     // the point kernel stores z + y there (x is not needed for x25519_base)
-    acc_load(x, p.acc, 0);                               // = z + y
+    acc_load(x, p.acc, ACC_X);                           // = z + y
     fe_sub(d, x, y); fe_sub(d, d, y);                    // z - y, to detect the zero denominator
     fe zero;
     fe_set(zero, 0);
@@ -1022,13 +992,10 @@ k_verify_prepare_pair(edk_verify_items src, size_t n, uint32_t* digits, uint32_t
     }
     verify_s_lane(sw);
     verify_half_scalars_lane<BITS>(hd, tw, sw);
-    uint4* d = reinterpret_cast<uint4*>(digits + 16 * i);
-    d[0] = make_uint4(tw[0], tw[1], tw[2], tw[3]); d[1] = make_uint4(tw[4], tw[5], tw[6], tw[7]);
-    d[2] = make_uint4(sw[0], sw[1], sw[2], sw[3]); d[3] = make_uint4(sw[4], sw[5], sw[6], sw[7]);
-    uint4* o = reinterpret_cast<uint4*>(hdigits + HALF_DIGIT_WORDS * i);
-#pragma unroll
-    for (int q = 0; q < HALF_DIGIT_WORDS / 4; q++) o[q] = make_uint4(hd[4 * q], hd[4 * q + 1], hd[4 * q + 2], hd[4 * q + 3]);
-    if ((hd[24] & 4u) != 0) atomicAdd(offcount + EDK_REFUSED_WORD, 1u);
+    store8(digits + digit_slot(i), tw);
+    store8(digits + digit_slot(i) + 8, sw);
+    hdigits_store(hdigits, i, hd);
+    if ((hd[HALF_STATUS_WORD] & HALF_PAIR_REFUSED) != 0) atomicAdd(offcount + EDK_REFUSED_WORD, 1u);
     return;
   }
   const size_t g = (size_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -1038,7 +1005,7 @@ k_verify_prepare_pair(edk_verify_items src, size_t n, uint32_t* digits, uint32_t
   // lane 0: -A permissively (ed.c:100-149), lane 1: -R' strictly (lanes.h: verify_half_point_lane)
   uint32_t pw[8];
   load32(pw, second ? src.sigs : src.pubs, i, second ? src.sig_stride : src.pub_stride);
-  uint32_t* tab = (second ? rtable : table) + i * (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS);
+  uint32_t* tab = (second ? rtable : table) + table_slot(i);
   bool oncurve;
   ge p;
   ge_frombytes(p, oncurve, pw, true);
@@ -1051,11 +1018,11 @@ k_verify_prepare_pair(edk_verify_items src, size_t n, uint32_t* digits, uint32_t
   const int other = __shfl_xor(mine, 1);
   if (!second) {
     const bool keep = oncurve && !all_exact;
-    flags[i] = (uint8_t)((keep ? 1 : 0) | (other ? 4 : 0));
+    flags[i] = (uint8_t)((keep ? VERIFY_WINDOWED : 0) | (other ? VERIFY_R_CANONICAL : 0));
     // the two work lists of k_verify_prepare (the four-lane evaluations of small passes do not use the first)
     const uint32_t on_slot = wave_append(offcount + EDK_ONLIST_WORD, keep);
     if (keep) onlist[on_slot] = (uint32_t)i;
-    const uint32_t off_slot = wave_append(offcount, !keep);
+    const uint32_t off_slot = wave_append(offcount + EDK_OFFLIST_WORD, !keep);
     if (!keep) offlist[off_slot] = (uint32_t)i;
   }
 }
@@ -1067,15 +1034,8 @@ k_verify_main_half_quad(uint8_t* ok, const uint32_t* hdigits, const uint32_t* ta
   const size_t i = ((size_t)blockIdx.x * QUAD_BLOCK + threadIdx.x) >> 2;      // quads are all-or-nothing
   if (i >= n) return;
   const int q = (int)(threadIdx.x & 3u);
-  const bool neutral = verify_half_main_quad<WINDOWS>(hdigits + HALF_DIGIT_WORDS * i, table + i * (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS),
-                                             rtable + i * (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS), base16, q);
-  if (q != 0) return;
-  const uint8_t fl = flags[i];
-  if ((fl & 1) == 0) {                           // the exact path owns this verdict
-    if (!exact_offcurve) ok[i] = 0;
-    return;
-  }
-  ok[i] = (uint8_t)(neutral && (fl & 4) != 0);
+  const bool neutral = verify_half_main_quad<WINDOWS>(hdigits + hdigit_slot(i), table + table_slot(i), rtable + table_slot(i), base16, q);
+  if (q == 0) half_verdict_store(ok, i, flags[i], neutral, exact_offcurve);
 }
 
 // The smallest passes (quad_lanes.h: verify_half_window_sum_quad): block i adds up the 64 windows of item i, one quad each;
@@ -1085,9 +1045,8 @@ __global__ void __launch_bounds__(QUAD_BLOCK, 2)
 k_verify_window_sums(uint32_t* sums, const uint32_t* hdigits, const uint32_t* table, const uint32_t* rtable, const uint32_t* base16) {
   const size_t i = blockIdx.x;
   const int w = (int)(threadIdx.x >> 2), q = (int)(threadIdx.x & 3u);
-  verify_half_window_sum_quad<WINDOWS>(sums + (i * HALF_LONG_WINDOWS + (size_t)w) * HALF_SUM_WORDS, hdigits + HALF_DIGIT_WORDS * i,
-                              table + i * (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS), rtable + i * (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS),
-                              base16, w, q);
+  verify_half_window_sum_quad<WINDOWS>(sums + (i * HALF_LONG_WINDOWS + (size_t)w) * HALF_SUM_WORDS, hdigits + hdigit_slot(i),
+                              table + table_slot(i), rtable + table_slot(i), base16, w, q);
 }
 
 template <int WINDOWS>
@@ -1096,14 +1055,8 @@ k_verify_main_sums_quad(uint8_t* ok, const uint32_t* hdigits, const uint32_t* su
   const size_t i = ((size_t)blockIdx.x * QUAD_BLOCK + threadIdx.x) >> 2;      // quads are all-or-nothing
   if (i >= n) return;
   const int q = (int)(threadIdx.x & 3u);
-  const bool neutral = verify_half_main_sums_quad<WINDOWS>(hdigits + HALF_DIGIT_WORDS * i, sums + i * (HALF_LONG_WINDOWS * HALF_SUM_WORDS), q);
-  if (q != 0) return;
-  const uint8_t fl = flags[i];
-  if ((fl & 1) == 0) {                           // the exact path owns this verdict
-    if (!exact_offcurve) ok[i] = 0;
-    return;
-  }
-  ok[i] = (uint8_t)(neutral && (fl & 4) != 0);
+  const bool neutral = verify_half_main_sums_quad<WINDOWS>(hdigits + hdigit_slot(i), sums + i * (HALF_LONG_WINDOWS * HALF_SUM_WORDS), q);
+  if (q == 0) half_verdict_store(ok, i, flags[i], neutral, exact_offcurve);
 }
 
 }  // namespace ed

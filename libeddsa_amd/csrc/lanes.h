@@ -22,19 +22,7 @@
 #include "sc25519.h"
 #include "sha512.h"
 #include "halve.h"
-
-#define TABLE_BASE16_ENTRIES 32769 /* k*B, k = 0..32768: 16-bit signed windows of S (4 MiB, L2/MALL) */
-#define COMB_W 6                  /* signed window width of the fixed-base comb (the reference's is 4, ed.c:397-430) */
-#define COMB_HALF (1 << (COMB_W - 1))          /* digits d in [-COMB_HALF, COMB_HALF - 1] */
-#define COMB_DIGITS (COMB_W == 4 ? 64 : COMB_W == 5 ? 52 : 44)   /* digits of x + offset: 64 x 4, 52 x 5 or 44 x 6 bits */
-#define COMB_ROWS (COMB_DIGITS / 2)            /* even digits and odd digits share a row */
-#define TABLE_COMB_ENTRIES (COMB_ROWS * COMB_HALF) /* comb[i][k] = (k+1) * 2^(2*COMB_W*i) * B, k < COMB_HALF */
-#define TABLE_ENTRY_WORDS 32      /* 3 x 10 limbs + 2 padding words */
-#define COMB_IMG_ENTRIES COMB_HALF       /* LDS image of a comb row: entry m - 1 = m * 2^(2*COMB_W*i) * B, m = 1..COMB_HALF */
-#define COMB_IMG_ENTRY_WORDS 36   /* 30 limbs + 6 padding words: entries start 4 banks apart */
-#define COMB_IMG_WORDS (COMB_ROWS * COMB_IMG_ENTRIES * COMB_IMG_ENTRY_WORDS)
-#define VERIFY_TABLE_ENTRIES 9    /* 0..8 times -A, cached form */
-#define VERIFY_ENTRY_WORDS 32     /* ymx | ypx | t2d | z2, 255 bits packed into eight words each: one 128-byte line */
+#include "edk_layout.h"
 
 namespace ed {
 
@@ -384,9 +372,12 @@ ED_DEV bool verify_encode_lane(const fe& X, const fe& Y, const fe& zinv, const u
 // read over 64 windows ("long"; f_j*B then for every j < 16 and no g); its wave runs the long loop, in which the
 // short items of the wave add neutral elements from window 34 on.  About one wave in 180 is long.
 // hd (HALF_DIGIT_WORDS per item): v + 0x88.. [0,8) | |u| + 0x88.. [8,16) | s' + 0x8000.. [16,24) |
-// [24]: bit 0 = (u < 0), bit 1 = long, bit 2 = the search returned a pair that failed the exact check (diagnostic: never seen).
+// [HALF_STATUS_WORD]: HALF_U_NEGATIVE = (u < 0), HALF_LONG, HALF_PAIR_REFUSED = the search returned a pair that failed the exact
+// check (diagnostic: never seen).
 // ---------------------------------------------------------------------------------------------
-#define HALF_DIGIT_WORDS 28
+constexpr int HALF_STATUS_WORD = 24;
+enum : uint32_t { HALF_U_NEGATIVE = 1u, HALF_LONG = 2u, HALF_PAIR_REFUSED = 4u };
+static_assert(HALF_STATUS_WORD < HALF_DIGIT_WORDS, "the status word is one of the item's words");
 constexpr int HALF_LONG_WINDOWS = 64;
 
 // tdig / sdig: the digit words k_verify_prepare wrote (t + 0x88.., S mod l + 0x8000..); BITS: halve.h
@@ -453,7 +444,7 @@ ED_DEV void verify_half_scalars_lane(uint32_t hd[HALF_DIGIT_WORDS], const uint32
   words_add_pattern(u8, 0x88888888u);
 #pragma unroll
   for (int k = 0; k < 8; k++) { hd[k] = v8[k]; hd[8 + k] = u8[k]; hd[16 + k] = sw[k]; }
-  hd[24] = (uneg ? 1u : 0u) | (found ? 0u : 2u) | (mismatch ? 4u : 0u);
+  hd[HALF_STATUS_WORD] = (uneg ? HALF_U_NEGATIVE : 0u) | (found ? 0u : HALF_LONG) | (mismatch ? HALF_PAIR_REFUSED : 0u);
   hd[25] = 0; hd[26] = 0; hd[27] = 0;
 }
 
@@ -482,7 +473,7 @@ ED_DEV bool verify_half_main_lane(const uint32_t* hd, const uint32_t* tab_a, con
                                   bool long_loop, int hs = 1, const uint32_t* neutral = nullptr) {   // hs: distance in words between consecutive digit words (1: as k_verify_halve wrote them); neutral: a table whose entry 0 every lane may read for a zero digit (one line for the whole chip instead of one per item), or none
   ge acc;
   ge_neutral(acc);
-  const bool uneg = (hd[24 * hs] & 1u) != 0, is_long = WITH_LONG && (hd[24 * hs] & 2u) != 0;
+  const bool uneg = (hd[HALF_STATUS_WORD * hs] & HALF_U_NEGATIVE) != 0, is_long = WITH_LONG && (hd[HALF_STATUS_WORD * hs] & HALF_LONG) != 0;
   const int top = (WITH_LONG && long_loop ? HALF_LONG_WINDOWS : WINDOWS) - 1;
 #pragma unroll 1
   for (int w = top; w >= 0; w--) {

@@ -76,7 +76,7 @@ constexpr size_t LAYER_SCRATCH_BYTES = 2 * ((REF_JSF_LEN + 3) / 4 * 4) + 160 * 4
 constexpr size_t LAYER_TABLE_SCRATCH_BYTES = (4 * VERIFY_ENTRY_WORDS + 36 + EXACT_STATE_WORDS + 16 + 4 + VERIFY_ENTRY_WORDS) * 4;
 static_assert(LAYER_TABLE_SCRATCH_BYTES % 128 == 0, "entries are 128-byte lines");
 // form 4: two table slots | two slots for digits (at +64 words) and walks (at +128) | the shared entry
-constexpr size_t LAYER_PAIR_SCRATCH_BYTES = (4 * VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS + VERIFY_ENTRY_WORDS) * 4;
+constexpr size_t LAYER_PAIR_SCRATCH_BYTES = (4 * VERIFY_ITEM_TABLE_WORDS + VERIFY_ENTRY_WORDS) * 4;
 static_assert(LAYER_PAIR_SCRATCH_BYTES % 128 == 0, "entries are 128-byte lines");
 
 __global__ void __launch_bounds__(64)
@@ -139,7 +139,7 @@ k_debug_layer(int op, int form, uint8_t* out, size_t out_w, const uint8_t* in, s
     ge_niels pcB;
     niels_load(pcB, base16 + TABLE_ENTRY_WORDS);
     if (form == 4) {                              // two items per lane, as k_verify_exact_lane_chain walks them: this item and the next one of the batch
-      constexpr uint32_t SLOT = VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS;
+      constexpr uint32_t SLOT = VERIFY_ITEM_TABLE_WORDS;
       uint32_t* sp = reinterpret_cast<uint32_t*>(scratch + i * LAYER_PAIR_SCRATCH_BYTES);
       uint32_t* tabs = sp; uint32_t* digs = sp + 2 * SLOT; uint32_t* bentry = sp + 4 * SLOT;
       exact_bentry_store(bentry);

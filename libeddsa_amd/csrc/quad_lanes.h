@@ -322,7 +322,7 @@ template <int WINDOWS = HALF_WINDOWS>
 ED_DEV bool verify_half_main_quad(const uint32_t* hd, const uint32_t* tab_a, const uint32_t* tab_r, const uint32_t* base16, int q) {
   fe r;
   fe_set(r, (uint32_t)(q & 1));                  // neutral element (0, 1, 0, 1) as (X, Y, T, Z)
-  const bool uneg = (hd[24] & 1u) != 0, is_long = (hd[24] & 2u) != 0;
+  const bool uneg = (hd[HALF_STATUS_WORD] & HALF_U_NEGATIVE) != 0, is_long = (hd[HALF_STATUS_WORD] & HALF_LONG) != 0;
   const int top = (__any(is_long) ? HALF_LONG_WINDOWS : WINDOWS) - 1;   // the wave's loop (lanes.h: verify_half_main_lane)
 #pragma unroll 1
   for (int w = top; w >= 0; w--) {
@@ -392,7 +392,7 @@ ED_DEV bool verify_half_main_quad(const uint32_t* hd, const uint32_t* tab_a, con
 template <int WINDOWS = HALF_WINDOWS>
 ED_DEV void verify_half_window_sum_quad(uint32_t* out, const uint32_t* hd, const uint32_t* tab_a, const uint32_t* tab_r,
                                         const uint32_t* base16, int w, int q) {
-  const bool uneg = (hd[24] & 1u) != 0, is_long = (hd[24] & 2u) != 0;
+  const bool uneg = (hd[HALF_STATUS_WORD] & HALF_U_NEGATIVE) != 0, is_long = (hd[HALF_STATUS_WORD] & HALF_LONG) != 0;
   fe r;
   if (w >= (is_long ? HALF_LONG_WINDOWS : WINDOWS)) {
     fe_set(r, q == 3 ? 2u : q == 2 ? 0u : 1u);   // the neutral element's multipliers (1, 1, 0, 2): a wave with a long item runs 64 windows
@@ -447,7 +447,7 @@ template <int WINDOWS = HALF_WINDOWS>
 ED_DEV bool verify_half_main_sums_quad(const uint32_t* hd, const uint32_t* sums, int q) {
   fe r;
   fe_set(r, (uint32_t)(q & 1));                  // neutral element (0, 1, 0, 1) as (X, Y, T, Z)
-  const bool is_long = (hd[24] & 2u) != 0;
+  const bool is_long = (hd[HALF_STATUS_WORD] & HALF_LONG) != 0;
   const int top = (__any(is_long) ? HALF_LONG_WINDOWS : WINDOWS) - 1;
 #pragma unroll 1
   for (int w = top; w >= 0; w--) {

@@ -45,6 +45,7 @@
 // coefficients, digit recoding) is in rlc_lanes.h, which the host-check build also compiles.
 #include "eddsa_kernels.h"
 #include "edk_checked.h"
+#include "kernel_io.h"
 #include "rlc_lanes.h"
 #include "quad_lanes.h"
 
@@ -91,15 +92,11 @@ __host__ inline rlc_layout rlc_carve(size_t cap) {
   return L;
 }
 
-ED_DEV void load_words8(uint32_t w[8], const uint8_t* p) {
-  if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-    const uint4 a = reinterpret_cast<const uint4*>(p)[0], b = reinterpret_cast<const uint4*>(p)[1];
-    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-      w[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) | ((uint32_t)p[4 * i + 3] << 24);
-  }
+// what the two hashing kernels leave per item: t | S mod l (eight words each) and the leaf of the batch hash tree
+ED_DEV void rlc_hash_store(uint32_t* ts, uint32_t* leaf, size_t i, const uint32_t tw[8], const uint32_t sw[8], const uint32_t lf[8]) {
+  store8(ts + 16 * i, tw);
+  store8(ts + 16 * i + 8, sw);
+  store8(leaf + 8 * i, lf);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -111,17 +108,13 @@ k_rlc_hash(edk_verify_items src, size_t n, uint32_t* ts, uint32_t* leaf, const u
   if (g >= n) return;
   const size_t i = perm ? perm[g] : g;           // ragged messages: a wave hashes items of one length (edk_msg_order)
   uint32_t rw[8], aw[8], sw[8], tw[8], lf[8];
-  load_words8(rw, src.sigs + i * src.sig_stride);
-  load_words8(aw, src.pubs + i * src.pub_stride);
-  load_words8(sw, src.sigs + i * src.sig_stride + 32);
+  load32(rw, src.sigs, i, src.sig_stride);
+  load32(aw, src.pubs, i, src.pub_stride);
+  load32(sw, src.sigs + 32, i, src.sig_stride);
   const uint8_t* m; size_t mlen;
   msg_span(m, mlen, src.msgs, src.msg_off, src.msg_end, src.msg_len, src.msg_stride, i);
   rlc_hash_lane(tw, sw, lf, rw, aw, src.sigs + i * src.sig_stride + 32, m, mlen);
-  uint4* o = reinterpret_cast<uint4*>(ts + 16 * i);
-  o[0] = make_uint4(tw[0], tw[1], tw[2], tw[3]); o[1] = make_uint4(tw[4], tw[5], tw[6], tw[7]);
-  o[2] = make_uint4(sw[0], sw[1], sw[2], sw[3]); o[3] = make_uint4(sw[4], sw[5], sw[6], sw[7]);
-  uint4* l = reinterpret_cast<uint4*>(leaf + 8 * i);
-  l[0] = make_uint4(lf[0], lf[1], lf[2], lf[3]); l[1] = make_uint4(lf[4], lf[5], lf[6], lf[7]);
+  rlc_hash_store(ts, leaf, i, tw, sw, lf);
 }
 // the same for caller-supplied digests (ed25519_verify_digests_rlc*): item i's 64 bytes of SHA-512(R || A || M) lie in the message
 // slot of src; nothing but the leaf is hashed
@@ -130,15 +123,11 @@ k_rlc_hash_digest(edk_verify_items src, size_t n, uint32_t* ts, uint32_t* leaf) 
   const size_t i = (size_t)blockIdx.x * RLC_BLOCK + threadIdx.x;
   if (i >= n) return;
   uint32_t dw[16], sw[8], tw[8], lf[8];
-  load_words8(dw, src.msgs + i * src.msg_stride);
-  load_words8(dw + 8, src.msgs + i * src.msg_stride + 32);
-  load_words8(sw, src.sigs + i * src.sig_stride + 32);
+  load32(dw, src.msgs, i, src.msg_stride);
+  load32(dw + 8, src.msgs + 32, i, src.msg_stride);
+  load32(sw, src.sigs + 32, i, src.sig_stride);
   rlc_digest_lane(tw, sw, lf, dw, src.sigs + i * src.sig_stride + 32);
-  uint4* o = reinterpret_cast<uint4*>(ts + 16 * i);
-  o[0] = make_uint4(tw[0], tw[1], tw[2], tw[3]); o[1] = make_uint4(tw[4], tw[5], tw[6], tw[7]);
-  o[2] = make_uint4(sw[0], sw[1], sw[2], sw[3]); o[3] = make_uint4(sw[4], sw[5], sw[6], sw[7]);
-  uint4* l = reinterpret_cast<uint4*>(leaf + 8 * i);
-  l[0] = make_uint4(lf[0], lf[1], lf[2], lf[3]); l[1] = make_uint4(lf[4], lf[5], lf[6], lf[7]);
+  rlc_hash_store(ts, leaf, i, tw, sw, lf);
 }
 
 // R2: one level of the hash tree: node j = SHA-512(children 16 j .. 16 j + 15)[0..32).  (A lane hashes its children's 512 bytes
@@ -166,10 +155,10 @@ k_rlc_points(edk_verify_items src, size_t n, uint32_t* niels_a, uint32_t* niels_
   if (i >= n) return;
   uint32_t w[8];
   ge_niels nl;
-  load_words8(w, src.pubs + i * src.pub_stride);
+  load32(w, src.pubs, i, src.pub_stride);
   uint8_t fl = rlc_decode_key_lane(nl, w);
   niels_store(niels_a + 32 * i, nl);
-  load_words8(w, src.sigs + i * src.sig_stride);
+  load32(w, src.sigs, i, src.sig_stride);
   fl |= rlc_decode_r_lane(nl, w);
   niels_store(niels_r + 32 * i, nl);
   flags[i] = fl;
@@ -196,11 +185,9 @@ k_rlc_scalars(size_t n, const uint32_t* ts, const uint32_t* seed, const uint8_t*
     const size_t g = i / RLC_G, k = i % RLC_G;
     int8_t* d = dig + g * (size_t)RLC_WINDOWS * RLC_G + k;
     if (i < n && (flags[i] & RLC_R_VALID)) {
-      const uint4* p = reinterpret_cast<const uint4*>(ts + 16 * i);
-      const uint4 t0 = p[0], t1 = p[1], s0 = p[2], s1 = p[3];
-      const uint32_t tw[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-      const uint32_t sw[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-      uint32_t sd[8];
+      uint32_t tw[8], sw[8], sd[8];
+      load8(tw, ts + 16 * i);
+      load8(sw, ts + 16 * i + 8);
 #pragma unroll
       for (int q = 0; q < 8; q++) sd[q] = seed[q];
       int8_t da[RLC_WINDOWS_A], dr[RLC_WINDOWS_R];

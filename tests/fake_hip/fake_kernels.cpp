@@ -102,7 +102,7 @@ static const Tables& tables() { static Tables t; return t; }
 // one verify item as the default route decides it: the half-length evaluation (long items in place), the reference-order
 // chain for keys that are no curve points
 static int verify_item(const edk_verify_src& s, size_t i, const uint32_t* base16, int exact_offcurve) {
-  alignas(16) uint32_t tab[VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS], rtab[VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS];
+  alignas(16) uint32_t tab[VERIFY_ITEM_TABLE_WORDS], rtab[VERIFY_ITEM_TABLE_WORDS];
   uint32_t rw[8], sw[8], aw[8], tw[8], hd[HALF_DIGIT_WORDS];
   rd(rw, s.sigs + i * s.sig_stride); rd(sw, s.sigs + i * s.sig_stride + 32); rd(aw, s.pubs + i * s.pub_stride);
   const uint8_t* m; size_t mlen;
@@ -118,7 +118,7 @@ static int verify_item(const edk_verify_src& s, size_t i, const uint32_t* base16
   }
   verify_half_scalars_lane(hd, tw, sw);
   const bool rvalid = verify_half_point_lane(rtab, rw);
-  const bool is_long = (hd[24] & 2u) != 0;
+  const bool is_long = (hd[HALF_STATUS_WORD] & HALF_LONG) != 0;
   const bool neutral = is_long ? verify_half_main_lane<true>(hd, tab, rtab, base16, true) : verify_half_main_lane<false>(hd, tab, rtab, base16, false);
   return neutral && rvalid ? 1 : 0;
 }
@@ -167,7 +167,7 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* src, size_t n, const ui
   else own(src->msgs, src->msg_len ? (n - 1) * src->msg_stride + src->msg_len : 0, "messages");
   own(base16, (size_t)2 * TABLE_BASE16_ENTRIES * TABLE_ENTRY_WORDS * 4, "base16");
   if (n > ws->capacity) { fprintf(stderr, "fake_kernels: pass of %zu items through a workspace of %zu\n", n, ws->capacity); abort(); }
-  own(ws->digits, ws->capacity * 64, "workspace digits"); own(ws->table, ws->capacity * VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS * 4, "workspace table");
+  own(ws->digits, ws->capacity * 64, "workspace digits"); own(ws->table, ws->capacity * VERIFY_ITEM_TABLE_WORDS * 4, "workspace table");
   own(ws->flags, ws->capacity, "workspace flags"); own(ws->offcount, 256, "work-list counter");
   if (fake_hip_stream_device(ws->side) != cur()) { fprintf(stderr, "fake_kernels: the workspace's side stream belongs to another device\n"); abort(); }
   // the events of kernels.hip: edk_verify, in its order

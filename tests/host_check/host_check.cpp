@@ -66,7 +66,7 @@ void hc_x25519(uint8_t out[32], const uint8_t scalar[32], const uint8_t point[32
 // the three verify kernels for one item (the finish step without the cross-item batching, plus
 // the same Z = 0 / off-curve rule)
 int hc_verify(const uint8_t sig[64], const uint8_t pub[32], const uint8_t* msg, size_t len) {
-  alignas(16) uint32_t tab[VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS];
+  alignas(16) uint32_t tab[VERIFY_ITEM_TABLE_WORDS];
   uint32_t rw[8], sw[8], aw[8], tw[8];
   rd(rw, sig); rd(sw, sig + 32); rd(aw, pub);
   const bool oncurve = verify_prepare_lane(tw, sw, tab, rw, aw, msg, len);
@@ -85,18 +85,18 @@ int hc_verify(const uint8_t sig[64], const uint8_t pub[32], const uint8_t* msg, 
 // a pair that the exact integer check of verify_half_scalars_lane refused), 2 = the item is handed to the exact path
 // (key off the curve)
 int hc_verify_half(const uint8_t sig[64], const uint8_t pub[32], const uint8_t* msg, size_t len) {
-  alignas(16) uint32_t tab[VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS], rtab[VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS];
+  alignas(16) uint32_t tab[VERIFY_ITEM_TABLE_WORDS], rtab[VERIFY_ITEM_TABLE_WORDS];
   uint32_t rw[8], sw[8], aw[8], tw[8], hd[HALF_DIGIT_WORDS];
   rd(rw, sig); rd(sw, sig + 32); rd(aw, pub);
   const bool oncurve = verify_prepare_lane(tw, sw, tab, rw, aw, msg, len);
   verify_half_scalars_lane(hd, tw, sw);
   const bool rvalid = verify_half_point_lane(rtab, rw);
   if (!oncurve) return 2;
-  const bool is_long = (hd[24] & 2u) != 0;
+  const bool is_long = (hd[HALF_STATUS_WORD] & HALF_LONG) != 0;
   // short items as k_verify_main_half evaluates them, long ones as their wave of k_verify_main_half_quad does
   const bool neutral = is_long ? verify_half_main_lane<true>(hd, tab, rtab, tables().b16(), true)
                                : verify_half_main_lane<false>(hd, tab, rtab, tables().b16(), false);
-  return (neutral && rvalid ? 1 : 0) + (is_long ? 4 : 0) + ((hd[24] & 4u) ? 8 : 0);   // + 8: the pair failed the exact check
+  return (neutral && rvalid ? 1 : 0) + (is_long ? 4 : 0) + ((hd[HALF_STATUS_WORD] & HALF_PAIR_REFUSED) ? 8 : 0);   // + 8: the pair failed the exact check
 }
 
 // fault injection into the pair search (halve.h: HALVE_FAULT): the n-th working half-step takes a quotient one too large
@@ -104,19 +104,19 @@ void hc_halve_fault(int n) { halve_fault = n; }
 
 // the wide form (pairs up to 2^138, 35 windows) that one-lane passes below 2^18 items use
 int hc_verify_half_wide(const uint8_t sig[64], const uint8_t pub[32], const uint8_t* msg, size_t len) {
-  alignas(16) uint32_t tab[VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS], rtab[VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS];
+  alignas(16) uint32_t tab[VERIFY_ITEM_TABLE_WORDS], rtab[VERIFY_ITEM_TABLE_WORDS];
   uint32_t rw[8], sw[8], aw[8], tw[8], hd[HALF_DIGIT_WORDS];
   rd(rw, sig); rd(sw, sig + 32); rd(aw, pub);
   const bool oncurve = verify_prepare_lane(tw, sw, tab, rw, aw, msg, len);
   verify_half_scalars_lane<HALF_BITS_SMALL>(hd, tw, sw);
   const bool rvalid = verify_half_point_lane(rtab, rw);
-  if (!oncurve || (hd[24] & 2u) != 0) return 2;   // the exact path
+  if (!oncurve || (hd[HALF_STATUS_WORD] & HALF_LONG) != 0) return 2;   // the exact path
   return verify_half_main_lane<false, HALF_WINDOWS_SMALL>(hd, tab, rtab, tables().b16(), false) && rvalid ? 1 : 0;
 }
 
 // the same with the long loop forced, as a short item runs it in a wave that contains a long one
 int hc_verify_half_in_long_wave(const uint8_t sig[64], const uint8_t pub[32], const uint8_t* msg, size_t len) {
-  alignas(16) uint32_t tab[VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS], rtab[VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS];
+  alignas(16) uint32_t tab[VERIFY_ITEM_TABLE_WORDS], rtab[VERIFY_ITEM_TABLE_WORDS];
   uint32_t rw[8], sw[8], aw[8], tw[8], hd[HALF_DIGIT_WORDS];
   rd(rw, sig); rd(sw, sig + 32); rd(aw, pub);
   const bool oncurve = verify_prepare_lane(tw, sw, tab, rw, aw, msg, len);
@@ -155,7 +155,7 @@ int hc_verify_exact(const uint8_t sig[64], const uint8_t pub[32], const uint8_t*
 // step left in the item's workspace (digit words, entry 1 of its table), Q + B and Q - B into entries 2 and 3, the chain
 // over packed cached entries
 int hc_verify_exact_table(const uint8_t sig[64], const uint8_t pub[32], const uint8_t* msg, size_t len) {
-  alignas(16) uint32_t tab[VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS], bentry[VERIFY_ENTRY_WORDS];
+  alignas(16) uint32_t tab[VERIFY_ITEM_TABLE_WORDS], bentry[VERIFY_ENTRY_WORDS];
   uint32_t rw[8], sw[8], aw[8], tw[8], digits[16], dig[EXACT_DIGIT_WORDS];
   rd(rw, sig); rd(sw, sig + 32); rd(aw, pub);
   verify_prepare_lane(tw, sw, tab, rw, aw, msg, len);
@@ -175,7 +175,7 @@ int hc_verify_exact_table(const uint8_t sig[64], const uint8_t pub[32], const ui
 // one-lane kernels compute, as bytes - for a Q that is no curve point the bytes depend on the digit string and on the order
 // of the formulas, which a verdict hardly ever shows
 void hc_dual_scale_exact_table(uint8_t out[32], const uint8_t s[32], const uint8_t t[32], const uint8_t q[32], int staged) {
-  alignas(16) uint32_t tab[VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS], bentry[VERIFY_ENTRY_WORDS], state[EXACT_STATE_WORDS];
+  alignas(16) uint32_t tab[VERIFY_ITEM_TABLE_WORDS], bentry[VERIFY_ENTRY_WORDS], state[EXACT_STATE_WORDS];
   uint32_t w[8], digits[16], dig[EXACT_DIGIT_WORDS], o[8];
   sc x, y;
   rd(w, s); sc_from_words<8>(x, w); sc_to_words(digits + 8, x);
@@ -221,7 +221,7 @@ static void table_setup(uint32_t* tab, uint32_t* dig, const uint8_t s[32], const
   verify_exact_setup_table_lane(tab, dig, 1, digits, tables().b16() + TABLE_ENTRY_WORDS);
 }
 int hc_dual_scale_exact_pair(uint8_t out_a[32], uint8_t out_b[32], const uint8_t a96[96], const uint8_t b96[96], int have_b, int unit) {
-  constexpr uint32_t SLOT = VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS;       // two workspace slots each, as the kernel's table / rtable
+  constexpr uint32_t SLOT = VERIFY_ITEM_TABLE_WORDS;       // two workspace slots each, as the kernel's table / rtable
   alignas(16) uint32_t tabs[2 * SLOT], digs[2 * SLOT], bentry[VERIFY_ENTRY_WORDS];
   alignas(16) uint32_t st_a[EXACT_STATE_WORDS + 4], st_b[EXACT_STATE_WORDS + 4];
   uint32_t *tab_a = tabs, *tab_b = tabs + SLOT, *dig_a = digs, *dig_b = digs + SLOT, o[8];
