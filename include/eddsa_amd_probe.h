@@ -5,7 +5,7 @@
  * fe25519.h ...) but linked into nothing a caller binds: libeddsa_amd.so exports none of these names and contains none of
  * these kernels.  The repository's GPU tests load it beside the product to run ONE layer - a field multiplication, a
  * scalar reduction, SHA-512, point import / export, the fixed-base comb, the reference-order double-scalar chain in each of
- * its forms - on caller-given inputs and compare with the golden layer vectors of the reference
+ * its forms, the two X25519 ladders - on caller-given inputs and compare with the golden layer vectors of the reference
  * (tests/golden/layer_kats.json).  Host pointers; runs on the calling thread's current HIP device; returns 0 or the
  * negated hipError_t.
  */
@@ -49,9 +49,14 @@ extern "C" {
  *                                                                               k_verify_exact_lane_chain walks them
  *   EDL_GE_DBL_ADD            p 32 | k 2 (LE) | pad 6                      32   enc(2 P + k B): form 0 ge_dbl + ge_add_niels, form 1 quad_dbl +
  *                                                                               quad_add_entry (the windowed evaluation's two steps)
+ *   EDL_X25519_LADDER         scalar 32 | point 32                         64   x2 32 | z2 32, both canonical: mg_scale lib/x25519.c:104-123 on
+ *                                                                               the clamped scalar, before the inversion; form 0 the one-lane
+ *                                                                               ladder (k_x25519_ladder), form 1 the four-lane one
+ *                                                                               (k_x25519_ladder_quad: lane 0 delivers x2, lane 1 z2)
  */
 enum { EDL_FE_MUL = 1, EDL_FE_SQ, EDL_FE_INV, EDL_FE_POW2523, EDL_FE_MUL_LOOSE, EDL_SC_REDUCE32, EDL_SC_REDUCE64,
-       EDL_SC_MULADD, EDL_SHA512, EDL_ED_IMPORT_EXPORT, EDL_ED_SCALE_BASE, EDL_ED_DUAL_SCALE, EDL_GE_DBL_ADD };
+       EDL_SC_MULADD, EDL_SHA512, EDL_ED_IMPORT_EXPORT, EDL_ED_SCALE_BASE, EDL_ED_DUAL_SCALE, EDL_GE_DBL_ADD,
+       EDL_X25519_LADDER };
 EDDSA_PROBE_DECL int eddsa_amd_probe_layer(int op, int form, uint8_t *out, size_t out_w, const uint8_t *in, size_t in_w, size_t n);
 
 

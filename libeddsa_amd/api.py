@@ -116,7 +116,8 @@ def shutdown():
 
 HOOKS_OFF = -100002
 LAYER_OPS = {"fe_mul": 1, "fe_sq": 2, "fe_inv": 3, "fe_pow2523": 4, "fe_mul_loose": 5, "sc_reduce32": 6, "sc_reduce64": 7,
-             "sc_muladd": 8, "sha512": 9, "ed_import_export": 10, "ed_scale_base": 11, "ed_dual_scale": 12, "ge_dbl_add": 13}
+             "sc_muladd": 8, "sha512": 9, "ed_import_export": 10, "ed_scale_base": 11, "ed_dual_scale": 12, "ge_dbl_add": 13,
+             "x25519_ladder": 14}
 
 
 def _hooks():

@@ -1205,6 +1205,17 @@ static_assert(shape_is(point_shape_of(1 << 16), 1, 256, 256, false) && shape_is(
 static_assert(shape_is(point_shape_of((size_t)POINT_MAX_BLOCKS * POINT_BLOCK), 1, POINT_BLOCK, POINT_MAX_BLOCKS, false) &&
               shape_is(point_shape_of((size_t)POINT_MAX_BLOCKS * POINT_BLOCK + 1), 1, POINT_BLOCK, POINT_MAX_BLOCKS, true), "more tiles than resident blocks: persistent");
 
+// X25519: the four-lane ladder in small passes, the one-lane ladder above; the finish shares one inversion between 1, 2, 4
+// or 8 items.  tests/test_gpu_x25519.py places low-order points in every slot of every lane group at exactly these sizes: a
+// retuning of the shapes must move the sizes of that test with it.
+constexpr bool x25519_ladder_is_quad(size_t n) { return n <= X25519_QUAD_MAX_N; }
+constexpr bool finish_is(const finish_shape& f, int k, unsigned grid) { return f.k == k && f.grid == grid; }
+static_assert(x25519_ladder_is_quad(X25519_QUAD_MAX_N) && !x25519_ladder_is_quad(X25519_QUAD_MAX_N + 1) && X25519_QUAD_MAX_N == 16384, "the one-lane ladder from 2^14 + 1 items on");
+static_assert(!x25519_ladder_is_quad(17229) && finish_is(finish_shape_of(17229), 1, 68), "one-lane ladder, K = 1");
+static_assert(finish_is(finish_shape_of(65536 + 2 * 256 + 77), 2, 130), "259 tiles: K = 2, the last block holds one tile");
+static_assert(finish_is(finish_shape_of(131072 + 256 + 77), 4, 129), "514 tiles: K = 4, the last block holds two tiles");
+static_assert(finish_is(finish_shape_of(262144 + 2 * 256 + 77), 8, 129), "1027 tiles: K = 8, the last block holds three tiles");
+
 // the point kernel of a pass of n items in the form its shape asks for (split: PARTS = POINT_SPLIT, whole: PARTS = 1); args: the
 // kernel's arguments without its last, the tile counter.  Unchecked like every fixed-base launch: the caller asks hipGetLastError
 template <class K, class... A>
@@ -1228,7 +1239,7 @@ hipError_t edk_init_tables(uint32_t* base16, uint32_t* comb, uint32_t* comb_img,
 hipError_t edk_x25519(uint8_t* out, const uint8_t* scalars, const uint8_t* points, size_t n, const edk_fixed_ws* ws, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   const finish_shape f = finish_shape_of(n);
-  if (n <= X25519_QUAD_MAX_N)
+  if (x25519_ladder_is_quad(n))
     hipLaunchKernelGGL(k_x25519_ladder_quad, dim3(blocks_of(4 * n)), dim3(BLOCK), 0, stream, ws->acc, scalars, points, n);
   else
     hipLaunchKernelGGL(k_x25519_ladder, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, ws->acc, scalars, points, n);

@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(BLOCK) k_debug_halve(uint8_t* out, const uint8
 // One lane per item; the four-lane forms below.  The op codes are those of the header.
 // ---------------------------------------------------------------------------------------------
 enum { L_FE_MUL = 1, L_FE_SQ, L_FE_INV, L_FE_POW2523, L_FE_MUL_LOOSE, L_SC_REDUCE32, L_SC_REDUCE64, L_SC_MULADD, L_SHA512,
-       L_ED_IMPORT_EXPORT, L_ED_SCALE_BASE, L_ED_DUAL_SCALE, L_GE_DBL_ADD };
+       L_ED_IMPORT_EXPORT, L_ED_SCALE_BASE, L_ED_DUAL_SCALE, L_GE_DBL_ADD, L_X25519_LADDER };
 
 ED_DEV void ldw(uint32_t w[8], const uint8_t* p) { load32(w, p, 0, 0); }
 ED_DEV void stw(uint8_t* p, const uint32_t w[8]) { store32(p, 0, 0, w); }
@@ -288,6 +288,37 @@ k_debug_dbl_add_quad(uint8_t* out, const uint8_t* in, size_t n, const uint32_t* 
   if (live && q == 1) store32(out, g, 32, wd);
 }
 
+// EDL_X25519_LADDER: (x2 : z2) as the ladder kernels leave it in the point workspace, here encoded - the one value of
+// X25519 that otherwise leaves the device only through the shared inversion of k_x25519_finish.
+// Form 0: lanes.h x25519_ladder_lane, a lane per item, as k_x25519_ladder runs it
+__global__ void __launch_bounds__(BLOCK, 4)
+k_debug_x25519_ladder(uint8_t* out, const uint8_t* in, size_t n) {
+  const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  uint32_t s[8], pt[8], w[8];
+  load32(s, in, i, 64);
+  load32(pt, in + 32, i, 64);
+  fe x2, z2;
+  x25519_ladder_lane(x2, z2, s, pt);
+  fe_tobytes(w, x2); store32(out, i, 64, w);
+  fe_tobytes(w, z2); store32(out + 32, i, 64, w);
+}
+// Form 1: quad_lanes.h x25519_ladder_quad, a quad per item; quads are all-or-nothing, as in k_x25519_ladder_quad
+__global__ void __launch_bounds__(QUAD_CHAIN_BLOCK, 2)
+k_debug_x25519_ladder_quad(uint8_t* out, const uint8_t* in, size_t n) {
+  const size_t g = ((size_t)blockIdx.x * QUAD_CHAIN_BLOCK + threadIdx.x) >> 2;
+  if (g >= n) return;
+  const int q = (int)(threadIdx.x & 3u);
+  uint32_t s[8], pt[8], w[8];
+  load32(s, in, g, 64);
+  load32(pt, in + 32, g, 64);
+  fe r;
+  x25519_ladder_quad(r, s, pt, q);
+  if (q > 1) return;                             // lane 0: x2, lane 1: z2
+  fe_tobytes(w, r);
+  store32(out + 32 * q, g, 64, w);
+}
+
 }  // namespace ed
 
 using namespace ed;
@@ -305,6 +336,7 @@ static int layer_widths_ok(int op, int form, size_t in_w, size_t out_w) {
     case L_ED_IMPORT_EXPORT: return form == 0 && in_w == 32 && out_w == 33;
     case L_ED_DUAL_SCALE: return in_w == 96 && out_w == 32;                         // forms 0..4
     case L_GE_DBL_ADD: return form <= 1 && in_w == 40 && out_w == 32;
+    case L_X25519_LADDER: return form <= 1 && in_w == 64 && out_w == 64;
   }
   return 0;
 }
@@ -323,6 +355,9 @@ static hipError_t layer_launch(int op, int form, uint8_t* out, size_t out_w, con
     hipLaunchKernelGGL(k_debug_dual_scale_quad, dim3(qblocks), dim3(QUAD_CHAIN_BLOCK), 0, stream, out, in, n, base16, (uint32_t*)scratch);
   } else if (op == L_GE_DBL_ADD && form == 1) {
     hipLaunchKernelGGL(k_debug_dbl_add_quad, dim3(qblocks), dim3(QUAD_CHAIN_BLOCK), 0, stream, out, in, n, base16);
+  } else if (op == L_X25519_LADDER) {
+    if (form == 1) hipLaunchKernelGGL(k_debug_x25519_ladder_quad, dim3(qblocks), dim3(QUAD_CHAIN_BLOCK), 0, stream, out, in, n);
+    else hipLaunchKernelGGL(k_debug_x25519_ladder, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, out, in, n);
   } else {
     if (op == L_ED_DUAL_SCALE && form == 2 && (e = hipMalloc(&scratch, n * LAYER_SCRATCH_BYTES)) != hipSuccess) return e;
     if (op == L_ED_DUAL_SCALE && form == 3 && (e = hipMalloc(&scratch, n * LAYER_TABLE_SCRATCH_BYTES)) != hipSuccess) return e;

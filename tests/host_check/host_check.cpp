@@ -63,6 +63,16 @@ void hc_x25519(uint8_t out[32], const uint8_t scalar[32], const uint8_t point[32
   wr(out, o);
 }
 
+// (x2 : z2) as the ladder leaves it, before the inversion: out = x2 32 | z2 32, canonical
+void hc_x25519_ladder(uint8_t out[64], const uint8_t scalar[32], const uint8_t point[32]) {
+  uint32_t s[8], p[8], o[8];
+  rd(s, scalar); rd(p, point);
+  fe x2, z2;
+  x25519_ladder_lane(x2, z2, s, p);
+  fe_tobytes(o, x2); wr(out, o);
+  fe_tobytes(o, z2); wr(out + 32, o);
+}
+
 // the three verify kernels for one item (the finish step without the cross-item batching, plus
 // the same Z = 0 / off-curve rule)
 int hc_verify(const uint8_t sig[64], const uint8_t pub[32], const uint8_t* msg, size_t len) {
