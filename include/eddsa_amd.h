@@ -62,6 +62,9 @@
  * Host memory: ordinary (malloc) memory is staged through page-locked buffers by a few copier threads
  * (eddsa_amd_set_host_threads); page-locked caller memory (eddsa_amd_host_alloc, hipHostMalloc,
  * hipHostRegister) is used in place.
+ * Strict verification: by default every verdict is the reference's permissive one (S is not range-checked, the key is not
+ * validated, points of order 1, 2, 4 and 8 pass as keys and as R).  The rules most strict verifiers add - S < l, a canonical
+ * key, no small-order key or R - are opt-in and process-wide: EDDSA_AMD_VERIFY_*, set through eddsa_amd_set_offcurve_mode.
  * Test and measurement hooks (fault injection, route selection, probes, traces) are NOT part of this contract: they are
  * declared in eddsa_amd_debug.h and inert unless a test arms them.
  * Secrets: the staging copies of secret keys / scalars / shared secrets and the secret scalars that
@@ -136,7 +139,39 @@ EDDSA_AMD_DECL const char *eddsa_amd_strerror(int err);
  * they are rejected outright, which differs from the reference only on a SHA-512 fixed point and
  * saves about 1 ms per pass that contains such keys.  exact == 2: EVERY item is evaluated in the
  * reference's order of operations (JSF/Shamir chain, lib/ed.c:455-507) and the windowed kernel's
- * result is ignored -- same verdicts, latency-bound, meant for self-checks. */
+ * result is ignored -- same verdicts, latency-bound, meant for self-checks.
+ *
+ * The same word carries the OPT-IN STRICT RULES in its bits 8-11 (EDDSA_AMD_VERIFY_POLICY_MASK): the call stores
+ * exact & EDDSA_AMD_VERIFY_POLICY_MASK as the process-wide verify policy and reads the mode above from
+ * exact & ~EDDSA_AMD_VERIFY_POLICY_MASK (2 -> 2, otherwise non-zero -> 1), both under one lock.  0, 1 and 2 therefore mean
+ * what they always meant, with policy 0; a value with some of bits 8-11 set, -1 among them, used to mean "exact" and now
+ * means "exact plus those rules" (-1: exact and EDDSA_AMD_VERIFY_STRICT).  Policy 0 is the default and is the reference's
+ * verdict, byte for byte; no kernel is added to any pass.  The rules: */
+#define EDDSA_AMD_VERIFY_S_BELOW_L     0x100   /* reject unless sig[32..64), little-endian, is < l (RFC 8032 5.1.7; S + k l is a
+                                                  second encoding of the same signature) */
+#define EDDSA_AMD_VERIFY_A_CANONICAL   0x200   /* reject unless the key is an encoding RFC 8032 5.1.3 decodes: y (the low 255 bits)
+                                                  < p, (y^2 - 1) / (d y^2 + 1) a square, and not x = 0 with the sign bit set */
+#define EDDSA_AMD_VERIFY_A_NOT_SMALL   0x400   /* reject a key with y mod p in {0, 1, -1, y8, -y8}: the eight points of order 1, 2,
+                                                  4 and 8 in every encoding, the non-canonical ones included (each of these y is on
+                                                  the curve, so y alone decides) */
+#define EDDSA_AMD_VERIFY_R_NOT_SMALL   0x800   /* the same test on sig[0..32) */
+#define EDDSA_AMD_VERIFY_STRICT        0xF00   /* all four */
+#define EDDSA_AMD_VERIFY_POLICY_MASK   0xF00
+/* The verdict of an item under policy P is (the reference's verdict for the item) AND (every predicate whose bit is in P): a
+ * policy only ever turns accepts into rejects.  It holds for EVERY form of verification in the process - the thirteen names of
+ * eddsa.h, the batched, records, digest, _rlc, _multi and device-pointer forms - so a program linked against the reference's
+ * library makes one call at start-up, eddsa_amd_set_offcurve_mode(1 | EDDSA_AMD_VERIFY_STRICT), and changes no call site.  A call
+ * uses the policy in force when each of its passes is enqueued, like the off-curve mode.
+ * There is no R_CANONICAL bit because none is needed: an accepted R equals, byte for byte, what the reference's export step
+ * wrote, and that has y < p and the sign bit of its x.  With A_CANONICAL an accepted item is thus made of canonical encodings
+ * of curve points only.
+ * The opt-in batch verification (ed25519_verify_batch_rlc) keeps its documented caveat under every policy: the rules reject
+ * points OF small order, and a point of mixed order (a small-order component on a prime-order point) is not one of those.
+ * The rules are one more kernel behind each pass's verdicts (it reads 96 bytes of an accepted item; A_CANONICAL decodes the key
+ * once more).  Measured (profiles/verify_policy.txt, tools/policy_cost.py: ed25519_verify_batch_dev, 2^20 valid items in HBM,
+ * 32-byte messages, one MI355X): policy 0 9.39 ms per pass, S_BELOW_L 9.44 (+0.5 %), A_NOT_SMALL 9.44 (+0.5 %), R_NOT_SMALL 9.47
+ * (+0.8 %), A_CANONICAL 10.23 (+8.9 %), STRICT 10.24 (+9.0 %: 102 M instead of 112 M verifies/s).  Policy 0 against the commit
+ * before the rules, alternating on that box: 9.42-9.46 ms against 9.41-9.47 ms - inside the older build's own repeat spread. */
 EDDSA_AMD_DECL void eddsa_amd_set_offcurve_mode(int exact);
 EDDSA_AMD_DECL void eddsa_amd_set_rlc_min_items(size_t items);   /* see ed25519_verify_batch_rlc */
 /* ---- host-pointer entry points ---- */
@@ -182,7 +217,7 @@ EDDSA_AMD_DECL int ed25519_verify_batch_rlc(uint8_t *ok, uint32_t stats[4], cons
  * alignment required.  Item i is accepted exactly when the reference's ed25519_verify accepts (sigs[i], pubs[i], M) for an M
  * with SHA-512(R_i || A_i || M) = digests[i].  The digest's only use is t = (the 64 bytes as a little-endian integer) mod l,
  * the sc_import(t, h, 64) of lib/ed25519-sha512.c:171; any 64 bytes are legal input.  Everything else is ed25519_verify_batch's,
- * byte for byte: S is not range-checked, off-curve keys follow eddsa_amd_set_offcurve_mode, EDDSA_AMD_STALLED is reported as
+ * byte for byte: S is not range-checked, off-curve keys and the strict rules follow eddsa_amd_set_offcurve_mode, EDDSA_AMD_STALLED is reported as
  * there; return values, ownership, device selection, threading and page-locked memory follow the rules at the top.
  * THE CALLER VOUCHES that digests[i] was computed over the R bytes (sigs[i][0..32)) and the A bytes (pubs[i]) of THIS call,
  * followed by the message.  A digest computed over other bytes verifies a different statement, and the library cannot tell:

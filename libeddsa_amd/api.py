@@ -202,11 +202,42 @@ def verify_phase_ms():
     return tuple(out)
 
 
+# the opt-in strict rules of verification: include/eddsa_amd.h, EDDSA_AMD_VERIFY_*
+VERIFY_S_BELOW_L = 0x100
+VERIFY_A_CANONICAL = 0x200
+VERIFY_A_NOT_SMALL = 0x400
+VERIFY_R_NOT_SMALL = 0x800
+VERIFY_STRICT = 0xF00
+_VERIFY_POLICY_MASK = 0xF00
+# the two halves of the word eddsa_amd_set_offcurve_mode takes: each setter remembers its own and sends both
+_offcurve_mode = 1
+_verify_policy = 0
+
+
+def _send_mode_word():
+    library().eddsa_amd_set_offcurve_mode(_offcurve_mode | _verify_policy)
+
+
 def set_offcurve_mode(exact=True):
     """exact=True (default): off-curve public keys are verified in the reference's own operation
     order; False: they are rejected outright (differs only on a SHA-512 fixed point); 2: every item
-    takes the reference-order path (self-check mode, slow)."""
-    library().eddsa_amd_set_offcurve_mode(2 if exact == 2 else int(bool(exact)))
+    takes the reference-order path (self-check mode, slow).  The verify policy (set_verify_policy) stays as it is."""
+    global _offcurve_mode
+    _offcurve_mode = 2 if exact == 2 else int(bool(exact))
+    _send_mode_word()
+
+
+def set_verify_policy(policy=0):
+    """the opt-in strict rules every form of verification applies from now on, process-wide: an OR of VERIFY_S_BELOW_L (S < l),
+    VERIFY_A_CANONICAL (the key is an encoding RFC 8032 5.1.3 decodes), VERIFY_A_NOT_SMALL / VERIFY_R_NOT_SMALL (no key / R of
+    order 1, 2, 4 or 8); VERIFY_STRICT = all four; 0 (default) = the reference's verdicts.  A policy only turns accepts into
+    rejects.  ValueError for any other bit; the off-curve mode (set_offcurve_mode) stays as it is."""
+    global _verify_policy
+    policy = int(policy)
+    if policy & ~_VERIFY_POLICY_MASK:
+        raise ValueError(f"set_verify_policy: {policy:#x} has bits outside VERIFY_STRICT ({_VERIFY_POLICY_MASK:#x})")
+    _verify_policy = policy
+    _send_mode_word()
 
 
 def set_verify_algo(algo=0):

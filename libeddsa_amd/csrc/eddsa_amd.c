@@ -23,6 +23,7 @@ struct engine *g_eng[MAX_DEVICES];
 static int g_default = -1;            /* device of the host-pointer entry points; -1: the caller's current device at first use */
 static int g_verify_algo = 0;         /* eddsa_amd_set_verify_algo: 0 by pass size (default), 1 full-length windows, 2 half-length scalars */
 static int g_offcurve_mode = 1;       /* eddsa_amd_set_offcurve_mode: 0 reject, 1 exact (default), 2 all exact */
+static int g_verify_policy;           /* the EDDSA_AMD_VERIFY_* bits of the same word (default 0: the reference's verdicts) */
 static int g_profiling;               /* record marks around the three verify kernels */
 static size_t g_rlc_min_items = EDDSA_AMD_RLC_MIN_ITEMS_DEFAULT;   /* eddsa_amd_set_rlc_min_items: smaller calls go to the per-item kernels */
 
@@ -403,11 +404,14 @@ void eddsa_amd_shutdown(void)
  * rejected outright; this differs from the reference only if encode(C) == R for a C that depends on
  * SHA-512(R || A || M), i.e. on a fixed point of a random function, and saves the ~1 ms the exact
  * pass costs whenever a batch contains such keys.  ALL (2): every item takes the reference-order
- * path and the windowed evaluation's result is ignored -- slow (latency-bound), for self-checks. */
+ * path and the windowed evaluation's result is ignored -- slow (latency-bound), for self-checks.
+ * Bits 8-11 of the word (EDDSA_AMD_VERIFY_POLICY_MASK) are the opt-in strict rules; the mode is what the other bits say. */
 void eddsa_amd_set_offcurve_mode(int exact)
 {
     pthread_rwlock_wrlock(&g_table);
-    g_offcurve_mode = exact == 2 ? 2 : exact != 0;
+    const int mode = exact & ~EDDSA_AMD_VERIFY_POLICY_MASK;
+    g_offcurve_mode = mode == 2 ? 2 : mode != 0;
+    g_verify_policy = exact & EDDSA_AMD_VERIFY_POLICY_MASK;
     pthread_rwlock_unlock(&g_table);
 }
 
@@ -478,6 +482,7 @@ static edk_verify_src src_at(const edk_verify_src *all, size_t n, size_t done)
     src.sigs += done * all->sig_stride;
     src.pubs += done * all->pub_stride;
     if (all->msg_off) src.msg_off += done; else src.msgs += done * all->msg_stride;
+    src.policy = g_verify_policy;   /* read where the pass is enqueued, like g_offcurve_mode */
     return src;
 }
 
@@ -643,7 +648,7 @@ static int leave_with(struct call *c, int rc) { leave(c); return rc; }
 int ed25519_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs,
                              const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0 };
+    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0 };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -662,7 +667,7 @@ int ed25519_verify_records_dev(uint8_t *ok, const uint8_t *records, size_t strid
 {
     if (!records_ok(stride, sig_off, pub_off, msg_off, msg_len)) return -(int)hipErrorInvalidValue;
     const edk_verify_src src = { records + sig_off, records + pub_off, records + msg_off, NULL, msg_len,
-                                 stride, stride, stride, NULL, 0 };
+                                 stride, stride, stride, NULL, 0, 0 };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -672,7 +677,7 @@ int ed25519_verify_records_dev(uint8_t *ok, const uint8_t *records, size_t strid
 int ed25519_verify_batch_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *sigs, const uint8_t *pubs,
                                  const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0 };
+    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0 };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -683,7 +688,7 @@ int ed25519_verify_batch_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *si
  * message slot and the flag that selects the kernels that do not hash */
 int ed25519_verify_digests_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1 };
+    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1, 0 };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -693,7 +698,7 @@ int ed25519_verify_digests_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *
 int ed25519_verify_digests_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests,
                                    size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1 };
+    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1, 0 };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -851,7 +856,7 @@ int ed25519_verify_batch_multi_dev(uint8_t *const ok_full[], const uint8_t *cons
         size_t lo, hi;
         eddsa_amd_shard_bounds(n_total, d, g, &lo, &hi);
         if (hi - lo != n_total / (size_t)g) even = 0;
-        const edk_verify_src src = { sigs[d], pubs[d], msgs[d], NULL, msg_len, 64, 32, msg_len, NULL, 0 };
+        const edk_verify_src src = { sigs[d], pubs[d], msgs[d], NULL, msg_len, 64, 32, msg_len, NULL, 0, 0 };
         TRY(hipSetDevice(g_multi.dev[d]));
         rc = verify_on(g_eng[g_multi.dev[d]], ok_full[d] + lo, &src, hi - lo, (hipStream_t)streams[d], NULL, 0);
     }

@@ -60,6 +60,9 @@ typedef struct {
                                 item's span is clamped into it (lanes.h: msg_span).  verify_on / rlc_on fill it in. */
   int digest;                /* != 0 (ed25519_verify_digests*): the message slot holds the caller's SHA-512(R || A || M), 64 bytes per
                                 item (msg_len 64, no offset table); the hashing kernels' digest forms take t from it unhashed */
+  int policy;                /* the EDDSA_AMD_VERIFY_* bits in force (include/eddsa_amd.h), 0 = none: != 0 adds k_verify_policy behind the
+                                pass's verdicts (kernels.hip).  Filled in by src_at (eddsa_amd.c) for verify_on / rlc_on alike; initialisers
+                                that stop at `digest` leave it 0.  Host side only, like `digest` */
 } edk_verify_src;
 
 /* What the kernels take BY VALUE: the nine fields of edk_verify_src that lanes read, 72 bytes as before the flag existed.  The flag stays

@@ -7,6 +7,11 @@
 #include <hip/hip_runtime.h>
 
 extern "C" int edk_fault_tick(void);   // kernels.hip: 1 when the armed fault falls on this call
+// kernels.hip: k_verify_policy over the n verdicts ok[] of a pass (include/eddsa_amd.h: EDDSA_AMD_VERIFY_*), one checked launch;
+// policy 0 queues nothing.  Shared by edk_verify and edk_verify_rlc, which is why it is declared here and not in eddsa_kernels.h:
+// the host library never calls it.
+extern "C" hipError_t verify_policy_launch(uint8_t* ok, const uint8_t* sigs, size_t sig_stride, const uint8_t* pubs, size_t pub_stride,
+                                           size_t n, int policy, hipStream_t stream);
 
 #define EDK_DO(expr) do { if (edk_fault_tick()) return hipErrorUnknown; \
     const hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)

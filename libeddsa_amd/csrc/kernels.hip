@@ -19,7 +19,9 @@
 #include "edk_checked.h"
 #include "kernel_io.h"
 #include "lanes.h"
+#include "policy_lanes.h"
 #include "quad_lanes.h"
+#include "eddsa_amd.h"
 
 #include <atomic>
 
@@ -643,6 +645,23 @@ __global__ void __launch_bounds__(BLOCK, 2)
 k_verify_finish(uint8_t* ok, const uint8_t* sigs, size_t sig_stride, uint32_t* acc, uint8_t* flags, size_t n,
                 int exact_offcurve, int K) {
   finish_batch8(verify_finish_policy{ok, sigs, sig_stride, acc, flags, n, exact_offcurve, K}, acc);
+}
+
+// The opt-in strict rules (include/eddsa_amd.h: EDDSA_AMD_VERIFY_*; policy_lanes.h: verify_policy_lane) as a pass of their own
+// behind every writer of ok[]: an item the pass accepted is rejected when a predicate of `policy` fails on its bytes.  It never
+// writes a 1 and reads nothing of the workspace, so it cannot turn a verdict of the kernels before it into an accept.
+static_assert(POLICY_S_BELOW_L == EDDSA_AMD_VERIFY_S_BELOW_L && POLICY_A_CANONICAL == EDDSA_AMD_VERIFY_A_CANONICAL &&
+              POLICY_A_NOT_SMALL == EDDSA_AMD_VERIFY_A_NOT_SMALL && POLICY_R_NOT_SMALL == EDDSA_AMD_VERIFY_R_NOT_SMALL &&
+              EDDSA_AMD_VERIFY_STRICT == (POLICY_S_BELOW_L | POLICY_A_CANONICAL | POLICY_A_NOT_SMALL | POLICY_R_NOT_SMALL), "the lane's bits are the header's");
+__global__ void __launch_bounds__(BLOCK)
+k_verify_policy(uint8_t* ok, const uint8_t* sigs, size_t sig_stride, const uint8_t* pubs, size_t pub_stride, size_t n, unsigned policy) {
+  const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n || ok[i] == 0) return;
+  uint32_t rw[8], sw[8], aw[8];
+  load32(rw, sigs, i, sig_stride);
+  load32(sw, sigs + 32, i, sig_stride);
+  load32(aw, pubs, i, pub_stride);
+  if (!verify_policy_lane(rw, sw, aw, policy)) ok[i] = 0;
 }
 
 // x25519.c:144-149: x2 / z2, and 0 when z2 = 0 (fld_inv(0) = 0): such an item contributes 1 to the
@@ -1287,6 +1306,14 @@ hipError_t edk_msg_order(const uint32_t** perm, const edk_verify_ws* ws, const u
   return msg_order(perm, ws->perm, ws->lenbins, msg_off, msg_end, n, stream);
 }
 
+// the strict rules over the n verdicts of a pass (edk_checked.h; rlc.hip launches it too); policy 0: nothing is queued
+hipError_t verify_policy_launch(uint8_t* ok, const uint8_t* sigs, size_t sig_stride, const uint8_t* pubs, size_t pub_stride, size_t n,
+                                int policy, hipStream_t stream) {
+  if (policy == 0 || n == 0) return hipSuccess;
+  EDK_LAUNCH(k_verify_policy, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, ok, sigs, sig_stride, pubs, pub_stride, n, (unsigned)policy);
+  return hipSuccess;
+}
+
 // Every HIP call below that orders work or moves data is checked (edk_checked.h): the first failure ends the pass with
 // that error.  What has been queued by then still runs; eddsa_amd.c: verify_on waits for it (both streams) before the
 // workspace can be handed out again, and the caller learns that the outputs are unspecified.
@@ -1374,7 +1401,8 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
   if (bulk_done && !bulk_early) EDK_DO(hipEventRecord(bulk_done, stream));
   // 7. the join: complete when both paths are
   if (ws->exact_offcurve) EDK_DO(hipStreamWaitEvent(stream, ws->ev_exact, 0));
-  return hipSuccess;
+  // 8. the opt-in strict rules, behind every writer of ok[] on both streams (nothing is queued for policy 0)
+  return verify_policy_launch(ok, src.sigs, src.sig_stride, src.pubs, src.pub_stride, n, src.policy, stream);
 }
 
 hipError_t edk_genpub(uint8_t* pubs, const uint8_t* secs, size_t n, const uint32_t* comb, const edk_fixed_ws* ws, hipStream_t stream) {

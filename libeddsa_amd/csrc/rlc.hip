@@ -671,6 +671,9 @@ extern "C" hipError_t edk_verify_rlc(uint8_t* ok, uint32_t* stats, const edk_ver
   EDK_LAUNCH(k_rlc_final, dim3((unsigned)((groups + RLC_HORNER_GROUPS - 1) / RLC_HORNER_GROUPS)), dim3(4 * RLC_HORNER_GROUPS), 0, stream,
              n, segpts, gflags, gok, stats);
   EDK_LAUNCH(k_rlc_verdicts, dim3(blocks), dim3(RLC_BLOCK), 0, stream, n, gok, flags, ok);
+  // the opt-in strict rules over all n items (kernels.hip: k_verify_policy; nothing is queued for policy 0).  An item of a group
+  // that edk_verify_rlc_fallback decides again meets them there a second time, which changes nothing
+  if ((e = verify_policy_launch(ok, src.sigs, src.sig_stride, src.pubs, src.pub_stride, n, src.policy, stream)) != hipSuccess) return e;
 
   // groups the combination did not accept: the per-item kernels decide (edk_verify_rlc_fallback).  This is the
   // one place where the host looks at a result: the caller synchronises the stream once per pass.

@@ -7,6 +7,7 @@
 // bucket sums, scans) exist only in rlc.hip and are covered by the GPU tests.
 #pragma once
 #include "lanes.h"
+#include "policy_lanes.h"
 
 namespace ed {
 
@@ -19,24 +20,8 @@ ED_DEV bool ge_is_neutral(const ge& p) {
   fe_sub(d, p.Y, p.Z);
   return fe_iszero(p.X) && fe_iszero(d);
 }
-// Is the curve point p (Z = 1) one of the eight points of order dividing 8?  Those are exactly the points
-// with y in {0, 1, -1, y8, -y8} (y8 = the y of a point of order 8), so five comparisons of the canonical y
-// replace three doublings and a neutrality test.
-ED_DEV bool ge_small_order(const ge& p) {
-  constexpr uint32_t Y8[10] = {60155942, 32288931, 6862340, 26496934, 63071167, 28106709, 31680898, 18229030, 47743011, 1569101};
-  constexpr uint32_t Y8N[10] = {6952903, 1265500, 60246523, 7057497, 4037696, 5447722, 35427965, 15325401, 19365852, 31985330};
-  fe t;
-  fe_canon(t, p.Y);
-  uint32_t rest = 0, m1 = 0, d8 = 0, d8n = 0;
-#pragma unroll
-  for (int i = 0; i < 10; i++) {
-    if (i) rest |= t.v[i];
-    m1 |= t.v[i] ^ (i == 0 ? M26 - 19 : limb_mask(i));      // p - 1
-    d8 |= t.v[i] ^ Y8[i];
-    d8n |= t.v[i] ^ Y8N[i];
-  }
-  return (rest == 0 && t.v[0] <= 1u) || m1 == 0 || d8 == 0 || d8n == 0;
-}
+// Is the curve point p (Z = 1) one of the eight points of order dividing 8?  (policy_lanes.h: the five values of y)
+ED_DEV bool ge_small_order(const ge& p) { return fe_small_order_y(p.Y); }
 ED_DEV void niels_of_affine(ge_niels& n, const ge& p) {   // p.Z = 1: ed.c:436-442 ed_precompute
   fe_sub(n.ymx, p.Y, p.X); fe_carry(n.ymx);
   fe_add(n.ypx, p.Y, p.X); fe_carry(n.ypx);
@@ -58,13 +43,12 @@ ED_DEV uint8_t rlc_decode_key_lane(ge_niels& nl, const uint32_t aw[8]) {
 // writes (ed.c:155-169: y < p, sign bit = parity of x), so anything else is rejected outright (flag
 // RLC_R_VALID clear); a valid R of small order sends its group to the per-item kernels.
 ED_DEV uint8_t rlc_decode_r_lane(ge_niels& nl, const uint32_t rw[8]) {
-  const uint32_t sign = rw[7] >> 31, top = rw[7] & 0x7fffffffu;
-  const bool y_ge_p = top == 0x7fffffffu && (rw[1] & rw[2] & rw[3] & rw[4] & rw[5] & rw[6]) == 0xffffffffu &&
-                      rw[0] >= 0xffffffedu;
+  const uint32_t sign = rw[7] >> 31;
+  const bool y_ge_p = encoding_y_ge_p(rw);
   ge p;
   bool oncurve;
   ge_frombytes(p, oncurve, rw, true);
-  const bool valid = oncurve && !y_ge_p && !(sign != 0 && fe_iszero(p.X));
+  const bool valid = decoded_canonical(y_ge_p, sign, p, oncurve);
   uint8_t fl = 0;
   if (valid) {
     fl |= RLC_R_VALID;
@@ -99,12 +83,6 @@ ED_DEV void rlc_hash_lane(uint32_t tw[8], uint32_t sw[8], uint32_t leaf[8], cons
   rlc_digest_lane(tw, sw, leaf, dig, s_bytes);
 }
 
-// l as eight little-endian words
-ED_DEV constexpr uint32_t rlc_L(int i) {
-  constexpr uint32_t Lw[8] = {0x5cf5d3edu, 0x5812631au, 0xa2f79cd6u, 0x14def9deu, 0x00000000u, 0x00000000u, 0x00000000u, 0x10000000u};
-  return Lw[i];
-}
-
 // The key's scalar as an integer a' with |a'| <= 4 l and a' = z t (mod 8 l), from a0 = z t mod l: A may carry a
 // component of order dividing 8 (the reference checks neither subgroup membership nor small order), on
 // which z t and z t mod l act differently, so the class mod l alone does not determine a'*A.  z t = a0 + k l with
@@ -119,7 +97,7 @@ ED_DEV bool rlc_key_scalar_mod_8l(uint32_t mag[8], const uint32_t a0[8], uint32_
   int64_t c = 0;
 #pragma unroll
   for (int q = 0; q < 8; q++) {
-    p += (uint64_t)kk * rlc_L(q);
+    p += (uint64_t)kk * l_word(q);
     c += (int64_t)(uint32_t)p + (neg ? -(int64_t)a0[q] : (int64_t)a0[q]);
     mag[q] = (uint32_t)c;
     c >>= 32;
