@@ -12,6 +12,9 @@
  *   ed25519_verify_digests the same loop for callers that already hold SHA-512(R || A || M): 64 digest bytes per item instead
  *                          of the message (also _rlc, _multi and the device-pointer forms; see the declarations)
  *   ed25519_sign_batch     loop of ed25519_sign          reference lib/eddsa.h:47
+ *   ed25519ctx_sign_batch / ed25519ctx_verify_batch, ed25519ph_sign_batch / ed25519ph_verify_batch   the two other variants of
+ *                          RFC 8032 (a context; for ph the caller's SHA-512 prehash instead of the message): the reference has
+ *                          no such functions, the semantics are stated at the declarations
  *   ed25519_genpub_batch   loop of ed25519_genpub        reference lib/eddsa.h:44
  *   x25519_batch           loop of x25519                reference lib/eddsa.h:67
  *   x25519_base_batch      loop of x25519_base           reference lib/eddsa.h:64
@@ -267,6 +270,65 @@ EDDSA_AMD_DECL int x25519_batch_dev(uint8_t *out, const uint8_t *scalars, const 
 EDDSA_AMD_DECL int x25519_base_batch_dev(uint8_t *out, const uint8_t *scalars, size_t n, void *stream);
 EDDSA_AMD_DECL int pk_ed25519_to_x25519_batch_dev(uint8_t *out, const uint8_t *in, size_t n, void *stream);
 EDDSA_AMD_DECL int sk_ed25519_to_x25519_batch_dev(uint8_t *out, const uint8_t *in, size_t n, void *stream);
+
+/* ---- Ed25519ctx and Ed25519ph: the two other variants of RFC 8032 (section 5.1), batched ----
+ * Both are Ed25519 with dom2(F, C) = "SigEd25519 no Ed25519 collisions" (32 ASCII bytes) || F || len(C) || C in front of the two
+ * hashes that see the message (RFC 8032 section 2), C a context of 0..255 bytes:
+ *   sign     h = SHA-512(sk), clamped as in ed25519_sign_batch;  r = SHA-512(dom2 || h[32..64) || M') mod l;  R = r B;
+ *            t = SHA-512(dom2 || R || A || M') mod l;  S = r + t a       (reference lib/ed25519-sha512.c:84-122 with the prefix)
+ *   verify   item i is accepted exactly when ed25519_verify_digests accepts (sigs[i], pubs[i], SHA-512(dom2 || R || A || M')):
+ *            the reference's permissive check with t from the prefixed hash.  The off-curve mode and the strict rules of
+ *            eddsa_amd_set_offcurve_mode apply unchanged, EDDSA_AMD_STALLED is reported as for every verify form.
+ *   Ed25519ctx  F = 0, M' = the message (fixed-length or ragged, as in ed25519_sign_batch / ed25519_verify_batch).
+ *   Ed25519ph   F = 1, M' = SHA-512(M): THE CALLER supplies these 64 bytes per item (prehashes: packed, any alignment, what
+ *               hashlib.sha512(M).digest() returns) and the library never sees M.  A signer or verifier of large objects hashes
+ *               each object once, wherever its bytes stream by; the device then spends three to five SHA-512 blocks on an item
+ *               whatever the size of M, where ed25519_sign_batch hashes M twice at 10-13 MB/s per lane and cannot be handed a
+ *               digest (r needs the secret prefix).  The ph forms are the ctx forms with F = 1, msg_len 64 and no offset table.
+ * context: a HOST pointer in every form, the device-pointer ones too; one context per call; it is copied during the call and
+ * may be freed on return.  NULL is allowed with context_len 0.  An empty context is legal under both flags - RFC 8032 says
+ * a context SHOULD NOT be empty for Ed25519ctx - and dom2(0, "") is still not plain Ed25519: the three variants never accept
+ * one another's signatures.  context_len > 255 returns -hipErrorInvalidValue before anything is touched.
+ * Everything else - layout, ragged-table rules and clamping, return values, device selection, ownership, threading, page-locked
+ * memory, the wiping of secrets - follows the rules at the top.  Host-pointer calls go through the staging pipeline and are
+ * never merged by the small-call combiner (two calls may carry different contexts).  Out of scope: _rlc, _multi and records
+ * forms, and single-item convenience names.
+ * Measured (profiles/dom2.txt, tools/dom2_rate.py: device-pointer forms, 2^20 valid items in HBM, a 3-byte context, one MI355X,
+ * the forms alternating): verify 9.65 ms per pass as Ed25519 over 32-byte messages, 9.84 ms as Ed25519ctx over the same (+2.0 %),
+ * 9.86 ms as Ed25519ph over 64-byte prehashes (+2.2 %); sign 2.21 / 2.36 (+7 %) / 2.49 ms (+13 %: two more SHA-512 blocks per item
+ * than a 32-byte Ed25519 message needs).  What the ph form is for: 2^16 items of which one in 1024 is 1 MiB take ed25519_sign_batch_dev
+ * 124 ms and ed25519ph_sign_batch_dev 0.275 ms on their prehashes - the caller's own hashing of the objects not included.
+ * (Declared with a macro of their own, the same attribute: tests of earlier additions count the EDDSA_AMD_DECL names above.) */
+#if defined(__GNUC__) && defined(EDDSA_BUILD)
+#define RFC8032_EDDSA_DECL __attribute__((visibility("default")))
+#else
+#define RFC8032_EDDSA_DECL
+#endif
+RFC8032_EDDSA_DECL int ed25519ctx_sign_batch(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
+                                             const uint64_t *msg_off, size_t msg_len, size_t n,
+                                             const uint8_t *context, size_t context_len);
+RFC8032_EDDSA_DECL int ed25519ctx_verify_batch(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs,
+                                               const uint64_t *msg_off, size_t msg_len, size_t n,
+                                               const uint8_t *context, size_t context_len);
+RFC8032_EDDSA_DECL int ed25519ph_sign_batch(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs,
+                                            const uint8_t *prehashes /* 64 bytes per item */, size_t n,
+                                            const uint8_t *context, size_t context_len);
+RFC8032_EDDSA_DECL int ed25519ph_verify_batch(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs,
+                                              const uint8_t *prehashes /* 64 bytes per item */, size_t n,
+                                              const uint8_t *context, size_t context_len);
+/* device pointers (the context stays a host pointer): enqueue on `stream` and return */
+RFC8032_EDDSA_DECL int ed25519ctx_sign_batch_dev(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
+                                                 const uint64_t *msg_off, size_t msg_len, size_t n,
+                                                 const uint8_t *context, size_t context_len, void *stream);
+RFC8032_EDDSA_DECL int ed25519ctx_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs,
+                                                   const uint64_t *msg_off, size_t msg_len, size_t n,
+                                                   const uint8_t *context, size_t context_len, void *stream);
+RFC8032_EDDSA_DECL int ed25519ph_sign_batch_dev(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs,
+                                                const uint8_t *prehashes, size_t n,
+                                                const uint8_t *context, size_t context_len, void *stream);
+RFC8032_EDDSA_DECL int ed25519ph_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs,
+                                                  const uint8_t *prehashes, size_t n,
+                                                  const uint8_t *context, size_t context_len, void *stream);
 
 #ifdef __cplusplus
 }

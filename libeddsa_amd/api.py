@@ -598,6 +598,90 @@ def ed25519_sign_batch(secs, pubs, msgs, msg_off=None, msg_len=None):
 
 
 # ---------------------------------------------------------------------------------------------
+# Ed25519ctx and Ed25519ph (RFC 8032 5.1; include/eddsa_amd.h): a context of 0..255 bytes, always host bytes
+# ---------------------------------------------------------------------------------------------
+
+CONTEXT_MAX = 255
+PREHASH_BYTES = 64
+
+
+def _context(context):
+    """-> the context as bytes; ValueError for more than CONTEXT_MAX bytes (before the library is called)"""
+    if context is None:
+        context = b""
+    context = bytes(context)
+    if len(context) > CONTEXT_MAX:
+        raise ValueError(f"context: {len(context)} bytes, RFC 8032 allows at most {CONTEXT_MAX}")
+    return context
+
+
+def _run_dom(name, first, first_w, first_name, pubs, msgs, msg_off, msg_len, out_shape, context, prehashed):
+    """common driver of the four calls: `first` (sigs or secs), pubs and msgs (prehashed: 64 bytes per item, no offsets) under
+    `context` -> (n,) + out_shape uint8.  numpy / bytes: the host form `name`; CUDA tensors: `name`_dev on torch's stream."""
+    context = _context(context)
+    ctx_args = [ctypes.c_char_p(context), _c_size(len(context))]
+    on_device = _is_torch(first)
+    if on_device:
+        import torch
+        first = _torch_check(first, first_w, first_name); pubs = _torch_check(pubs, 32, "pubs")
+        msgs = _torch_check(msgs, PREHASH_BYTES if prehashed else 0, "prehashes" if prehashed else "msgs")
+        n = first.numel() // first_w
+        total = msgs.numel()
+    else:
+        first = _as_np(first, first_w, first_name); pubs = _as_np(pubs, 32, "pubs")
+        msgs = _as_np(msgs, PREHASH_BYTES if prehashed else 0, "prehashes" if prehashed else "msgs")
+        n = first.size // first_w
+        total = msgs.size
+    if (pubs.numel() if on_device else pubs.size) // 32 != n:
+        raise ValueError(f"{name}: {first_name} and pubs disagree on the batch size")
+    if prehashed and total != PREHASH_BYTES * n:
+        raise ValueError(f"{name}: prehashes holds {total // PREHASH_BYTES} items of {PREHASH_BYTES} bytes, expected {n}")
+    lib = library()
+    if on_device:
+        off, mlen = None, PREHASH_BYTES
+        if not prehashed:
+            _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, True)
+            _torch_off_check(off, n)
+        out = torch.empty((n,) + out_shape, dtype=torch.uint8, device=first.device)
+        args = [_c_ptr(t.data_ptr()) for t in (out, first, pubs, msgs)]
+        if not prehashed:
+            args += [_c_ptr(off.data_ptr()) if off is not None else None, _c_size(mlen)]
+        _check(getattr(lib, name + "_dev")(*args, _c_size(n), *ctx_args, _stream()), name)
+        return out
+    off, mlen = None, PREHASH_BYTES
+    if not prehashed:
+        msgs, off, mlen = _host_msgs(msgs, msg_off, msg_len, n)
+    out = np.zeros((n,) + out_shape, dtype=np.uint8)
+    args = [_np_ptr(out), _np_ptr(first), _np_ptr(pubs), _np_ptr(msgs)]
+    if not prehashed:
+        args += [_np_ptr(off) if off is not None else None, _c_size(mlen)]
+    _check(getattr(lib, name)(*args, _c_size(n), *ctx_args), name)
+    return out
+
+
+def ed25519ctx_sign_batch(secs, pubs, msgs, context, msg_off=None, msg_len=None):
+    """Ed25519ctx signatures (RFC 8032 5.1, dom2 flag 0) of the messages under `context` (bytes, 0..255) -> (n, 64) uint8;
+    messages as in ed25519_sign_batch"""
+    return _run_dom("ed25519ctx_sign_batch", secs, 32, "secs", pubs, msgs, msg_off, msg_len, (64,), context, False)
+
+
+def ed25519ctx_verify_batch(sigs, pubs, msgs, context, msg_off=None, msg_len=None):
+    """Ed25519ctx verdicts -> (n,) uint8, 1 = accept; the off-curve mode and the verify policy apply as in ed25519_verify_batch"""
+    return _run_dom("ed25519ctx_verify_batch", sigs, 64, "sigs", pubs, msgs, msg_off, msg_len, (), context, False)
+
+
+def ed25519ph_sign_batch(secs, pubs, prehashes, context=b""):
+    """Ed25519ph signatures (dom2 flag 1) over caller-supplied prehashes[i] = SHA-512(M_i), 64 bytes per item as
+    hashlib.sha512(M).digest() returns them: the library never sees M -> (n, 64) uint8"""
+    return _run_dom("ed25519ph_sign_batch", secs, 32, "secs", pubs, prehashes, None, None, (64,), context, True)
+
+
+def ed25519ph_verify_batch(sigs, pubs, prehashes, context=b""):
+    """Ed25519ph verdicts over caller-supplied prehashes (see ed25519ph_sign_batch) -> (n,) uint8, 1 = accept"""
+    return _run_dom("ed25519ph_verify_batch", sigs, 64, "sigs", pubs, prehashes, None, None, (), context, True)
+
+
+# ---------------------------------------------------------------------------------------------
 # several devices in one process (include/eddsa_amd.h: *_multi), after init_devices()
 # ---------------------------------------------------------------------------------------------
 

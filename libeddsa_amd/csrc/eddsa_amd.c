@@ -91,10 +91,12 @@ static void ws_release(struct vslot *v)
     if (v->ws.offcount) HIP_NOTE(hipFree(v->ws.offcount));
     if (v->ws.exact_pad) HIP_NOTE(hipFree(v->ws.exact_pad));
     if (v->ws.sums) HIP_NOTE(hipFree(v->ws.sums));
+    if (v->ws.domdig) HIP_NOTE(hipFree(v->ws.domdig));
     v->ws.capacity = 0;
     v->ws.digits = v->ws.table = v->ws.acc = v->ws.offlist = v->ws.offcount = v->ws.exact_pad = NULL;
     v->ws.hdigits = v->ws.rtable = v->ws.sums = v->ws.onlist = v->ws.perm = v->ws.lenbins = NULL;
     v->ws.flags = NULL;
+    v->ws.domdig = NULL;
 }
 
 /* bytes of the two secret-bearing buffers of a fixed-base workspace of `cap` items */
@@ -172,6 +174,7 @@ static int ws_reserve(struct vslot *v, size_t items)
     TRY(hipStreamSynchronize(NULL));      /* the pass's stream does not wait for the null stream */
     TRY(hipMalloc((void **)&v->ws.exact_pad, EDK_EXACT_PAD_BYTES));
     TRY(hipMalloc((void **)&v->ws.sums, EDK_SUMS_BYTES));
+    TRY(hipMalloc((void **)&v->ws.domdig, cap * EDK_DOM_DIGEST_BYTES));
     v->ws.capacity = cap;
 out:
     if (rc) ws_release(v);
@@ -522,15 +525,17 @@ out:
     return pass_close(&p, rc);
 }
 
-struct sign_ctx { uint8_t *sigs; const uint8_t *secs, *pubs, *msgs; const uint64_t *msg_off, *msg_end; size_t msg_len; };
+struct sign_ctx { uint8_t *sigs; const uint8_t *secs, *pubs, *msgs; const uint64_t *msg_off, *msg_end; size_t msg_len; const edk_dom *dom; };
 
 static hipError_t sign_step(struct engine *e, size_t done, size_t m, const void *vctx, const edk_fixed_ws *fws, hipStream_t st)
 {
     const struct sign_ctx *c = (const struct sign_ctx *)vctx;
     const uint8_t *mp = c->msg_off ? c->msgs : c->msgs + done * c->msg_len;
     const uint64_t *op = c->msg_off ? c->msg_off + done : NULL;
+    edk_fixed_ws with_dom = *fws;                  /* Ed25519ctx / Ed25519ph: the prefix travels in the launcher's copy of the workspace */
+    with_dom.dom = c->dom;
     return edk_sign(c->sigs + 64 * done, c->secs + 32 * done, c->pubs + 32 * done, mp, op, c->msg_end, c->msg_len, m,
-                    e->comb_img, fws, st);
+                    e->comb_img, &with_dom, st);
 }
 
 struct io_ctx { uint8_t *out; const uint8_t *in; };
@@ -555,11 +560,36 @@ static hipError_t xbase_step(struct engine *e, size_t done, size_t m, const void
     return edk_x25519_base(c->out + 32 * done, c->in + 32 * done, m, e->comb_img, fws, st);
 }
 
+/* dom: NULL (Ed25519), or the dom2 prefix both hashes run under (Ed25519ctx, Ed25519ph) */
+int sign_dom_on(struct engine *e, uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
+                const uint64_t *msg_off, size_t msg_len, size_t n, const edk_dom *dom, hipStream_t st)
+{
+    struct sign_ctx c = { sigs, secs, pubs, msgs, msg_off, msg_off ? msg_off + n : NULL, msg_len, dom };   /* spans are clamped into [0, msg_off[n]) */
+    return fixed_on(e, n, sign_step, &c, st);
+}
+
 int sign_on(struct engine *e, uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
                    const uint64_t *msg_off, size_t msg_len, size_t n, hipStream_t st)
 {
-    struct sign_ctx c = { sigs, secs, pubs, msgs, msg_off, msg_off ? msg_off + n : NULL, msg_len };   /* spans are clamped into [0, msg_off[n]) */
-    return fixed_on(e, n, sign_step, &c, st);
+    return sign_dom_on(e, sigs, secs, pubs, msgs, msg_off, msg_len, n, NULL, st);
+}
+
+/* dom2(flag, context) of RFC 8032 section 2 as the kernels take it (eddsa_kernels.h: edk_dom); a context of more than 255 bytes,
+ * or none where a length is given, is refused */
+int dom2_fill(edk_dom *d, int flag, const uint8_t *context, size_t context_len)
+{
+    static const char tag[32 + 1] = "SigEd25519 no Ed25519 collisions";
+    uint8_t bytes[EDK_DOM_WORDS * 4];
+    if (context_len > EDK_DOM_CONTEXT_MAX || (context_len && !context)) return -(int)hipErrorInvalidValue;
+    memset(bytes, 0, sizeof(bytes));
+    memcpy(bytes, tag, 32);
+    bytes[32] = (uint8_t)flag;
+    bytes[33] = (uint8_t)context_len;
+    if (context_len) memcpy(bytes + EDK_DOM_FIXED_BYTES, context, context_len);
+    d->len = (uint32_t)(EDK_DOM_FIXED_BYTES + context_len);
+    for (int k = 0; k < EDK_DOM_WORDS; k++)
+        d->w[k] = (uint32_t)bytes[4 * k] | (uint32_t)bytes[4 * k + 1] << 8 | (uint32_t)bytes[4 * k + 2] << 16 | (uint32_t)bytes[4 * k + 3] << 24;
+    return 0;
 }
 
 int genpub_on(struct engine *e, uint8_t *pubs, const uint8_t *secs, size_t n, hipStream_t st)
@@ -648,7 +678,7 @@ static int leave_with(struct call *c, int rc) { leave(c); return rc; }
 int ed25519_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs,
                              const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0 };
+    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -667,7 +697,7 @@ int ed25519_verify_records_dev(uint8_t *ok, const uint8_t *records, size_t strid
 {
     if (!records_ok(stride, sig_off, pub_off, msg_off, msg_len)) return -(int)hipErrorInvalidValue;
     const edk_verify_src src = { records + sig_off, records + pub_off, records + msg_off, NULL, msg_len,
-                                 stride, stride, stride, NULL, 0, 0 };
+                                 stride, stride, stride, NULL, 0, 0, NULL };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -677,7 +707,7 @@ int ed25519_verify_records_dev(uint8_t *ok, const uint8_t *records, size_t strid
 int ed25519_verify_batch_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *sigs, const uint8_t *pubs,
                                  const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0 };
+    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -688,7 +718,7 @@ int ed25519_verify_batch_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *si
  * message slot and the flag that selects the kernels that do not hash */
 int ed25519_verify_digests_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1, 0 };
+    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1, 0, NULL };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -698,7 +728,7 @@ int ed25519_verify_digests_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *
 int ed25519_verify_digests_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests,
                                    size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1, 0 };
+    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1, 0, NULL };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -712,6 +742,53 @@ int ed25519_sign_batch_dev(uint8_t *sigs, const uint8_t *secs, const uint8_t *pu
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, sigs))) return rc;
     return leave_with(&c, sign_on(c.e, sigs, secs, pubs, msgs, msg_off, msg_len, n, (hipStream_t)stream));
+}
+
+/* Ed25519ctx and Ed25519ph (include/eddsa_amd.h): the message forms with dom2(F, context) in front of both hashes; ph is ctx with
+ * F = 1 over the caller's 64-byte prehashes.  The prefix is built here, on the host, and goes to the kernels by value. */
+static int dom_verify_dev(int flag, uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
+                          size_t msg_len, size_t n, const uint8_t *context, size_t context_len, void *stream)
+{
+    edk_dom dom;
+    struct call c;
+    int rc = dom2_fill(&dom, flag, context, context_len);
+    if (rc || n == 0 || (rc = enter_dev(&c, ok))) return rc;
+    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, &dom };
+    return leave_with(&c, verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
+}
+
+static int dom_sign_dev(int flag, uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
+                        size_t msg_len, size_t n, const uint8_t *context, size_t context_len, void *stream)
+{
+    edk_dom dom;
+    struct call c;
+    int rc = dom2_fill(&dom, flag, context, context_len);
+    if (rc || n == 0 || (rc = enter_dev(&c, sigs))) return rc;
+    return leave_with(&c, sign_dom_on(c.e, sigs, secs, pubs, msgs, msg_off, msg_len, n, &dom, (hipStream_t)stream));
+}
+
+int ed25519ctx_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
+                                size_t msg_len, size_t n, const uint8_t *context, size_t context_len, void *stream)
+{
+    return dom_verify_dev(0, ok, sigs, pubs, msgs, msg_off, msg_len, n, context, context_len, stream);
+}
+
+int ed25519ph_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *prehashes, size_t n,
+                               const uint8_t *context, size_t context_len, void *stream)
+{
+    return dom_verify_dev(1, ok, sigs, pubs, prehashes, NULL, EDDSA_PREHASH_BYTES, n, context, context_len, stream);
+}
+
+int ed25519ctx_sign_batch_dev(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
+                              size_t msg_len, size_t n, const uint8_t *context, size_t context_len, void *stream)
+{
+    return dom_sign_dev(0, sigs, secs, pubs, msgs, msg_off, msg_len, n, context, context_len, stream);
+}
+
+int ed25519ph_sign_batch_dev(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *prehashes, size_t n,
+                             const uint8_t *context, size_t context_len, void *stream)
+{
+    return dom_sign_dev(1, sigs, secs, pubs, prehashes, NULL, EDDSA_PREHASH_BYTES, n, context, context_len, stream);
 }
 
 int ed25519_genpub_batch_dev(uint8_t *pubs, const uint8_t *secs, size_t n, void *stream)
@@ -856,7 +933,7 @@ int ed25519_verify_batch_multi_dev(uint8_t *const ok_full[], const uint8_t *cons
         size_t lo, hi;
         eddsa_amd_shard_bounds(n_total, d, g, &lo, &hi);
         if (hi - lo != n_total / (size_t)g) even = 0;
-        const edk_verify_src src = { sigs[d], pubs[d], msgs[d], NULL, msg_len, 64, 32, msg_len, NULL, 0, 0 };
+        const edk_verify_src src = { sigs[d], pubs[d], msgs[d], NULL, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL };
         TRY(hipSetDevice(g_multi.dev[d]));
         rc = verify_on(g_eng[g_multi.dev[d]], ok_full[d] + lo, &src, hi - lo, (hipStream_t)streams[d], NULL, 0);
     }

@@ -22,6 +22,15 @@ hipError_t edk_init_tables(uint32_t* base16, uint32_t* comb, uint32_t* comb_img,
 #define EDK_EXACT_SLOTS 65536                        /* items k_verify_exact_quad has in flight at once (4096 waves of 16); a longer work list is walked in strides of this */
 #define EDK_EXACT_PAD_BYTES ((size_t)EDK_EXACT_SLOTS * 960)   /* per slot: four addends x five factors x 12 words (quad_lanes.h: QUAD_ITEM_WORDS) */
 
+/* The dom2(F, C) prefix of Ed25519ctx (F = 0) and Ed25519ph (F = 1), RFC 8032 section 2: the 32 bytes "SigEd25519 no Ed25519
+ * collisions", F, len(C), C - len = 34 + len(C) bytes as little-endian words, zero behind the last byte.  Built on the host per call
+ * (eddsa_amd.c: dom2_fill) and handed BY VALUE to the kernels that hash under it, and to no other kernel: the caller's context
+ * need not outlive the call, and a lane reads the words by uniform index (sha512.h: sha512_dom_msg). */
+typedef struct edk_dom {
+  uint32_t len;
+  uint32_t w[EDK_DOM_WORDS];
+} edk_dom;
+
 /* verify workspace for up to `capacity` items (a multiple of VERIFY_TILE), all in HBM */
 typedef struct edk_verify_ws {
   size_t capacity;
@@ -47,6 +56,8 @@ typedef struct edk_verify_ws {
   int algo;           /* 0: half-length scalars (four lanes per item up to 24 576 items, one above); 1: always full-length; 2: half-length, one lane per item;
                          3: the mid-size arrangement below 2^18 items, full-length from there on.  The table: kernels.hip, verify_route_of */
   int exact_offcurve; /* 1: replay the reference's chain for off-curve keys (default); 0: reject them; 2: replay for every item */
+  uint8_t* domdig;    /* capacity * EDK_DOM_DIGEST_BYTES: Ed25519ctx / Ed25519ph passes: the items' SHA-512(dom2 | R | A | M'), written by
+                         k_dom_challenge and read by the digest forms of the prepare kernels (kernels.hip: edk_verify) */
 } edk_verify_ws;
 
 /* where the items of a verify pass live: item i has its signature at sigs + i * sig_stride, its key
@@ -63,6 +74,10 @@ typedef struct {
   int policy;                /* the EDDSA_AMD_VERIFY_* bits in force (include/eddsa_amd.h), 0 = none: != 0 adds k_verify_policy behind the
                                 pass's verdicts (kernels.hip).  Filled in by src_at (eddsa_amd.c) for verify_on / rlc_on alike; initialisers
                                 that stop at `digest` leave it 0.  Host side only, like `digest` */
+  const edk_dom* dom;        /* != NULL (ed25519ctx_verify_batch*, ed25519ph_verify_batch*): t comes from SHA-512(dom2 || R || A || M') - one
+                                kernel hashes every item under the prefix into ws->domdig and the pass goes on as a digest pass over that
+                                area.  Host side only (the pointer is read while the pass is enqueued); initialisers that stop earlier
+                                leave it NULL; never set together with `digest` */
 } edk_verify_src;
 
 /* What the kernels take BY VALUE: the nine fields of edk_verify_src that lanes read, 72 bytes as before the flag existed.  The flag stays
@@ -96,6 +111,9 @@ typedef struct edk_fixed_ws {
   uint32_t* lenbins;  /* 2 * EDK_LEN_BINS words: sign's ragged messages in order of length, as in edk_verify_ws */
   uint32_t* tiles;    /* EDK_TILES_WORDS words; [0] the next 64-item tile a wave of a persistent point kernel takes (zeroed by the launcher before
                          every such launch): kernels.hip, point_tile */
+  const edk_dom* dom; /* NULL in the engine's own copy.  sign_step (eddsa_amd.c) hands edk_sign a COPY of the workspace with this set for
+                         ed25519ctx_sign_batch* / ed25519ph_sign_batch*: both hashes then run under the prefix (kernels.hip: sign_dom).
+                         Host side only, read while the pass is enqueued */
 } edk_fixed_ws;
 
 /* workspace of the batch (random-linear-combination) verification for up to `capacity` items: one

@@ -50,6 +50,13 @@
 #define EDK_TILES_WORDS 64
 #define EDK_TILES_BYTES (EDK_TILES_WORDS * 4)
 
+/* ---- the dom2 prefix of Ed25519ctx / Ed25519ph (RFC 8032 section 2; eddsa_kernels.h: edk_dom) ---- */
+#define EDK_DOM_FIXED_BYTES 34     /* "SigEd25519 no Ed25519 collisions" | flag | len(context) */
+#define EDK_DOM_CONTEXT_MAX 255
+#define EDK_DOM_WORDS 73           /* the prefix as little-endian words, zero-filled behind its last byte */
+#define EDK_DOM_DIGEST_BYTES 64    /* edk_verify_ws.domdig [item]: SHA-512(dom2 | R | A | M') */
+
+EDK_LAYOUT_ASSERT(EDK_DOM_WORDS * 4 >= EDK_DOM_FIXED_BYTES + EDK_DOM_CONTEXT_MAX, "the longest prefix fits its words");
 EDK_LAYOUT_ASSERT(VERIFY_ITEM_TABLE_WORDS * VERIFY_TILE == VERIFY_TABLE_WORDS_PER_TILE, "a tile of the table is its items' slots");
 EDK_LAYOUT_ASSERT(EDK_BENTRY_WORD + VERIFY_ENTRY_WORDS <= EDK_OFFCOUNT_WORDS, "the base-point entry lies inside offcount");
 EDK_LAYOUT_ASSERT(EDK_OFFLIST_WORD < EDK_PASS_WORDS && EDK_ONLIST_WORD < EDK_PASS_WORDS && EDK_EXACT_UNIT_WORD < EDK_PASS_WORDS &&

@@ -175,6 +175,12 @@ int verify_on(struct engine *e, uint8_t *ok, const edk_verify_src *all, size_t n
 int rlc_on(struct engine *e, uint8_t *ok, uint32_t *stats, const edk_verify_src *all, size_t n, hipStream_t st);
 int sign_on(struct engine *e, uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
             const uint64_t *msg_off, size_t msg_len, size_t n, hipStream_t st);
+/* Ed25519ctx / Ed25519ph: sign_on under the dom2 prefix (NULL: sign_on itself); dom2_fill builds the prefix and is the one place
+ * that refuses a context of more than 255 bytes.  EDDSA_PREHASH_BYTES: what an Ed25519ph item carries in the message slot */
+#define EDDSA_PREHASH_BYTES 64
+int sign_dom_on(struct engine *e, uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
+                const uint64_t *msg_off, size_t msg_len, size_t n, const edk_dom *dom, hipStream_t st);
+int dom2_fill(edk_dom *d, int flag, const uint8_t *context, size_t context_len);
 int genpub_on(struct engine *e, uint8_t *pubs, const uint8_t *secs, size_t n, hipStream_t st);
 int x25519_on(struct engine *e, uint8_t *out, const uint8_t *scalars, const uint8_t *points, size_t n, hipStream_t st);
 int xbase_on(struct engine *e, uint8_t *out, const uint8_t *scalars, size_t n, hipStream_t st);

@@ -254,6 +254,7 @@ struct hjob {
     size_t stride, rec_sig, rec_pub, rec_msg;  /* records: the width of in[0]'s items and the offsets inside them */
     uint32_t *stats;                           /* rlc: host copy of the pass statistics (4 words) or NULL */
     int src_pinned;                            /* every host array of the job is page-locked: no staging */
+    const edk_dom *dom;                        /* Ed25519ctx / Ed25519ph: the call's dom2 prefix (lives on the entry point's stack); else NULL */
 };
 
 static size_t in_w(const struct hjob *j, int i) { return j->op->in_w[i] ? j->op->in_w[i] : j->stride; }
@@ -916,12 +917,12 @@ static int pipe_run(const struct hjob j, size_t n)
 static int run_done(int rc, const struct chunk *c) { return !rc && hipEventRecord(c->kdone, c->st) != hipSuccess ? -(int)hipErrorUnknown : rc; }
 static int run_verify(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0 };
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, NULL };
     return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
 }
 static int run_verify_rlc(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0 };
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, NULL };
     return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
 }
 /* caller-supplied digests: the 64 bytes of SHA-512(R || A || M) per item travel in the message slot (EDDSA_DIGEST_BYTES wide, staged
@@ -930,24 +931,34 @@ static int run_verify_rlc(struct engine *e, const struct hjob *j, const struct c
 static int run_verify_digests(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     (void)j;
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1, 0 };
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1, 0, NULL };
     return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
 }
 static int run_verify_digests_rlc(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     (void)j;
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1, 0 };
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1, 0, NULL };
     return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
 }
 static int run_verify_records(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     const edk_verify_src src = { c->d_in[0] + j->rec_sig, c->d_in[0] + j->rec_pub, c->d_in[0] + j->rec_msg, NULL, j->msg_len,
-                                 j->stride, j->stride, j->stride, NULL, 0, 0 };
+                                 j->stride, j->stride, j->stride, NULL, 0, 0, NULL };
     return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
 }
 static int run_sign(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     return run_done(sign_on(e, c->d_out, c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, c->m, c->st), c);
+}
+/* Ed25519ctx / Ed25519ph: verify and sign under the call's dom2 prefix (ph: msg_len 64, never an offset table) */
+static int run_verify_dom(struct engine *e, const struct hjob *j, const struct chunk *c)
+{
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, j->dom };
+    return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
+}
+static int run_sign_dom(struct engine *e, const struct hjob *j, const struct chunk *c)
+{
+    return run_done(sign_dom_on(e, c->d_out, c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, c->m, j->dom, c->st), c);
 }
 static int run_x25519(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
@@ -967,7 +978,8 @@ RUN_1IN(run_sk_to_x, sk_to_x_on)
  * in chunk order 79-86), and the small first chunk gets the chip working 0.2 ms after the call.  The batch verification
  * makes one combination per 2^20 items; it, the records form and the digest forms (their
  * message counterparts with the digests in the message slot, 64 bytes per item) are never merged by the combiner. */
-enum { OP_VERIFY, OP_VERIFY_RLC, OP_VERIFY_RECORDS, OP_VERIFY_DIGESTS, OP_VERIFY_DIGESTS_RLC, OP_SIGN, OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X };
+enum { OP_VERIFY, OP_VERIFY_RLC, OP_VERIFY_RECORDS, OP_VERIFY_DIGESTS, OP_VERIFY_DIGESTS_RLC, OP_SIGN, OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X,
+       OP_VERIFY_DOM, OP_SIGN_DOM };
 static const struct op g_ops[] = {
     [OP_VERIFY] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify, .wipe = WIPE_NONE, .chain = 0,
                     .kind = KIND_VERIFY, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
@@ -985,6 +997,10 @@ static const struct op g_ops[] = {
     [OP_XBASE] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_xbase, .wipe = WIPE_IN0, .chain = 1, .kind = KIND_XBASE },
     [OP_PK_TO_X] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_pk_to_x, .wipe = WIPE_NONE, .chain = 1, .kind = KIND_PK_TO_X },
     [OP_SK_TO_X] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_sk_to_x, .wipe = WIPE_IN0 | WIPE_OUT, .chain = 1, .kind = KIND_SK_TO_X },
+    /* Ed25519ctx / Ed25519ph: the rows of verify and sign; never merged - two small calls may carry different contexts */
+    [OP_VERIFY_DOM] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_dom, .wipe = WIPE_NONE, .chain = 0,
+                    .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
+    [OP_SIGN_DOM] = { .n_in = 2, .in_w = { 32, 32, 0 }, .out_w = 64, .has_msgs = 1, .run = run_sign_dom, .wipe = WIPE_IN0, .chain = 1, .kind = KIND_NONE },
 };
 
 /* a call of operation `id` (in1, msgs, msg_off: NULL where the operation has none) */
@@ -1044,6 +1060,43 @@ int ed25519_sign_batch(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, 
                        const uint64_t *msg_off, size_t msg_len, size_t n)
 {
     return pipe_run(job(OP_SIGN, sigs, secs, pubs, msgs, msg_off, msg_len), n);
+}
+
+/* Ed25519ctx / Ed25519ph (include/eddsa_amd.h): the prefix is built before anything is touched - a context of more than 255
+ * bytes ends the call there - and lives on this frame for the length of the call */
+static int dom_run(int op, int flag, uint8_t *out, const uint8_t *in0, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
+                   size_t msg_len, size_t n, const uint8_t *context, size_t context_len)
+{
+    edk_dom dom;
+    const int rc = dom2_fill(&dom, flag, context, context_len);
+    if (rc) return rc;
+    struct hjob j = job(op, out, in0, pubs, msgs, msg_off, msg_len);
+    j.dom = &dom;
+    return pipe_run(j, n);
+}
+
+int ed25519ctx_sign_batch(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
+                          size_t msg_len, size_t n, const uint8_t *context, size_t context_len)
+{
+    return dom_run(OP_SIGN_DOM, 0, sigs, secs, pubs, msgs, msg_off, msg_len, n, context, context_len);
+}
+
+int ed25519ctx_verify_batch(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
+                            size_t msg_len, size_t n, const uint8_t *context, size_t context_len)
+{
+    return dom_run(OP_VERIFY_DOM, 0, ok, sigs, pubs, msgs, msg_off, msg_len, n, context, context_len);
+}
+
+int ed25519ph_sign_batch(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *prehashes, size_t n,
+                         const uint8_t *context, size_t context_len)
+{
+    return dom_run(OP_SIGN_DOM, 1, sigs, secs, pubs, prehashes, NULL, EDDSA_PREHASH_BYTES, n, context, context_len);
+}
+
+int ed25519ph_verify_batch(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *prehashes, size_t n,
+                           const uint8_t *context, size_t context_len)
+{
+    return dom_run(OP_VERIFY_DOM, 1, ok, sigs, pubs, prehashes, NULL, EDDSA_PREHASH_BYTES, n, context, context_len);
 }
 
 int x25519_batch(uint8_t *out, const uint8_t *scalars, const uint8_t *points, size_t n) { return pipe_run(job(OP_X25519, out, scalars, points, NULL, NULL, 0), n); }

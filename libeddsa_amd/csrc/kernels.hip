@@ -10,6 +10,7 @@
 //                    *_pair / *_quad forms for small passes; for keys that are not curve points k_verify_exact_quad (short
 //                    work lists, four lanes per item) and k_verify_exact_lane_setup / _chain (long ones, two items per lane)
 //   k_sign_*         ed25519-sha512.c:84-123 sign                    (config 5)
+//   k_dom_challenge, k_sign_dom_*             Ed25519ctx / Ed25519ph, RFC 8032 5.1: the same with dom2 in front of the hashes
 //   k_genpub_point + k_encode_finish          ed25519-sha512.c:53-67 genpub
 //   k_x25519_base_*  x25519.c:158-197 do_x25519_base
 //   k_pk_to_x        ed25519-sha512.c:187-232 pk_ed25519_to_x25519
@@ -894,6 +895,120 @@ k_sign_finish(uint8_t* sigs, uint32_t* acc, uint32_t* aux, const uint8_t* pubs, 
   finish_batch8(sign_finish_policy{sigs, acc, aux, pubs, msgs, msg_off, msg_end, msg_len, n, K, perm}, acc);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Ed25519ctx / Ed25519ph (RFC 8032 5.1): kernels of their own beside the ones above, whose register arrangements stay as they
+// are.  The dom2 prefix arrives by value (eddsa_kernels.h: edk_dom), is staged into LDS once per block and read from there by
+// uniform index.  Sign is three kernels: the secret scalars (one lane per item, both hashes' only secret input), the point
+// R = r B with r taken from aux in every shape of point_shape_of, and the finish with the prefixed challenge.  Verify is one
+// kernel in front of the digest route (edk_verify below).
+// ---------------------------------------------------------------------------------------------
+ED_DEV void stage_dom(uint32_t* lds_dom, const edk_dom& dom) {
+  for (unsigned w = threadIdx.x; w < (unsigned)EDK_DOM_WORDS; w += blockDim.x) lds_dom[w] = dom.w[w];
+  __syncthreads();
+}
+
+// position g hashes item perm[g] (ragged messages in order of length) or item g; the digest goes to the ITEM's slot
+__global__ void __launch_bounds__(BLOCK, 2)
+k_dom_challenge(edk_verify_items src, size_t n, uint8_t* digests, const uint32_t* perm, edk_dom dom) {
+  __shared__ uint32_t lds_dom[EDK_DOM_WORDS];
+  stage_dom(lds_dom, dom);
+  const size_t g = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (g >= n) return;
+  const size_t item = perm ? perm[g] : g;
+  uint32_t rw[8], aw[8], dig[16];
+  const uint8_t* m; size_t mlen;
+  load32(rw, src.sigs, item, src.sig_stride);
+  load32(aw, src.pubs, item, src.pub_stride);
+  msg_span(m, mlen, src.msgs, src.msg_off, src.msg_end, src.msg_len, src.msg_stride, item);
+  verify_dom_hash_lane(dig, lds_dom, dom.len, rw, aw, m, mlen);
+  store32(digests, item, EDK_DOM_DIGEST_BYTES, dig);
+  store32(digests + 32, item, EDK_DOM_DIGEST_BYTES, dig + 8);
+}
+
+// a and r of position g's item into the POSITION's slot of aux, where the two kernels behind it find them
+__global__ void __launch_bounds__(BLOCK, 2)
+k_sign_dom_scalars(uint32_t* aux, const uint8_t* secs, const uint8_t* msgs, const uint64_t* msg_off, const uint64_t* msg_end,
+                   size_t msg_len, size_t n, const uint32_t* perm, edk_dom dom) {
+  __shared__ uint32_t lds_dom[EDK_DOM_WORDS];
+  stage_dom(lds_dom, dom);
+  const size_t g = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (g >= n) return;                            // (an idle lane holds no item's secrets)
+  const size_t item = perm ? perm[g] : g;
+  const uint8_t* m; size_t mlen;
+  msg_span(m, mlen, msgs, msg_off, msg_end, msg_len, msg_len, item);
+  uint32_t sk[8], aw[8], rw[8];
+  load32(sk, secs, item, 32);
+  sign_dom_scalars_lane(aw, rw, lds_dom, dom.len, sk, m, mlen);
+  store8(aux + 16 * g, aw);
+  store8(aux + 16 * g + 8, rw);
+}
+
+// k_sign_point without its hashes: r comes from aux (k_sign_dom_scalars).  An idle lane takes the last position's r and keeps
+// the result to itself (split shape) or leaves R - a public point - in a slot past the pass, like k_sign_point.
+template <int PARTS>
+__global__ void __launch_bounds__(POINT_BLOCK, 512 / POINT_BLOCK)
+k_sign_dom_point(uint32_t* accout, const uint32_t* aux, size_t n, const uint32_t* comb, uint32_t* tiles) {
+  __shared__ alignas(16) uint32_t lds_comb[COMB_IMG_WORDS];
+  stage_table(lds_comb, comb, COMB_IMG_WORDS);
+  __shared__ uint32_t lds_shares[PARTS == 1 ? 1 : 2 * 40 * 64];
+  const int part = PARTS == 1 ? 0 : (int)(threadIdx.x >> 6);
+  size_t i;
+#pragma unroll 1
+  for (unsigned it = 0; point_tile<PARTS>(i, it, n, tiles); it++) {
+    uint32_t rw[8];
+    load8(rw, aux + 16 * (i < n ? i : n - 1) + 8);
+    ge R;
+    scale_base_lane<PARTS>(R, rw, lds_comb, part);
+    if (PARTS > 1) point_reduce4(R, lds_shares, part);
+    if (PARTS == 1 || (part == 0 && i < n)) acc_store(accout, i, R);
+  }
+}
+
+// sign_finish_policy with the prefixed challenge
+struct sign_dom_finish_policy {
+  uint8_t* sigs; uint32_t* acc; uint32_t* aux; const uint8_t* pubs; const uint8_t* msgs;
+  const uint64_t* msg_off; const uint64_t* msg_end; size_t msg_len; size_t n; int K; const uint32_t* perm;
+  const uint32_t* dom; uint32_t dom_len;
+  ED_DEV void den(int k, fe& z) const {
+    const finish_pos p = finish_at(k, acc, K);
+    fe_set(z, 1);
+    if (p.i < n) acc_load(z, p.acc, ACC_Z);
+    den_commit(z, true, acc, k, K);
+  }
+  ED_DEV void item(int k) const {
+    const finish_pos p = finish_at(k, acc, K);
+    if (p.i >= n) return;
+    const size_t it = perm ? perm[p.i] : p.i;      // the item this position carries (k_sign_dom_scalars)
+    fe x, y, zinv;
+    acc_load(x, p.acc, ACC_X); acc_load(y, p.acc, ACC_Y); acc_load(zinv, p.acc, ACC_Z);
+    uint32_t Rw[8], Sw[8], pub[8];
+    encode_lane(Rw, x, y, zinv);
+    load32(pub, pubs, it, 32);
+    const uint8_t* m; size_t mlen;
+    msg_span(m, mlen, msgs, msg_off, msg_end, msg_len, msg_len, it);
+    sc t;
+    sign_dom_challenge_lane(t, dom, dom_len, Rw, pub, m, mlen);
+    uint32_t aw[8], rw[8];
+    uint32_t* d = aux + 16 * p.i;
+    load8(aw, d);
+    load8(rw, d + 8);
+    const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the secrets do not outlive the call in HBM
+    store8(d, zero);
+    store8(d + 8, zero);
+    sign_response_lane(Sw, t, aw, rw);
+    store32(sigs, it, 64, Rw);
+    store32(sigs + 32, it, 64, Sw);
+  }
+};
+
+__global__ void __launch_bounds__(BLOCK, 2)
+k_sign_dom_finish(uint8_t* sigs, uint32_t* acc, uint32_t* aux, const uint8_t* pubs, const uint8_t* msgs,
+                  const uint64_t* msg_off, const uint64_t* msg_end, size_t msg_len, size_t n, int K, const uint32_t* perm, edk_dom dom) {
+  __shared__ uint32_t lds_dom[EDK_DOM_WORDS];
+  stage_dom(lds_dom, dom);
+  finish_batch8(sign_dom_finish_policy{sigs, acc, aux, pubs, msgs, msg_off, msg_end, msg_len, n, K, perm, lds_dom, dom.len}, acc);
+}
+
 template <int PARTS>
 __global__ void __launch_bounds__(POINT_BLOCK, 512 / POINT_BLOCK)
 k_x25519_base_point(uint32_t* accout, const uint8_t* scalars, size_t n, const uint32_t* comb, uint32_t* tiles) {
@@ -1331,7 +1446,15 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
   if (!src.digest) EDK_DO(edk_msg_order(&perm, ws, src.msg_off, src.msg_end, n, stream));
   // 3. prepare.  Caller-supplied digests (ed25519_verify_digests*): the same preparations without the hash; everything after
   // them reads t from the workspace and does not know
-  const hipError_t prepared = src.digest ? launch_prepare<true>(edk_items_of(&src), n, ws, r, perm, stream) : launch_prepare<false>(edk_items_of(&src), n, ws, r, perm, stream);
+  hipError_t prepared;
+  if (src.dom) {
+    // Ed25519ctx / Ed25519ph: one lane per item hashes dom2 || R || A || M' into the item's 64 bytes of ws->domdig (in order of
+    // length, like every hashing kernel); from there on the pass IS a digest pass whose message slot is that area
+    EDK_LAUNCH(k_dom_challenge, dim3(blocks), dim3(BLOCK), 0, stream, edk_items_of(&src), n, ws->domdig, perm, *src.dom);
+    const edk_verify_items hashed = { src.sigs, src.pubs, ws->domdig, nullptr, EDK_DOM_DIGEST_BYTES, src.sig_stride, src.pub_stride, EDK_DOM_DIGEST_BYTES, nullptr };
+    prepared = launch_prepare<true>(hashed, n, ws, r, nullptr, stream);
+  } else
+    prepared = src.digest ? launch_prepare<true>(edk_items_of(&src), n, ws, r, perm, stream) : launch_prepare<false>(edk_items_of(&src), n, ws, r, perm, stream);
   if (prepared != hipSuccess) return prepared;
   // 4. halve.  Below HALF_WIDE_MIN_N items the pass searches pairs up to 2^138 and runs 35 windows (2 t in 10^7 without a pair
   // instead of 8.5 in 10^5; 3 % more instructions in the main kernel): an item without a short pair goes through the exact
@@ -1419,6 +1542,12 @@ hipError_t edk_sign(uint8_t* sigs, const uint8_t* secs, const uint8_t* pubs, con
   const finish_shape f = finish_shape_of(n);
   const uint32_t* perm = nullptr;                  // ragged messages: both kernels hash, both take their items in order of length
   if (const hipError_t e = msg_order(&perm, ws->perm, ws->lenbins, msg_off, msg_end, n, stream); e != hipSuccess) return e;
+  if (ws->dom) {                                   // Ed25519ctx / Ed25519ph: scalars, point, finish - the same shapes, the prefixed hashes
+    hipLaunchKernelGGL(k_sign_dom_scalars, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, ws->aux, secs, msgs, msg_off, msg_end, msg_len, n, perm, *ws->dom);
+    if (const hipError_t e = launch_point(k_sign_dom_point<POINT_SPLIT>, k_sign_dom_point<1>, n, ws, stream, ws->acc, (const uint32_t*)ws->aux, n, comb); e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_sign_dom_finish, dim3(f.grid), dim3(BLOCK), 0, stream, sigs, ws->acc, ws->aux, pubs, msgs, msg_off, msg_end, msg_len, n, f.k, perm, *ws->dom);
+    return hipGetLastError();
+  }
   if (const hipError_t e = launch_point(k_sign_point<POINT_SPLIT>, k_sign_point<1>, n, ws, stream, ws->acc, ws->aux, secs, msgs, msg_off, msg_end, msg_len, n, comb, perm); e != hipSuccess) return e;
   hipLaunchKernelGGL(k_sign_finish, dim3(f.grid), dim3(BLOCK), 0, stream, sigs, ws->acc, ws->aux, pubs, msgs, msg_off, msg_end, msg_len, n, f.k, perm);
   return hipGetLastError();

@@ -14,6 +14,7 @@
 //                          build and the layer probe; the kernels run its four-lane form, quad_lanes.h)
 //   scale_base_lane        ed.c:397-430 ed_scale_base (comb, constant-time select)
 //   genpub_point_lane, sign_point_lane, sign_finish_lane, encode_lane   ed25519-sha512.c:53-123
+//   verify_dom_hash_lane, sign_dom_scalars_lane, sign_dom_challenge_lane   the hashes of Ed25519ctx / Ed25519ph (RFC 8032 5.1)
 //   x25519_base_point_lane, x25519_base_finish_lane                      x25519.c:158-197
 //   pk_to_x_lane, sk_to_x_lane   ed25519-sha512.c:187-256
 #pragma once
@@ -1406,6 +1407,38 @@ ED_DEV void sign_finish_lane(uint32_t Sw[8], const uint32_t Rw[8], const uint32_
   sc t;
   sign_challenge_lane(t, Rw, pub, m, mlen);
   sign_response_lane(Sw, t, aw, rw);
+}
+
+// ---- Ed25519ctx / Ed25519ph (RFC 8032 5.1.6, 5.1.7): the same three hashes with dom2(F, C) in front.  dom, P: the prefix's
+// words and its length in bytes, the same in every lane (sha512.h: sha512_dom_msg); m: M' (the message, or the caller's prehash)
+static_assert(SHA_DOM_MAX_WORDS == EDK_DOM_WORDS, "sha512.h reads the words edk_layout.h lays out");
+
+// dig = SHA-512(dom2 || R || A || M') as sixteen little-endian words: what verify_digest_lane takes
+ED_DEV void verify_dom_hash_lane(uint32_t dig[16], const uint32_t* dom, uint32_t P, const uint32_t rw[8], const uint32_t aw[8],
+                                 const uint8_t* m, size_t mlen) {
+  uint32_t pre[16];
+#pragma unroll
+  for (int k = 0; k < 8; k++) { pre[k] = rw[k]; pre[8 + k] = aw[k]; }
+  sha512_dom_msg<16>(dig, dom, P, pre, m, mlen);
+}
+// aw = a (from the key hash, as in sign_scalars_lane) and rw = r = H(dom2 || h[32..64) || M') mod l, as words
+ED_DEV void sign_dom_scalars_lane(uint32_t aw[8], uint32_t rw[8], const uint32_t* dom, uint32_t P, const uint32_t sk[8],
+                                  const uint8_t* m, size_t mlen) {
+  uint32_t h[16], dig[16];
+  key_setup(h, sk);
+  sc a, r;
+  sc_from_words<8>(a, h);
+  sc_to_words(aw, a);
+  sha512_dom_msg<8>(dig, dom, P, h + 8, m, mlen);
+  sc_from_words<16>(r, dig);
+  sc_to_words(rw, r);
+}
+// t = H(dom2 || R || A || M') mod l; sign_response_lane follows
+ED_DEV void sign_dom_challenge_lane(sc& t, const uint32_t* dom, uint32_t P, const uint32_t Rw[8], const uint32_t pub[8],
+                                    const uint8_t* m, size_t mlen) {
+  uint32_t dig[16];
+  verify_dom_hash_lane(dig, dom, P, Rw, pub, m, mlen);
+  sc_from_words<16>(t, dig);
 }
 
 // x25519.c:158-190 do_x25519_base, up to R = x*B

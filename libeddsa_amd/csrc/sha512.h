@@ -7,6 +7,7 @@
 //   challenge   SHA-512(R || A || M)        ed25519-sha512.c:113-118 and :166-171
 // i.e. always "a prefix of NPRE little-endian 32-bit words held in registers, then a message in
 // global memory".  All 80 rounds are unrolled so the 16-word schedule ring stays in registers.
+// Ed25519ctx / Ed25519ph put a third part in front, the dom2 prefix of the call: sha512_dom_msg at the end of the file.
 #pragma once
 #include "fe25519.h"
 
@@ -182,6 +183,102 @@ ED_DEV void sha512_prefix_msg(uint32_t out[16], const uint32_t* pre, const uint8
           lo32 = sha_msg_word(msg, len, aligned, g + 1);
         }
         w[k] = ((uint64_t)bswap32(hi32) << 32) | bswap32(lo32);
+      }
+    }
+    if (b == nblk - 1) w[15] = (uint64_t)total << 3;   // sha512.c:196-203 (high 64 bits are 0)
+    sha512_compress(st, w);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    out[2 * k] = bswap32((uint32_t)(st[k] >> 32));
+    out[2 * k + 1] = bswap32((uint32_t)st[k]);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Ed25519ctx / Ed25519ph (RFC 8032 section 5.1): both hashes of the scheme with dom2(F, C) in front,
+//   nonce       SHA-512(dom2 || h[32..64) || M')
+//   challenge   SHA-512(dom2 || R || A || M')
+// i.e. "P bytes that every lane of the call shares, NPRE register words, then the message".  P = 34 + len(C) is any number from
+// 34 to 289, so neither the register words nor the message start on a word of the stream - but P is the same in every lane:
+// which bytes of a block come from where is wave-uniform, and only the blocks that hold a boundary are put together bytewise.
+// ---------------------------------------------------------------------------------------------
+constexpr int SHA_DOM_MAX_WORDS = 73;              // (34 + 255 bytes; edk_layout.h: EDK_DOM_WORDS)
+
+// sha_msg_word for a BYTE offset of either sign: the little-endian word of the stream bytes boff .. boff + 3 of the padded message.
+// Bytes in front of the message read 0 (the caller ORs the end of the prefix in), byte len reads 0x80, the bytes behind it 0.
+ED_DEV uint32_t sha_msg_word_at(const uint8_t* msg, size_t len, int64_t boff) {
+  if (boff >= 0 && (uint64_t)boff + 4 <= len) {
+    const uint8_t* p = msg + boff;
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+  }
+  uint32_t v = 0;
+#pragma unroll
+  for (int t = 0; t < 4; t++) {
+    const int64_t pos = boff + t;
+    uint32_t byte = 0;
+    if (pos >= 0 && (uint64_t)pos < len) byte = msg[pos];
+    else if (pos >= 0 && (uint64_t)pos == len) byte = 0x80u;
+    v |= byte << (8 * t);
+  }
+  return v;
+}
+
+// a[q], or 0 for q outside 0..N-1, without indexing registers at run time (q is wave-uniform: a compare and a select per entry)
+template <int N>
+ED_DEV uint32_t sha_pick_word(const uint32_t (&a)[N], int q) {
+  uint32_t v = 0;
+#pragma unroll
+  for (int i = 0; i < N; i++) v = q == i ? a[i] : v;
+  return v;
+}
+
+// out[16] = SHA-512(dom[0..P) bytes || pre[0..NPRE) words || msg[0..len)), NPRE 8 or 16.  dom: the prefix as little-endian words,
+// ZERO behind byte P - 1 up to the next word boundary, read by uniform index (LDS or constant memory on the device); 34 <= P <= 289.
+// Every block that lies wholly inside the message takes sha_full_block_words (any alignment; the header H = P + 4 NPRE only shifts
+// the pointer).  The other blocks - the one to four at the head that hold a part of the header, and the padded tail - are built
+// word by word: a stream word is the OR of the prefix's word, of the register words shifted by P mod 4 bytes (sp[], computed
+// once), and of the message's bytes, each present or not by comparisons of uniform numbers.
+template <int NPRE>
+ED_DEV void sha512_dom_msg(uint32_t out[16], const uint32_t* dom, uint32_t P, const uint32_t* pre, const uint8_t* msg, size_t len) {
+  uint64_t st[8] = {0x6a09e667f3bcc908ULL, 0xbb67ae8584caa73bULL, 0x3c6ef372fe94f82bULL,
+                    0xa54ff53a5f1d36f1ULL, 0x510e527fade682d1ULL, 0x9b05688c2b3e6c1fULL,
+                    0x1f83d9abfb41bd6bULL, 0x5be0cd19137e2179ULL};
+  ED_CHECK(P >= 34 && P <= 4 * SHA_DOM_MAX_WORDS - 3);
+  const size_t H = (size_t)P + 4 * (size_t)NPRE, total = H + len;
+  const size_t nblk = (total + 17 + 127) >> 7;
+  const int q0 = (int)(P >> 2);                  // the stream word that holds the first register byte
+  const uint32_t s8 = 8 * (P & 3);               // ... at this bit
+  uint32_t sp[NPRE + 1];                         // stream words q0 .. q0 + NPRE, the register bytes of each
+#pragma unroll
+  for (int i = 0; i <= NPRE; i++) {
+    const uint32_t lo = i < NPRE ? pre[i] : 0u, hi = i > 0 ? pre[i - 1] : 0u;
+    sp[i] = s8 ? (lo << s8) | (hi >> (32 - s8)) : lo;
+  }
+  uint64_t w[16];
+  for (size_t b = 0; b < nblk; b++) {
+    const size_t o0 = 128 * b;
+    if (o0 >= H && o0 + 128 <= total) {
+      ED_CHECK(o0 - H + 128 <= len);
+      sha_full_block_words(w, msg + (o0 - H));
+    } else {
+      const bool has_pre = o0 < H && o0 + 128 > 4 * (size_t)q0;
+#pragma unroll
+      for (int k = 0; k < 16; k++) {
+        uint32_t x[2];                           // stream words 2k (first in byte order) and 2k+1 of this block
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          const size_t o = o0 + 8 * k + 4 * h;   // the word's first stream byte
+          uint32_t v = 0;
+          if (o < P) {
+            ED_CHECK((o >> 2) < (size_t)SHA_DOM_MAX_WORDS);
+            v = dom[o >> 2];
+          }
+          if (has_pre) v |= sha_pick_word(sp, (int)(o >> 2) - q0);
+          if (o + 4 > H && o <= total) v |= sha_msg_word_at(msg, len, (int64_t)o - (int64_t)H);
+          x[h] = v;
+        }
+        w[k] = ((uint64_t)bswap32(x[0]) << 32) | bswap32(x[1]);
       }
     }
     if (b == nblk - 1) w[15] = (uint64_t)total << 3;   // sha512.c:196-203 (high 64 bits are 0)
