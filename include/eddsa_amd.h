@@ -201,6 +201,9 @@ EDDSA_AMD_DECL int ed25519_verify_records(uint8_t *ok, const uint8_t *records, s
  * generated keys and signatures) -- up to a 2^-125 chance per group; crafted inputs with small-order
  * COMPONENTS in several items of one group can make the group pass although the reference's
  * cofactorless check rejects one of them.  That is why this is never the default.
+ * Under the COFACTORED equation (eddsa_amd_set_verify_equation, below) that caveat does not exist: the verdicts equal the
+ * per-item ones of that equation, up to 2^-125 per group, for every input; an R that is no canonical encoding then sends its
+ * group to the per-item kernels instead of being rejected at once.
  * stats (4 words, may be NULL) receives: items decided by the combination, items decided per item,
  * groups sent to the per-item kernels, groups decided by the combination.
  * The device-pointer form synchronises `stream` once per pass (it reads the group verdicts).
@@ -329,6 +332,45 @@ RFC8032_EDDSA_DECL int ed25519ph_sign_batch_dev(uint8_t *sigs, const uint8_t *se
 RFC8032_EDDSA_DECL int ed25519ph_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs,
                                                   const uint8_t *prehashes, size_t n,
                                                   const uint8_t *context, size_t context_len, void *stream);
+
+/* ---- the equation an item is held to: cofactorless (the reference's, default) or COFACTORED (the rules of ZIP-215) ----
+ * Opt-in and process-wide, like the strict rules, but a call of its own: eddsa_amd_set_offcurve_mode's word, its policy mask and
+ * what its values mean are untouched.  Returns 0, or -hipErrorInvalidValue for any value other than the two below, in which
+ * case the setting stays what it was.  A call uses the equation in force when each of its passes is enqueued, under the same
+ * lock as the off-curve mode and the policy.
+ * Under EDDSA_AMD_EQUATION_COFACTORED an item is accepted exactly when ALL of these hold:
+ *   - sig[32..64), read little-endian, is below l;
+ *   - A (pub) decodes: y = the low 255 bits mod p (a non-canonical y counts), (y^2 - 1) / (d y^2 + 1) is a square, x takes the
+ *     sign bit, and x = 0 with the sign bit set is accepted as x = 0;
+ *   - R (sig[0..32)) decodes by the same rule;
+ *   - [8]([S]B - [t]A - R) is the neutral element, t = SHA-512(R || A || M) mod l over the bytes as given (the digest forms:
+ *     t from the caller's 64 bytes; Ed25519ctx / Ed25519ph: t from the dom2-prefixed hash - as for the cofactorless check).
+ * A key or an R that is no curve point is rejected: off-curve modes 0 and 1 then give the same verdicts (mode 1 runs as mode 0
+ * and the reference-order chain is not launched; mode 2 keeps its meaning as a self-check).  The strict rules compose as they
+ * do with the reference's check: the verdict is (the cofactored verdict) AND (every predicate of the policy) - A_NOT_SMALL on
+ * top of this equation rejects every small-order key, for instance.  The setting holds for EVERY form of verification: the
+ * thirteen names of eddsa.h (calls merged by the small-call combiner included), the batched, records and digest forms,
+ * Ed25519ctx and Ed25519ph, _rlc, _multi and the device-pointer forms.
+ * Why: this is the one per-item rule under which single and batch verification always agree, which is what nodes that must
+ * reach the same verdict need.  Under it ed25519_verify_batch_rlc's verdicts EQUAL the per-item ones, up to 2^-125 per group,
+ * for EVERY input: the caveat in that function's description (crafted small-order components) is gone, because a group the
+ * combination accepts consists - up to that bound - of items this equation accepts, and a group that fails, or that holds a
+ * key or an R of small order, a key off the curve or an R that is no canonical encoding, is decided item by item by this rule.
+ * How: the pass runs unchanged (full-length route, off-curve keys rejected, S < l added to the policy kernel); what it accepts
+ * this equation accepts too, so only the items it REJECTED are listed and evaluated again, one lane each: the same 252
+ * doublings and 80 additions, - R added, three doublings and a projective neutrality test (no inversion).  With the
+ * cofactorless equation nothing is queued and no kernel's arguments change.
+ * Measured (profiles/verify_cofactored.txt, tools/cofactored_cost.py: ed25519_verify_batch_dev, 2^20 items in HBM, 32-byte
+ * messages, one MI355X, the rows alternating): equation 0 9.51 ms per pass; cofactored, every item valid 10.55 ms (+11 %: the
+ * full-length route of the reject mode, the listing kernel, S < l); with 1 % of the items rejected 11.87 ms (+25 %: the one-lane
+ * evaluation of a short list costs its latency, 1.3 ms, behind the pass - a four-lane form for short lists is a follow-up);
+ * with EVERY item rejected, the worst case a caller can construct, 22.20 ms (+134 %: a second full-length evaluation, 47 M
+ * items/s); _rlc on valid items 4.40 ms against 4.38 (+0.4 %).  Equation 0 against the commit before the equation, alternating
+ * on that box: 9.48-9.49 ms against 9.48-9.49 ms - inside the older build's own repeat spread.
+ * (Declared with the macro of the RFC 8032 variants: tests of earlier additions count the EDDSA_AMD_DECL names.) */
+#define EDDSA_AMD_EQUATION_COFACTORLESS 0
+#define EDDSA_AMD_EQUATION_COFACTORED   1
+RFC8032_EDDSA_DECL int eddsa_amd_set_verify_equation(int equation);
 
 #ifdef __cplusplus
 }

@@ -240,6 +240,19 @@ def set_verify_policy(policy=0):
     _send_mode_word()
 
 
+# the equation an item is held to: include/eddsa_amd.h, EDDSA_AMD_EQUATION_*
+EQUATION_COFACTORLESS = 0
+EQUATION_COFACTORED = 1
+
+
+def set_verify_equation(cofactored=False):
+    """the equation every form of verification holds an item to from now on, process-wide: False / EQUATION_COFACTORLESS
+    (default) = the reference's check, True / EQUATION_COFACTORED = the rules of ZIP-215: S < l, A and R any encoding that
+    decodes, [8](S B - t A - R) = 0 - the rule under which single and batch verification always agree.  A call of its own:
+    the off-curve mode (set_offcurve_mode) and the verify policy (set_verify_policy) stay as they are."""
+    _check(library().eddsa_amd_set_verify_equation(ctypes.c_int(int(cofactored))), "eddsa_amd_set_verify_equation")
+
+
 def set_verify_algo(algo=0):
     """0 (default): half-length scalars (four lanes per item up to 24 576 items, one above); 1: always full-length;
     2: half-length with one lane per item whatever the size; 3: the arrangement of 24 577 .. 2^18 items (three-lane

@@ -24,6 +24,7 @@ static int g_default = -1;            /* device of the host-pointer entry points
 static int g_verify_algo = 0;         /* eddsa_amd_set_verify_algo: 0 by pass size (default), 1 full-length windows, 2 half-length scalars */
 static int g_offcurve_mode = 1;       /* eddsa_amd_set_offcurve_mode: 0 reject, 1 exact (default), 2 all exact */
 static int g_verify_policy;           /* the EDDSA_AMD_VERIFY_* bits of the same word (default 0: the reference's verdicts) */
+static int g_verify_equation;         /* eddsa_amd_set_verify_equation: EDDSA_AMD_EQUATION_COFACTORLESS (default) or _COFACTORED */
 static int g_profiling;               /* record marks around the three verify kernels */
 static size_t g_rlc_min_items = EDDSA_AMD_RLC_MIN_ITEMS_DEFAULT;   /* eddsa_amd_set_rlc_min_items: smaller calls go to the per-item kernels */
 
@@ -418,6 +419,24 @@ void eddsa_amd_set_offcurve_mode(int exact)
     pthread_rwlock_unlock(&g_table);
 }
 
+/* The equation an item is held to (include/eddsa_amd.h): a call of its own, not a bit of the word above - the policy mask and
+ * the meaning of that word's other values stay what they are.  Read where a pass is enqueued, under the same lock. */
+int eddsa_amd_set_verify_equation(int equation)
+{
+    if (equation != EDDSA_AMD_EQUATION_COFACTORLESS && equation != EDDSA_AMD_EQUATION_COFACTORED) return -(int)hipErrorInvalidValue;
+    pthread_rwlock_wrlock(&g_table);
+    g_verify_equation = equation;
+    pthread_rwlock_unlock(&g_table);
+    return 0;
+}
+
+/* The off-curve mode a pass runs in.  Under the cofactored equation a key that is no curve point is rejected whatever the
+ * mode says, so mode 1 runs as mode 0 - the exact chain is not launched; the self-check mode 2 keeps its meaning. */
+static int pass_offcurve_mode(void)
+{
+    return g_verify_equation && g_offcurve_mode == 1 ? 0 : g_offcurve_mode;
+}
+
 /* ed25519_verify_batch_rlc[_dev] calls of fewer than `items` items use the per-item kernels (default EDDSA_AMD_RLC_MIN_ITEMS_DEFAULT:
  * above the measured break-even; 0 = always try the combination) */
 void eddsa_amd_set_rlc_min_items(size_t items)
@@ -486,6 +505,7 @@ static edk_verify_src src_at(const edk_verify_src *all, size_t n, size_t done)
     src.pubs += done * all->pub_stride;
     if (all->msg_off) src.msg_off += done; else src.msgs += done * all->msg_stride;
     src.policy = g_verify_policy;   /* read where the pass is enqueued, like g_offcurve_mode */
+    src.equation = g_verify_equation;
     return src;
 }
 
@@ -497,8 +517,8 @@ int verify_on(struct engine *e, uint8_t *ok, const edk_verify_src *all, size_t n
     if (n == 0) return 0;
     if ((rc = take_async_error(e))) return rc;   /* an earlier pass's kernels gave up: see engine.h */
     if ((rc = pass_open(&p, e, n, PASS_WS, st))) return rc;
-    p.v->ws.exact_offcurve = g_offcurve_mode;
-    p.v->ws.algo = g_offcurve_mode ? g_verify_algo : 1;   /* the reject mode has no exact path for the items the pair search gives up on */
+    p.v->ws.exact_offcurve = pass_offcurve_mode();
+    p.v->ws.algo = p.v->ws.exact_offcurve ? g_verify_algo : 1;   /* the reject mode has no exact path for the items the pair search gives up on */
     for (size_t done = 0; done < n; done += CHUNK_MAX) {
         const size_t m = n - done < CHUNK_MAX ? n - done : CHUNK_MAX;
         const edk_verify_src src = src_at(all, n, done);
@@ -644,7 +664,9 @@ int rlc_on(struct engine *e, uint8_t *ok, uint32_t *stats, const edk_verify_src 
      * e->lk (other threads keep enqueueing on this engine meanwhile); the workspace slot stays reserved through its
      * busy mark, which ws_pick honours. */
     if ((rc = pass_open(&p, e, n, PASS_WS | PASS_RWS | PASS_BUSY, st))) return rc;
-    p.v->ws.exact_offcurve = g_offcurve_mode ? g_offcurve_mode : 1;
+    /* (the fallback of the cofactorless equation always has the exact path; under the cofactored one it rejects off-curve keys
+     * like every pass, and verify_route_of takes the full-length route) */
+    p.v->ws.exact_offcurve = g_verify_equation ? pass_offcurve_mode() : g_offcurve_mode ? g_offcurve_mode : 1;
     p.v->ws.algo = g_verify_algo;
     for (size_t done = 0; done < n; done += CHUNK_MAX) {
         const size_t m = n - done < CHUNK_MAX ? n - done : CHUNK_MAX;
@@ -678,7 +700,7 @@ static int leave_with(struct call *c, int rc) { leave(c); return rc; }
 int ed25519_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs,
                              const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL };
+    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL, 0 };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -697,7 +719,7 @@ int ed25519_verify_records_dev(uint8_t *ok, const uint8_t *records, size_t strid
 {
     if (!records_ok(stride, sig_off, pub_off, msg_off, msg_len)) return -(int)hipErrorInvalidValue;
     const edk_verify_src src = { records + sig_off, records + pub_off, records + msg_off, NULL, msg_len,
-                                 stride, stride, stride, NULL, 0, 0, NULL };
+                                 stride, stride, stride, NULL, 0, 0, NULL, 0 };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -707,7 +729,7 @@ int ed25519_verify_records_dev(uint8_t *ok, const uint8_t *records, size_t strid
 int ed25519_verify_batch_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *sigs, const uint8_t *pubs,
                                  const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL };
+    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL, 0 };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -718,7 +740,7 @@ int ed25519_verify_batch_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *si
  * message slot and the flag that selects the kernels that do not hash */
 int ed25519_verify_digests_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1, 0, NULL };
+    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1, 0, NULL, 0 };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -728,7 +750,7 @@ int ed25519_verify_digests_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *
 int ed25519_verify_digests_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests,
                                    size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1, 0, NULL };
+    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1, 0, NULL, 0 };
     struct call c;
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
@@ -753,7 +775,7 @@ static int dom_verify_dev(int flag, uint8_t *ok, const uint8_t *sigs, const uint
     struct call c;
     int rc = dom2_fill(&dom, flag, context, context_len);
     if (rc || n == 0 || (rc = enter_dev(&c, ok))) return rc;
-    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, &dom };
+    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, &dom, 0 };
     return leave_with(&c, verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
 }
 
@@ -933,7 +955,7 @@ int ed25519_verify_batch_multi_dev(uint8_t *const ok_full[], const uint8_t *cons
         size_t lo, hi;
         eddsa_amd_shard_bounds(n_total, d, g, &lo, &hi);
         if (hi - lo != n_total / (size_t)g) even = 0;
-        const edk_verify_src src = { sigs[d], pubs[d], msgs[d], NULL, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL };
+        const edk_verify_src src = { sigs[d], pubs[d], msgs[d], NULL, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL, 0 };
         TRY(hipSetDevice(g_multi.dev[d]));
         rc = verify_on(g_eng[g_multi.dev[d]], ok_full[d] + lo, &src, hi - lo, (hipStream_t)streams[d], NULL, 0);
     }

@@ -78,6 +78,10 @@ typedef struct {
                                 kernel hashes every item under the prefix into ws->domdig and the pass goes on as a digest pass over that
                                 area.  Host side only (the pointer is read while the pass is enqueued); initialisers that stop earlier
                                 leave it NULL; never set together with `digest` */
+  int equation;              /* EDDSA_AMD_EQUATION_* (include/eddsa_amd.h), 0 = the reference's cofactorless check: != 0 adds the
+                                k_cofactor_* kernels behind the pass's verdicts and S < l to its policy (kernels.hip: edk_verify), and
+                                sends a group with a non-canonical R to the per-item kernels (rlc.hip).  Filled in by src_at like
+                                `policy`, read beside it; initialisers that stop earlier leave it 0.  Host side only */
 } edk_verify_src;
 
 /* What the kernels take BY VALUE: the nine fields of edk_verify_src that lanes read, 72 bytes as before the flag existed.  The flag stays

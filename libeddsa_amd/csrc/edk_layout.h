@@ -44,6 +44,7 @@
 #define EDK_PASS_WORDS 4            /* words 0..3 are zeroed by every pass */
 #define EDK_REFUSED_WORD 8          /* half-length pairs that the exact check of lanes.h: verify_half_scalars_lane refused since allocation (diagnostic) */
 #define EDK_WITHHOLD_WORD 9         /* test hook (eddsa_amd_debug_withhold_handoff): tile + 1 whose first hand-off is never published; 0: none */
+#define EDK_COLIST_WORD 10          /* the cofactored equation (kernels.hip: k_cofactor_list): the length of its work list; zeroed on the stream in front of that kernel */
 #define EDK_BENTRY_WORD 32          /* words 32..63: the base point as a packed cached entry (lanes.h: exact_bentry_store) */
 
 /* ---- edk_fixed_ws.tiles: [0] the tile counter of the persistent point kernels ---- */
@@ -63,3 +64,5 @@ EDK_LAYOUT_ASSERT(EDK_OFFLIST_WORD < EDK_PASS_WORDS && EDK_ONLIST_WORD < EDK_PAS
                   EDK_STALL_WORD < EDK_PASS_WORDS && EDK_PASS_WORDS == 4, "every pass zeroes its four words");
 EDK_LAYOUT_ASSERT(EDK_REFUSED_WORD >= EDK_PASS_WORDS && EDK_WITHHOLD_WORD >= EDK_PASS_WORDS && EDK_BENTRY_WORD >= EDK_PASS_WORDS &&
                   EDK_REFUSED_WORD < EDK_BENTRY_WORD && EDK_WITHHOLD_WORD < EDK_BENTRY_WORD, "... and nothing that outlives it");
+EDK_LAYOUT_ASSERT(EDK_COLIST_WORD >= EDK_PASS_WORDS && EDK_COLIST_WORD < EDK_BENTRY_WORD && EDK_COLIST_WORD != EDK_REFUSED_WORD &&
+                  EDK_COLIST_WORD != EDK_WITHHOLD_WORD, "the cofactored list's length has a word of its own outside the four");

@@ -30,6 +30,13 @@ ED_DEV void ge_neutral(ge& p) {                  // ed.c:72 ed_zero
   fe_set(p.X, 0); fe_set(p.Y, 1); fe_set(p.Z, 1); fe_set(p.T, 0);
 }
 
+// is p (tight coordinates, Z != 0) the neutral element: X = 0 and Y = Z?  No inversion
+ED_DEV bool ge_is_neutral(const ge& p) {
+  fe d;
+  fe_sub(d, p.Y, p.Z);
+  return fe_iszero(p.X) && fe_iszero(d);
+}
+
 ED_DEV void ge_base(ge& p) {
   p.X = fe_const_bx(); p.Y = fe_const_by(); fe_set(p.Z, 1);
   fe_mul(p.T, p.X, p.Y);

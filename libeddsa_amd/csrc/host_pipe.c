@@ -917,12 +917,12 @@ static int pipe_run(const struct hjob j, size_t n)
 static int run_done(int rc, const struct chunk *c) { return !rc && hipEventRecord(c->kdone, c->st) != hipSuccess ? -(int)hipErrorUnknown : rc; }
 static int run_verify(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, NULL };
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, NULL, 0 };
     return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
 }
 static int run_verify_rlc(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, NULL };
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, NULL, 0 };
     return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
 }
 /* caller-supplied digests: the 64 bytes of SHA-512(R || A || M) per item travel in the message slot (EDDSA_DIGEST_BYTES wide, staged
@@ -931,19 +931,19 @@ static int run_verify_rlc(struct engine *e, const struct hjob *j, const struct c
 static int run_verify_digests(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     (void)j;
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1, 0, NULL };
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1, 0, NULL, 0 };
     return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
 }
 static int run_verify_digests_rlc(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     (void)j;
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1, 0, NULL };
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1, 0, NULL, 0 };
     return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
 }
 static int run_verify_records(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     const edk_verify_src src = { c->d_in[0] + j->rec_sig, c->d_in[0] + j->rec_pub, c->d_in[0] + j->rec_msg, NULL, j->msg_len,
-                                 j->stride, j->stride, j->stride, NULL, 0, 0, NULL };
+                                 j->stride, j->stride, j->stride, NULL, 0, 0, NULL, 0 };
     return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
 }
 static int run_sign(struct engine *e, const struct hjob *j, const struct chunk *c)
@@ -953,7 +953,7 @@ static int run_sign(struct engine *e, const struct hjob *j, const struct chunk *
 /* Ed25519ctx / Ed25519ph: verify and sign under the call's dom2 prefix (ph: msg_len 64, never an offset table) */
 static int run_verify_dom(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, j->dom };
+    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, j->dom, 0 };
     return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
 }
 static int run_sign_dom(struct engine *e, const struct hjob *j, const struct chunk *c)

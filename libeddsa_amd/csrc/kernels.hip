@@ -9,6 +9,7 @@
 //                    default (half-length scalars, halve.h), prepare / main / finish for the full-length route,
 //                    *_pair / *_quad forms for small passes; for keys that are not curve points k_verify_exact_quad (short
 //                    work lists, four lanes per item) and k_verify_exact_lane_setup / _chain (long ones, two items per lane)
+//   k_cofactor_*     the opt-in cofactored equation [8](S B - t A - R) = 0 over the items a pass rejected (cofactor_lanes.h)
 //   k_sign_*         ed25519-sha512.c:84-123 sign                    (config 5)
 //   k_dom_challenge, k_sign_dom_*             Ed25519ctx / Ed25519ph, RFC 8032 5.1: the same with dom2 in front of the hashes
 //   k_genpub_point + k_encode_finish          ed25519-sha512.c:53-67 genpub
@@ -21,6 +22,7 @@
 #include "kernel_io.h"
 #include "lanes.h"
 #include "policy_lanes.h"
+#include "cofactor_lanes.h"
 #include "quad_lanes.h"
 #include "eddsa_amd.h"
 
@@ -663,6 +665,57 @@ k_verify_policy(uint8_t* ok, const uint8_t* sigs, size_t sig_stride, const uint8
   load32(sw, sigs + 32, i, sig_stride);
   load32(aw, pubs, i, pub_stride);
   if (!verify_policy_lane(rw, sw, aw, policy)) ok[i] = 0;
+}
+
+// The opt-in cofactored equation (include/eddsa_amd.h: eddsa_amd_set_verify_equation; cofactor_lanes.h), three kernels behind
+// every writer of ok[] and in front of k_verify_policy.  The pass before them ran unchanged, in reject mode: what it accepted has
+// its key on the curve, so with S < l (k_verify_policy, S_BELOW_L forced) the cofactored equation accepts it too - an accepted R
+// equals the canonical export and decodes.  Only the REJECTED items can change their verdict:
+//   k_cofactor_list    collects them into the onlist storage, which is free after the join (all: self-check mode 2, where the
+//                      reference-order chain may have accepted an item whose key is no curve point - there every item is
+//                      listed and these kernels own every verdict)
+//   k_cofactor_points  S < l, -R decoded into the item's rtable slot, the table of -A rebuilt (the exact path may have written
+//                      over entries 2 and 3) -> the item's flags byte
+//   k_cofactor_eval    persistent blocks, one lane per listed item: the 252 doublings and 80 additions over the digit words the
+//                      prepare kernel left, - R, three doublings, the neutrality test -> ok[i]
+// Two kernels for the lane's two steps like k_verify_prepare and k_verify_main: as one they spilled 1160 bytes per lane at the
+// evaluation's 128 registers and 240 at 256; apart they take 245 and 124 and no scratch.  No route writes `digits` after its
+// prepare kernel (the halve kernels and the exact path's set-ups only read them), flags, rtable and onlist have no reader left
+// after the join, and the kernels wait on nothing but the stream.
+constexpr unsigned COFACTOR_MAX_BLOCKS = 1024;   // as many as are resident at once (four per CU)
+constexpr uint8_t COFACTOR_POINTS_GOOD = 8;      // flags[i] after k_cofactor_points: S < l, A and R on the curve (no bit of kernel_io.h's)
+__global__ void __launch_bounds__(BLOCK)
+k_cofactor_list(const uint8_t* ok, size_t n, uint32_t* list, uint32_t* offcount, int all) {
+  const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  const bool want = i < n && (all || ok[i] == 0);
+  const uint32_t slot = wave_append(offcount + EDK_COLIST_WORD, want);
+  if (want) list[slot] = (uint32_t)i;            // slot < n: one entry per item at the most
+}
+
+// over the list, not over the pass: the grid is sized for the pass, the blocks beyond the list end at once (like k_verify_halve)
+__global__ void __launch_bounds__(BLOCK, 2)
+k_cofactor_points(const uint8_t* sigs, size_t sig_stride, const uint8_t* pubs, size_t pub_stride, uint32_t* table, uint32_t* rtable,
+                  uint8_t* flags, const uint32_t* list, const uint32_t* offcount) {
+  const size_t g = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (g >= (size_t)offcount[EDK_COLIST_WORD]) return;
+  const size_t i = list[g];                      // < n: the item's own slots of the workspace
+  uint32_t rw[8], sw[8], aw[8];
+  load32(rw, sigs, i, sig_stride);
+  load32(sw, sigs + 32, i, sig_stride);
+  load32(aw, pubs, i, pub_stride);
+  flags[i] = cofactor_points_lane(rw, sw, aw, table + table_slot(i), rtable + table_slot(i)) ? COFACTOR_POINTS_GOOD : 0;
+}
+
+__global__ void __launch_bounds__(BLOCK, 4)
+k_cofactor_eval(uint8_t* ok, const uint32_t* digits, const uint32_t* table, const uint32_t* rtable, const uint32_t* base16,
+                const uint8_t* flags, const uint32_t* list, const uint32_t* offcount) {
+  const size_t listed = offcount[EDK_COLIST_WORD];
+#pragma unroll 1
+  for (size_t g = (size_t)blockIdx.x * BLOCK + threadIdx.x; g < listed; g += (size_t)gridDim.x * BLOCK) {
+    const size_t i = list[g];
+    const bool neutral = cofactor_equation_lane(digits + digit_slot(i), table + table_slot(i), rtable + table_slot(i), base16);
+    ok[i] = (uint8_t)(neutral && flags[i] == COFACTOR_POINTS_GOOD);
+  }
 }
 
 // x25519.c:144-149: x2 / z2, and 0 when z2 = 0 (fld_inv(0) = 0): such an item contributes 1 to the
@@ -1524,8 +1577,19 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
   if (bulk_done && !bulk_early) EDK_DO(hipEventRecord(bulk_done, stream));
   // 7. the join: complete when both paths are
   if (ws->exact_offcurve) EDK_DO(hipStreamWaitEvent(stream, ws->ev_exact, 0));
-  // 8. the opt-in strict rules, behind every writer of ok[] on both streams (nothing is queued for policy 0)
-  return verify_policy_launch(ok, src.sigs, src.sig_stride, src.pubs, src.pub_stride, n, src.policy, stream);
+  // 7b. the opt-in cofactored equation: the rejected items are listed and decided again (nothing is queued for equation 0)
+  if (src.equation) {
+    EDK_DO(hipMemsetAsync(ws->offcount + EDK_COLIST_WORD, 0, sizeof(uint32_t), stream));
+    EDK_LAUNCH(k_cofactor_list, dim3(blocks), dim3(BLOCK), 0, stream, ok, n, ws->onlist, ws->offcount, ws->exact_offcurve == 2);
+    EDK_LAUNCH(k_cofactor_points, dim3(blocks), dim3(BLOCK), 0, stream, src.sigs, src.sig_stride, src.pubs, src.pub_stride, ws->table,
+               ws->rtable, ws->flags, ws->onlist, ws->offcount);
+    EDK_LAUNCH(k_cofactor_eval, dim3(blocks < COFACTOR_MAX_BLOCKS ? blocks : COFACTOR_MAX_BLOCKS), dim3(BLOCK), 0, stream, ok, ws->digits,
+               ws->table, ws->rtable, base16, ws->flags, ws->onlist, ws->offcount);
+  }
+  // 8. the opt-in strict rules, behind every writer of ok[] on both streams (nothing is queued for policy 0); the cofactored
+  // equation adds S < l for the items the pass itself accepted
+  return verify_policy_launch(ok, src.sigs, src.sig_stride, src.pubs, src.pub_stride, n,
+                              src.policy | (src.equation ? EDDSA_AMD_VERIFY_S_BELOW_L : 0), stream);
 }
 
 hipError_t edk_genpub(uint8_t* pubs, const uint8_t* secs, size_t n, const uint32_t* comb, const edk_fixed_ws* ws, hipStream_t stream) {

@@ -149,6 +149,10 @@ k_rlc_tree(const uint32_t* in, uint32_t* out, size_t count) {
 // ---------------------------------------------------------------------------------------------
 // R3: per item, -A and -R as affine niels points; the routing flags
 // ---------------------------------------------------------------------------------------------
+// COFACTORED (the launcher's choice, src.equation; the arguments are the same): an R that is no canonical encoding is not
+// rejected through RLC_R_VALID but sends its group to the per-item kernels like a point of small order - the cofactored
+// equation accepts every encoding that decodes, and those kernels decide it (kernels.hip: k_cofactor_*)
+template <bool COFACTORED>
 __global__ void __launch_bounds__(RLC_BLOCK, 2)
 k_rlc_points(edk_verify_items src, size_t n, uint32_t* niels_a, uint32_t* niels_r, uint8_t* flags, uint32_t* gflags) {
   const size_t i = (size_t)blockIdx.x * RLC_BLOCK + threadIdx.x;
@@ -160,6 +164,7 @@ k_rlc_points(edk_verify_items src, size_t n, uint32_t* niels_a, uint32_t* niels_
   niels_store(niels_a + 32 * i, nl);
   load32(w, src.sigs, i, src.sig_stride);
   fl |= rlc_decode_r_lane(nl, w);
+  if (COFACTORED && (fl & RLC_R_VALID) == 0) fl |= RLC_PER_ITEM;
   niels_store(niels_r + 32 * i, nl);
   flags[i] = fl;
   if (fl & RLC_PER_ITEM) atomicOr(gflags + RLC_GROUP_WORDS * (i / RLC_G), 1u);
@@ -656,7 +661,8 @@ extern "C" hipError_t edk_verify_rlc(uint8_t* ok, uint32_t* stats, const edk_ver
   } while (count > 1);
   const uint32_t* seed = level;
   EDK_DO(hipEventRecord(ws->ev_exact, ws->side));
-  EDK_LAUNCH(k_rlc_points, dim3(blocks), dim3(RLC_BLOCK), 0, stream, items, n, niels_a, niels_r, flags, gflags);
+  const auto points = src.equation ? k_rlc_points<true> : k_rlc_points<false>;
+  EDK_LAUNCH(points, dim3(blocks), dim3(RLC_BLOCK), 0, stream, items, n, niels_a, niels_r, flags, gflags);
   EDK_DO(hipStreamWaitEvent(stream, ws->ev_exact, 0));
   EDK_LAUNCH(k_rlc_scalars, dim3((unsigned)(groups * (RLC_G / RLC_BLOCK))), dim3(RLC_BLOCK), 0, stream, n, ts, seed, flags, dig, bsum);
   EDK_LAUNCH(k_rlc_group_scalar, dim3((unsigned)((groups + 63) / 64)), dim3(64), 0, stream, n, bsum, bdig);
@@ -672,8 +678,10 @@ extern "C" hipError_t edk_verify_rlc(uint8_t* ok, uint32_t* stats, const edk_ver
              n, segpts, gflags, gok, stats);
   EDK_LAUNCH(k_rlc_verdicts, dim3(blocks), dim3(RLC_BLOCK), 0, stream, n, gok, flags, ok);
   // the opt-in strict rules over all n items (kernels.hip: k_verify_policy; nothing is queued for policy 0).  An item of a group
-  // that edk_verify_rlc_fallback decides again meets them there a second time, which changes nothing
-  if ((e = verify_policy_launch(ok, src.sigs, src.sig_stride, src.pubs, src.pub_stride, n, src.policy, stream)) != hipSuccess) return e;
+  // that edk_verify_rlc_fallback decides again meets them there a second time, which changes nothing.  The cofactored equation
+  // forces S < l: with it an accepted group holds, up to the 2^-125 bound, only items that equation accepts one by one
+  if ((e = verify_policy_launch(ok, src.sigs, src.sig_stride, src.pubs, src.pub_stride, n,
+                                src.policy | (src.equation ? (int)POLICY_S_BELOW_L : 0), stream)) != hipSuccess) return e;
 
   // groups the combination did not accept: the per-item kernels decide (edk_verify_rlc_fallback).  This is the
   // one place where the host looks at a result: the caller synchronises the stream once per pass.

@@ -15,11 +15,7 @@ enum : uint8_t { RLC_R_VALID = 1, RLC_PER_ITEM = 2 };
 constexpr int RLC_WINDOWS_A = 32, RLC_WINDOWS_R = 16, RLC_WINDOWS = RLC_WINDOWS_A + RLC_WINDOWS_R;
 constexpr int RLC_TREE_FAN = 16;                // children per node of the batch hash tree (rlc.hip: k_rlc_tree)
 
-ED_DEV bool ge_is_neutral(const ge& p) {
-  fe d;
-  fe_sub(d, p.Y, p.Z);
-  return fe_iszero(p.X) && fe_iszero(d);
-}
+// (ge_is_neutral: ge25519.h - the cofactored equation's lane, cofactor_lanes.h, tests the same way)
 // Is the curve point p (Z = 1) one of the eight points of order dividing 8?  (policy_lanes.h: the five values of y)
 ED_DEV bool ge_small_order(const ge& p) { return fe_small_order_y(p.Y); }
 ED_DEV void niels_of_affine(ge_niels& n, const ge& p) {   // p.Z = 1: ed.c:436-442 ed_precompute
