@@ -42,7 +42,7 @@ $(LIB): $(BUILD)/kernels.o $(BUILD)/rlc.o $(BUILD)/eddsa_amd.o $(BUILD)/host_pip
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -Wl,-soname,libeddsa.so.0 -o $@ $^ -lpthread -ldl
 	ln -sf libeddsa_amd.so libeddsa_amd/libeddsa.so.0
 
-$(BUILD)/rlc.o: $(CSRC)/rlc.hip $(wildcard $(CSRC)/*.h)
+$(BUILD)/rlc.o: $(CSRC)/rlc.hip $(wildcard $(CSRC)/*.h) include/eddsa_amd_debug.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

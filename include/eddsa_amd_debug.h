@@ -84,6 +84,25 @@ EDDSA_AMD_DECL int eddsa_amd_combiner_stats(uint64_t out[2]);
  * i < 22, k < 32 (the reference's ed_lookup[i][k], lib/ed.c:41-43, is (k+1)*256^i*B: the same comb with 4-bit windows;
  * row 0 coincides for k < 8); each entry 32 words: 10 radix-2^25.5 limbs of y-x, y+x, 2dxy, then 2 words of padding */
 EDDSA_AMD_DECL int eddsa_amd_dump_tables(uint32_t *base16_words, uint32_t *comb_words);
+/* What the LAST pass of the batch verification (ed25519_verify_batch_rlc*, ed25519_verify_digests_rlc*; csrc/rlc.hip) of this process
+ * on the default device left in its workspace, so that the tests can hold every device stage of it against integers: the hash tree,
+ * the scalars and their digits, the window points of the bucket kernel, the group verdicts.  Read-only: waits for the device and
+ * copies ONE region, trimmed to the pass's n items and groups = ceil(n / 8192) groups, to `out`.  Returns the bytes written, or a
+ * negative error: hipErrorNotReady when no such pass has run (a call routed to the per-item kernels, eddsa_amd_set_rlc_min_items,
+ * is none), hipErrorInvalidValue for an unknown region or when out_bytes is too small.  A call of more than 2^20 items is several
+ * passes: the last one counts. */
+#define EDDSA_AMD_RLC_INFO 0      /* three uint64: n, groups, the workspace's capacity in items */
+#define EDDSA_AMD_RLC_LEAF 1      /* 32 n bytes: the items' leaves of the batch hash tree */
+#define EDDSA_AMD_RLC_SEED 2      /* 32 bytes: the root of the tree */
+#define EDDSA_AMD_RLC_TS 3        /* 64 n bytes: per item t mod l | S mod l, 32 bytes each, little-endian */
+#define EDDSA_AMD_RLC_FLAGS 4     /* n bytes: bit 0 R is a canonical encoding of a point, bit 1 the item sends its group to the per-item kernels */
+#define EDDSA_AMD_RLC_DIG 5       /* per group 48 rows of 8192 int8: row w < 32 digit w of the keys' scalars, row 32 + w digit w of z */
+#define EDDSA_AMD_RLC_BDIG 6      /* 32 groups bytes (int8): the digits of each group's base-point scalar */
+#define EDDSA_AMD_RLC_GFLAGS 7    /* one uint32 per group: non-zero when an item sent the group to the per-item kernels */
+#define EDDSA_AMD_RLC_GOK 8       /* groups bytes: 1 the combination accepted the group, 0 it did not */
+#define EDDSA_AMD_RLC_SEG 9       /* per group 48 window points of 32 words: Y-X | Y+X | 2dT | 2Z, eight little-endian words each; entry s < 32
+                                     is window 31 - s of the keys and the base point, entry 32 + s window 15 - s of the R */
+EDDSA_AMD_DECL int eddsa_amd_debug_rlc_snapshot(int region, void *out, size_t out_bytes);
 /* the half-length route re-verifies every pair with integers before it is used (u t = v mod 8 l) and falls back to
  * (u, v) = (1, t) when the check fails; *count = how often that has happened on the default device since its
  * workspaces were allocated.  Waits for the device.  Expected, and observed over the 2^24-item batch: 0 */

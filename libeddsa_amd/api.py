@@ -282,7 +282,39 @@ def halve_rejected():
     return int(out.value)
 
 
-RLC_MIN_ITEMS_DEFAULT = 5 << 15                 # EDDSA_AMD_RLC_MIN_ITEMS_DEFAULT, include/eddsa_amd.h
+# region -> (its number in include/eddsa_amd_debug.h, dtype, bytes per item, bytes per group, the shape of one item's / group's part)
+_RLC_REGIONS = {"info": (0, np.uint64, 0, 0, ()), "leaf": (1, np.uint8, 32, 0, (32,)), "seed": (2, np.uint8, 0, 0, ()),
+                "ts": (3, np.uint8, 64, 0, (2, 32)), "flags": (4, np.uint8, 1, 0, ()), "dig": (5, np.int8, 0, 48 * 8192, (48, 8192)),
+                "bdig": (6, np.int8, 0, 32, (32,)), "gflags": (7, np.uint32, 0, 4, ()), "gok": (8, np.uint8, 0, 1, ()),
+                "seg": (9, np.uint8, 0, 48 * 128, (48, 4, 32))}
+
+
+def debug_rlc_snapshot(region):
+    """diagnostic: one region of what the last pass of the batch verification on the default device left in its workspace
+    (eddsa_amd_debug_rlc_snapshot; waits for the device, reads only), trimmed to the pass's n items and its groups: "info" -> (n,
+    groups, capacity); "seed" -> 32 bytes; "leaf" (n, 32) uint8; "ts" (n, 2, 32) uint8, t mod l and S mod l little-endian; "flags"
+    (n,) uint8; "dig" (groups, 48, 8192) int8, rows 0..31 the keys' digits and 32..47 those of z; "bdig" (groups, 32) int8;
+    "gflags" (groups,) uint32; "gok" (groups,) uint8; "seg" (groups, 48, 4, 32) uint8, the packed window points
+    Y-X | Y+X | 2dT | 2Z.  EddsaAmdError when no such pass has run."""
+    lib = _hooks()
+    code, dtype, per_item, per_group, shape = _RLC_REGIONS[region]
+    info = np.zeros(3, np.uint64)
+    _check(min(lib.eddsa_amd_debug_rlc_snapshot(ctypes.c_int(0), _np_ptr(info), _c_size(info.nbytes)), 0), "eddsa_amd_debug_rlc_snapshot")
+    n, groups = int(info[0]), int(info[1])
+    if region == "info":
+        return n, groups, int(info[2])
+    nbytes = 32 if region == "seed" else n * per_item + groups * per_group
+    out = np.zeros(nbytes, np.uint8)
+    got = lib.eddsa_amd_debug_rlc_snapshot(ctypes.c_int(code), _np_ptr(out), _c_size(nbytes))
+    _check(min(got, 0), "eddsa_amd_debug_rlc_snapshot")
+    if got != nbytes:
+        raise EddsaAmdError(f"eddsa_amd_debug_rlc_snapshot({region}): {got} bytes, expected {nbytes}")
+    if region == "seed":
+        return out.tobytes()
+    return out.view(dtype).reshape((n if per_item else groups,) + shape)
+
+
+RLC_MIN_ITEMS_DEFAULT = 5 << 15                # EDDSA_AMD_RLC_MIN_ITEMS_DEFAULT, include/eddsa_amd.h
 
 
 def set_rlc_min_items(items):

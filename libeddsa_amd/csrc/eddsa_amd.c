@@ -672,6 +672,9 @@ int rlc_on(struct engine *e, uint8_t *ok, uint32_t *stats, const edk_verify_src 
         const size_t m = n - done < CHUNK_MAX ? n - done : CHUNK_MAX;
         const edk_verify_src src = src_at(all, n, done);
         TRY(edk_verify_rlc(ok + done, stats, &src, m, e->base16, &p.v->ws, &p.v->rws, st));
+#ifdef EDDSA_AMD_DEBUG_BUILD
+        e->snap_slot = (int)(p.v - e->vs); e->snap_n = m;   /* what eddsa_amd_debug_rlc_snapshot reads */
+#endif
         pthread_mutex_unlock(&e->lk);
         hipError_t er = hipStreamSynchronize(st);
         pthread_mutex_lock(&e->lk);
@@ -1072,6 +1075,41 @@ int eddsa_amd_dump_tables(uint32_t *base16_words, uint32_t *comb_words)
     TRY(hipMemcpy(base16_words, c.e->base16, (size_t)TABLE_BASE16_ENTRIES * TABLE_ENTRY_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
     TRY(hipMemcpy(comb_words, c.e->comb, TABLE_COMB_ENTRIES * TABLE_ENTRY_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
 out:
+    leave(&c);
+    return rc;
+}
+
+/* One region of what the last pass of the batch verification on the default device left in its workspace (include/eddsa_amd_debug.h;
+ * the layout is rlc.hip's: edk_rlc_region).  Reads only, after the device has gone idle.
+ * edk_rlc_region is a WEAK reference: the host side is also linked without rlc.hip (tests/fake_hip, whose launchers decide every item
+ * one by one: there is no combination to take a snapshot of, and that build stands in for none of it) - the call is then
+ * hipErrorNotSupported. */
+extern __typeof__(edk_rlc_region) edk_rlc_region __attribute__((weak));
+int eddsa_amd_debug_rlc_snapshot(int region, void *out, size_t out_bytes)
+{
+    struct call c;
+    int rc;
+    if (!edk_rlc_region) return -(int)hipErrorNotSupported;
+    if ((rc = enter(&c, -1))) return rc;
+    pthread_mutex_lock(&c.e->lk);
+    const struct vslot *v = &c.e->vs[c.e->snap_slot];
+    const size_t n = c.e->snap_n;
+    edk_rlc_span s;
+    TRY(hipDeviceSynchronize());
+    if (n == 0 || !v->rws.base) { rc = -(int)hipErrorNotReady; goto out; }
+    if (region == EDDSA_AMD_RLC_INFO) {
+        if (!out || out_bytes < 3 * sizeof(uint64_t) || !edk_rlc_region(&s, EDDSA_AMD_RLC_GOK, v->rws.capacity, n)) { rc = -(int)hipErrorInvalidValue; goto out; }
+        const uint64_t info[3] = { n, s.bytes, v->rws.capacity };   /* (one verdict byte per group) */
+        memcpy(out, info, sizeof(info));
+        rc = (int)sizeof(info);
+        goto out;
+    }
+    if (!out || !edk_rlc_region(&s, region, v->rws.capacity, n) || out_bytes < s.bytes * s.count) { rc = -(int)hipErrorInvalidValue; goto out; }
+    for (size_t k = 0; k < s.count; k++)
+        TRY(hipMemcpy((char *)out + k * s.bytes, (const char *)v->rws.base + s.offset + k * s.stride, s.bytes, hipMemcpyDeviceToHost));
+    rc = (int)(s.bytes * s.count);
+out:
+    pthread_mutex_unlock(&c.e->lk);
     leave(&c);
     return rc;
 }

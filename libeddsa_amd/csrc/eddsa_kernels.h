@@ -133,6 +133,11 @@ hipError_t edk_msg_order(const uint32_t** perm, const edk_verify_ws* ws, const u
                          hipStream_t stream);
 size_t edk_rlc_ws_bytes(size_t capacity);
 size_t edk_rlc_hook_offset(size_t capacity);   /* of the workspace's test-hook word (256 bytes to zero at allocation; rlc.hip: k_rlc_bucket) */
+/* for eddsa_amd_debug_rlc_snapshot (the debug build; include/eddsa_amd_debug.h has the region numbers): `count` pieces of `bytes`
+ * bytes, `stride` bytes apart, from `offset` in the workspace - one region of a pass of n items, trimmed to its items and groups.
+ * Returns 0 when `region` names none or such a pass does not fit the workspace */
+typedef struct edk_rlc_span { size_t offset, bytes, stride, count; } edk_rlc_span;
+int edk_rlc_region(edk_rlc_span* out, int region, size_t capacity, size_t n);
 hipError_t edk_rlc_note_per_item(uint32_t* stats, size_t n, hipStream_t stream);
 /* one pass in two halves: edk_verify_rlc enqueues the combination and the copy of the group verdicts to rws->host_gok;
  * the caller synchronises `stream`; edk_verify_rlc_fallback hands the groups that did not pass to the per-item kernels */

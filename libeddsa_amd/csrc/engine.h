@@ -130,6 +130,9 @@ struct engine {
     hipEvent_t marks[MARK_SLOTS][4];
     struct pipe pipe;
     struct combiner comb_q;
+#ifdef EDDSA_AMD_DEBUG_BUILD
+    int snap_slot; size_t snap_n;     /* (under lk) the slot and the items of the last pass of rlc_on; snap_n = 0: none yet (eddsa_amd_debug_rlc_snapshot) */
+#endif
 };
 
 /* the device set of the *_multi entry points (eddsa_amd_init_devices) */

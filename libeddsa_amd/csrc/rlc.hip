@@ -44,6 +44,7 @@
 // bytes: the same 129 per item as verify.  The per-lane arithmetic (decoding and routing flags,
 // coefficients, digit recoding) is in rlc_lanes.h, which the host-check build also compiles.
 #include "eddsa_kernels.h"
+#include "eddsa_amd_debug.h"                     // (the region numbers of edk_rlc_region)
 #include "edk_checked.h"
 #include "kernel_io.h"
 #include "rlc_lanes.h"
@@ -90,6 +91,24 @@ __host__ inline rlc_layout rlc_carve(size_t cap) {
   L.hook = o;    o += 256;                                       // word 0: test hook (eddsa_amd_debug_withhold_handoff); word 1: waves of k_rlc_horner that gave up; zeroed at allocation
   L.total = o;
   return L;
+}
+
+// The levels of the batch hash tree over n leaves: level k (k_rlc_tree) hashes its count[k] children - the leaves for k = 0,
+// the nodes of level k - 1 after that - into count[k + 1] nodes in buffer k & 1 of the tree area, until one node is left: the
+// seed.  One walk, for the launcher and for edk_rlc_region.
+struct rlc_tree_plan { int levels; size_t count[18]; };
+__host__ inline rlc_tree_plan rlc_tree_levels(size_t n) {
+  rlc_tree_plan t;
+  t.levels = 0;
+  t.count[0] = n;
+  do {
+    t.count[t.levels + 1] = (t.count[t.levels] + RLC_TREE_FAN - 1) / RLC_TREE_FAN;
+    t.levels++;
+  } while (t.count[t.levels] > 1);
+  return t;
+}
+__host__ inline size_t rlc_tree_buffer(const rlc_layout& L, size_t cap, int which) {   // (bytes from the workspace's base)
+  return L.tree + (size_t)which * 32 * (cap / RLC_TREE_FAN + 2);
 }
 
 // what the two hashing kernels leave per item: t | S mod l (eight words each) and the leaf of the batch hash tree
@@ -610,6 +629,28 @@ extern "C" hipError_t edk_rlc_note_per_item(uint32_t* stats, size_t n, hipStream
 
 extern "C" size_t edk_rlc_ws_bytes(size_t capacity) { return capacity ? rlc_carve(capacity).total : 0; }
 extern "C" size_t edk_rlc_hook_offset(size_t capacity) { return rlc_carve(capacity).hook; }
+// Where a pass of n items through a workspace of `capacity` items left `region` (include/eddsa_amd_debug.h: EDDSA_AMD_RLC_*), trimmed
+// to its n items and its groups; 0 for a number that names none.  Only eddsa_amd_debug_rlc_snapshot asks.
+extern "C" int edk_rlc_region(edk_rlc_span* out, int region, size_t capacity, size_t n) {
+  if (n == 0 || n > capacity) return 0;
+  const rlc_layout L = rlc_carve(capacity);
+  const size_t groups = (n + RLC_G - 1) / RLC_G;
+  edk_rlc_span s = {0, 0, 0, 1};
+  switch (region) {
+    case EDDSA_AMD_RLC_LEAF:   s.offset = L.leaf;   s.bytes = n * 32; break;
+    case EDDSA_AMD_RLC_SEED:   s.offset = rlc_tree_buffer(L, capacity, (rlc_tree_levels(n).levels - 1) & 1); s.bytes = 32; break;
+    case EDDSA_AMD_RLC_TS:     s.offset = L.ts;     s.bytes = n * 64; break;
+    case EDDSA_AMD_RLC_FLAGS:  s.offset = L.flags;  s.bytes = n; break;
+    case EDDSA_AMD_RLC_DIG:    s.offset = L.dig;    s.bytes = groups * RLC_WINDOWS * (size_t)RLC_G; break;
+    case EDDSA_AMD_RLC_BDIG:   s.offset = L.bdig;   s.bytes = groups * 32; break;
+    case EDDSA_AMD_RLC_GFLAGS: s.offset = L.gflags; s.bytes = 4; s.stride = RLC_GROUP_WORDS * 4; s.count = groups; break;
+    case EDDSA_AMD_RLC_GOK:    s.offset = L.gok;    s.bytes = groups; break;
+    case EDDSA_AMD_RLC_SEG:    s.offset = L.seg;    s.bytes = groups * RLC_SEGS * VERIFY_ENTRY_WORDS * 4; break;
+    default: return 0;
+  }
+  *out = s;
+  return 1;
+}
 
 // First half of a pass: everything the combination itself needs, and the copy of the group verdicts to the
 // host (pinned).  The caller synchronises `stream` and then calls edk_verify_rlc_fallback.
@@ -631,7 +672,6 @@ extern "C" hipError_t edk_verify_rlc(uint8_t* ok, uint32_t* stats, const edk_ver
   uint32_t* gflags = reinterpret_cast<uint32_t*>(base + L.gflags);
   uint8_t* gok = base + L.gok;
   uint32_t* segpts = reinterpret_cast<uint32_t*>(base + L.seg);
-  uint32_t* tree = reinterpret_cast<uint32_t*>(base + L.tree);
   const size_t groups = (n + RLC_G - 1) / RLC_G;
   const unsigned blocks = (unsigned)((n + RLC_BLOCK - 1) / RLC_BLOCK);
   hipError_t e;
@@ -645,20 +685,16 @@ extern "C" hipError_t edk_verify_rlc(uint8_t* ok, uint32_t* stats, const edk_ver
     EDK_DO(edk_msg_order(&perm, ws, src.msg_off, src.msg_end, n, stream));
     EDK_LAUNCH(k_rlc_hash, dim3(blocks), dim3(RLC_BLOCK), 0, stream, items, n, ts, leaf, perm);
   }
-  // the batch seed: a SHA-512 tree of fan-in 64 over the leaves, on the side stream beside k_rlc_points
+  // the batch seed: a SHA-512 tree of fan-in RLC_TREE_FAN = 16 over the leaves, on the side stream beside k_rlc_points
   EDK_DO(hipEventRecord(ws->ev_prepared, stream));
   EDK_DO(hipStreamWaitEvent(ws->side, ws->ev_prepared, 0));
+  const rlc_tree_plan tp = rlc_tree_levels(n);
   const uint32_t* level = leaf;
-  uint32_t* bufs[2] = {tree, tree + 8 * (rws->capacity / RLC_TREE_FAN + 2)};
-  size_t count = n;
-  int flip = 0;
-  do {
-    const size_t next = (count + RLC_TREE_FAN - 1) / RLC_TREE_FAN;
-    EDK_LAUNCH(k_rlc_tree, dim3((unsigned)((next + 63) / 64)), dim3(64), 0, ws->side, level, bufs[flip], count);
-    level = bufs[flip];
-    flip ^= 1;
-    count = next;
-  } while (count > 1);
+  for (int k = 0; k < tp.levels; k++) {
+    uint32_t* out = reinterpret_cast<uint32_t*>(base + rlc_tree_buffer(L, rws->capacity, k & 1));
+    EDK_LAUNCH(k_rlc_tree, dim3((unsigned)((tp.count[k + 1] + 63) / 64)), dim3(64), 0, ws->side, level, out, tp.count[k]);
+    level = out;
+  }
   const uint32_t* seed = level;
   EDK_DO(hipEventRecord(ws->ev_exact, ws->side));
   const auto points = src.equation ? k_rlc_points<true> : k_rlc_points<false>;
