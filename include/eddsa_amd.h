@@ -372,6 +372,60 @@ RFC8032_EDDSA_DECL int ed25519ph_verify_batch_dev(uint8_t *ok, const uint8_t *si
 #define EDDSA_AMD_EQUATION_COFACTORED   1
 RFC8032_EDDSA_DECL int eddsa_amd_set_verify_equation(int equation);
 
+/* ---- KEY SETS: register the public keys once, verify by key index ----
+ * For callers whose signatures come from a few hundred or a few thousand keys known in advance (validator sets).  Every other
+ * form takes 32 key bytes per item and, per item, decompresses the key (a square root), builds the table 0..8 * (-A), writes its
+ * 1152 bytes into the workspace and reads them back 34 times.  A key set does that once per KEY: it holds, in HBM, the key
+ * bytes, one flag byte per key (the key decodes to a curve point) and 1152 bytes of table per key - 1.1 MB for 1024 keys - and
+ * a keyed pass takes all three by index; the host-pointer form uploads 4 bytes per item where ed25519_verify_batch uploads 32.
+ * Verdicts: ok[i] is byte for byte what ed25519_verify_batch returns for (sigs[i], keys[key_idx[i]], message i), under the
+ *   off-curve mode (0, 1, 2), the strict rules and the equation in force when each pass is enqueued; the settings in force when
+ *   the key set was created play no part.  A key set holds ANY 32-byte strings - strings that are no curve point, non-canonical
+ *   encodings, small-order points: the reference's ed_import never fails, and neither does registration.
+ * Out-of-range indices: an item with key_idx[i] >= count is rejected (ok[i] = 0) under every setting, in both forms; nothing is
+ *   read outside the key set for it, and the verdicts of its neighbours are unaffected.
+ * Creating: eddsa_amd_keyset_create takes a host pointer and runs on the default device (the rule of the host-pointer calls);
+ *   eddsa_amd_keyset_create_dev takes a device pointer and runs on the device that holds `keys`.  Both return once the tables are
+ *   built (create_dev synchronises `stream`); the caller's `keys` may be freed then.  count == 0,
+ *   count > EDDSA_AMD_KEYSET_MAX_KEYS, out == NULL or keys == NULL return -hipErrorInvalidValue and leave *out NULL (where out
+ *   is not NULL itself), before any device is touched.  On every other error *out is NULL too.
+ * Ownership and lifetime: a key set is immutable after creation and may be used by any number of threads and streams at once;
+ *   no pass writes it.  It owns its HBM, SURVIVES eddsa_amd_shutdown, and is freed only by eddsa_amd_keyset_destroy (NULL
+ *   allowed), which synchronises the key set's device before it frees: destroy it after the last call that uses it has returned.
+ * Devices: a device-pointer call whose `ok` lies on another device than the key set returns -hipErrorInvalidValue; a
+ *   host-pointer call runs on the key set's device.
+ * key_idx: packed uint32, one per item, host memory in ed25519_verify_keyed and HBM in ed25519_verify_keyed_dev.  Everything
+ *   else - layout, ragged-table rules and clamping, return values, EDDSA_AMD_STALLED, page-locked memory, threading - follows the
+ *   rules at the top.  Host-pointer keyed calls are never merged by the small-call combiner (two calls may carry two key sets).
+ * Routes: a keyed pass always takes the one-lane kernels, whatever its size (half-length scalars in off-curve modes 1 and 2,
+ *   full-length windows in mode 0 and under the cofactored equation): the four-lane forms that serve unkeyed passes below 2^18
+ *   items have no keyed counterpart, so a SMALL keyed pass pays the latency of the one-lane forms: 0.58-0.64 ms from 1 to 2^16
+ *   items, where the unkeyed pass takes 0.27-0.36 ms up to 2^14 - the two meet at about 2^16 items (profiles/verify_keyed.txt).
+ *   An item that needs the reference-order chain (a key off the curve in mode 1, every item in mode 2, an item without a short
+ *   scalar pair) gets a table of its own in the workspace, as in an unkeyed pass.
+ * Out of scope: _rlc, _multi, records, digest, Ed25519ctx / Ed25519ph and single-item forms; tables wider than nine entries.
+ * Measured (profiles/verify_keyed.txt, tools/keyed_rate.py: device-pointer forms, 2^20 valid items in HBM, 32-byte messages, one
+ * MI355X, the two passes alternating, repeat spread 0.03-0.04 ms): items under 1024 distinct keys 9.44 ms per pass through
+ * ed25519_verify_batch_dev, 8.31 ms through ed25519_verify_keyed_dev (-12.0 %: 126 M instead of 111 M verifies/s); under ONE key
+ * 9.51 / 8.23 ms (-13.4 %), under 2^16 keys 9.43 / 8.43 ms (-10.6 %), under 2^20 distinct keys - a 1.2 GB key set read in random
+ * order - 9.45 / 8.55 ms (-9.6 %).  The gain is the square root and the table store that the prepare kernel no longer does (the
+ * kernels in front of the main kernel: 2.68 -> 1.65 ms); the main kernel itself gains 1.8 % from tables that stay in L2.  Host to
+ * host, 1024 keys, ordinary memory: 10.26 -> 9.04 ms (-11.9 %).  eddsa_amd_keyset_create: 0.11 ms for 1024 keys, 1.75 ms for 2^20.
+ * ed25519_verify_batch_dev against the commit before key sets, alternating on that box: 9.413 ms against 9.407 (that build's own
+ * repeats: 9.376-9.419).
+ * (Declared with the macro of the RFC 8032 variants: tests of earlier additions count the EDDSA_AMD_DECL names.) */
+typedef struct eddsa_amd_keyset eddsa_amd_keyset;          /* opaque */
+#define EDDSA_AMD_KEYSET_MAX_KEYS ((size_t)1 << 20)
+RFC8032_EDDSA_DECL int eddsa_amd_keyset_create(eddsa_amd_keyset **out, const uint8_t *keys /* host, 32 bytes per key */, size_t count);
+RFC8032_EDDSA_DECL int eddsa_amd_keyset_create_dev(eddsa_amd_keyset **out, const uint8_t *keys /* device */, size_t count, void *stream);
+RFC8032_EDDSA_DECL void eddsa_amd_keyset_destroy(eddsa_amd_keyset *ks);
+RFC8032_EDDSA_DECL size_t eddsa_amd_keyset_count(const eddsa_amd_keyset *ks);
+RFC8032_EDDSA_DECL int eddsa_amd_keyset_device(const eddsa_amd_keyset *ks);   /* the HIP device that holds the key set */
+RFC8032_EDDSA_DECL int ed25519_verify_keyed(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                                            const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n);
+RFC8032_EDDSA_DECL int ed25519_verify_keyed_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                                                const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -611,6 +611,90 @@ def ed25519_verify_digests_rlc(sigs, pubs, digests, return_stats=False):
                         sigs, pubs, digests, stats=bool(return_stats))
 
 
+KEYSET_MAX_KEYS = 1 << 20                      # EDDSA_AMD_KEYSET_MAX_KEYS, include/eddsa_amd.h
+
+
+class Keyset:
+    """A key set (include/eddsa_amd.h: eddsa_amd_keyset): public keys registered once, in HBM with their tables, for
+    ed25519_verify_keyed.  Immutable; lives until close() (or the end of a `with` block), also across shutdown()."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("Keyset: already closed")
+        return self._h
+
+    @property
+    def count(self):
+        lib = library()
+        lib.eddsa_amd_keyset_count.restype = ctypes.c_size_t
+        return int(lib.eddsa_amd_keyset_count(self._handle()))
+
+    @property
+    def device(self):
+        return int(library().eddsa_amd_keyset_device(self._handle()))
+
+    def close(self):
+        if self._h is not None:
+            library().eddsa_amd_keyset_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def keyset_create(keys):
+    """keys: count x 32 bytes, numpy / bytes (host form, on the default device) or a CUDA uint8 tensor (on its device) -> Keyset.
+    Any 32-byte strings may be registered; returns once the tables are built."""
+    lib = library()
+    h = _c_ptr()
+    if _is_torch(keys):
+        keys = _torch_check(keys, 32, "keys")
+        _check(lib.eddsa_amd_keyset_create_dev(ctypes.byref(h), _c_ptr(keys.data_ptr()), _c_size(keys.numel() // 32), _stream()),
+               "eddsa_amd_keyset_create_dev")
+    else:
+        keys = _as_np(keys, 32, "keys")
+        _check(lib.eddsa_amd_keyset_create(ctypes.byref(h), _np_ptr(keys), _c_size(keys.size // 32)), "eddsa_amd_keyset_create")
+    return Keyset(h)
+
+
+def ed25519_verify_keyed(sigs, keyset, key_idx, msgs, msg_off=None, msg_len=None):
+    """ed25519_verify_batch with item i's key taken from a key set: keys[key_idx[i]] -> (n,) uint8, 1 = accept; an index outside
+    the key set rejects its item.  numpy inputs (key_idx: uint32) take the host form, CUDA tensors (key_idx: int32, read as
+    unsigned) the device form on torch's current stream.  msgs / msg_off / msg_len: as in ed25519_verify_batch."""
+    lib = library()
+    what = "ed25519_verify_keyed"
+    if _is_torch(sigs):
+        import torch
+        sigs = _torch_check(sigs, 64, "sigs"); msgs = _torch_check(msgs, 0, "msgs")
+        n = sigs.numel() // 64
+        if not _is_torch(key_idx) or key_idx.dtype != torch.int32 or not key_idx.is_cuda or not key_idx.is_contiguous() or key_idx.numel() != n:
+            raise ValueError(f"{what}: key_idx: expected n contiguous int32 indices on the device")
+        _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, True)
+        _torch_off_check(off, n)
+        out = torch.empty((n,), dtype=torch.uint8, device=sigs.device)
+        _check(lib.ed25519_verify_keyed_dev(_c_ptr(out.data_ptr()), keyset._handle(), _c_ptr(key_idx.data_ptr()), _c_ptr(sigs.data_ptr()),
+                                            _c_ptr(msgs.data_ptr()), _c_ptr(off.data_ptr()) if off is not None else None,
+                                            _c_size(mlen), _c_size(n), _stream()), what + "_dev")
+        return out
+    sigs = _as_np(sigs, 64, "sigs")
+    n = sigs.size // 64
+    idx = np.ascontiguousarray(np.asarray(key_idx))
+    if idx.dtype != np.uint32 or idx.size != n:
+        raise ValueError(f"{what}: key_idx: expected n uint32 indices")
+    msgs, off, mlen = _host_msgs(msgs, msg_off, msg_len, n)
+    out = np.zeros((n,), dtype=np.uint8)
+    _check(lib.ed25519_verify_keyed(_np_ptr(out), keyset._handle(), _np_ptr(idx), _np_ptr(sigs), _np_ptr(msgs),
+                                    _np_ptr(off) if off is not None else None, _c_size(mlen), _c_size(n)), what)
+    return out
+
+
 def ed25519_verify_records(records, sig_off, pub_off, msg_off, msg_len):
     """loop of ed25519_verify over fixed-size records: `records` is an (n, stride) uint8 array (numpy:
     host path, one upload; CUDA tensor: device path) holding each item's 64-byte signature at

@@ -93,11 +93,13 @@ static void ws_release(struct vslot *v)
     if (v->ws.exact_pad) HIP_NOTE(hipFree(v->ws.exact_pad));
     if (v->ws.sums) HIP_NOTE(hipFree(v->ws.sums));
     if (v->ws.domdig) HIP_NOTE(hipFree(v->ws.domdig));
+    if (v->ws.keybytes) HIP_NOTE(hipFree(v->ws.keybytes));
     v->ws.capacity = 0;
     v->ws.digits = v->ws.table = v->ws.acc = v->ws.offlist = v->ws.offcount = v->ws.exact_pad = NULL;
     v->ws.hdigits = v->ws.rtable = v->ws.sums = v->ws.onlist = v->ws.perm = v->ws.lenbins = NULL;
     v->ws.flags = NULL;
     v->ws.domdig = NULL;
+    v->ws.keybytes = NULL;
 }
 
 /* bytes of the two secret-bearing buffers of a fixed-base workspace of `cap` items */
@@ -176,6 +178,7 @@ static int ws_reserve(struct vslot *v, size_t items)
     TRY(hipMalloc((void **)&v->ws.exact_pad, EDK_EXACT_PAD_BYTES));
     TRY(hipMalloc((void **)&v->ws.sums, EDK_SUMS_BYTES));
     TRY(hipMalloc((void **)&v->ws.domdig, cap * EDK_DOM_DIGEST_BYTES));
+    TRY(hipMalloc((void **)&v->ws.keybytes, cap * 32));   /* keyed passes: the items' key bytes */
     v->ws.capacity = cap;
 out:
     if (rc) ws_release(v);
@@ -502,8 +505,9 @@ static edk_verify_src src_at(const edk_verify_src *all, size_t n, size_t done)
     edk_verify_src src = *all;
     if (all->msg_off && !all->msg_end) src.msg_end = all->msg_off + n;   /* the kernels clamp every span into [0, msg_off[n]) */
     src.sigs += done * all->sig_stride;
-    src.pubs += done * all->pub_stride;
+    if (all->pubs) src.pubs += done * all->pub_stride;   /* (a keyed pass has none) */
     if (all->msg_off) src.msg_off += done; else src.msgs += done * all->msg_stride;
+    if (all->key_idx) src.key_idx += done;   /* keyed passes: the chunk's indices are the chunk's */
     src.policy = g_verify_policy;   /* read where the pass is enqueued, like g_offcurve_mode */
     src.equation = g_verify_equation;
     return src;
@@ -758,6 +762,93 @@ int ed25519_verify_digests_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
     return leave_with(&c, rlc_on(c.e, ok, stats, &src, n, (hipStream_t)stream));
+}
+
+/* ------------------------------------------------------------------------------------------
+ * key sets (include/eddsa_amd.h): keys registered once, verified against by index
+ * ---------------------------------------------------------------------------------------- */
+
+/* edk_keyset_build is a WEAK reference, like edk_rlc_region below: the host side is also linked without the HIP translation
+ * unit (tests/fake_hip) - creating a key set is then hipErrorNotSupported */
+extern __typeof__(edk_keyset_build) edk_keyset_build __attribute__((weak));
+
+static void keyset_free(eddsa_amd_keyset *ks)
+{
+    if (ks->keys) HIP_NOTE(hipFree(ks->keys));
+    if (ks->flags) HIP_NOTE(hipFree(ks->flags));
+    if (ks->table) HIP_NOTE(hipFree(ks->table));
+    free(ks);
+}
+
+/* device < 0: host keys, on the default device; else device keys on `device`.  Returns once the tables are built. */
+static int keyset_create_on(eddsa_amd_keyset **out, const uint8_t *keys, size_t count, int device, hipStream_t st)
+{
+    struct call c;
+    int rc;
+    eddsa_amd_keyset *ks;
+    if (!edk_keyset_build) return -(int)hipErrorNotSupported;
+    if ((rc = enter(&c, device))) return rc;
+    ks = (eddsa_amd_keyset *)calloc(1, sizeof(*ks));
+    if (!ks) { rc = -(int)hipErrorOutOfMemory; goto out; }
+    ks->device = c.e->device;
+    ks->count = count;
+    TRY(hipMalloc((void **)&ks->keys, count * 32));
+    TRY(hipMalloc((void **)&ks->flags, count));
+    TRY(hipMalloc((void **)&ks->table, count * VERIFY_ITEM_TABLE_WORDS * sizeof(uint32_t)));
+    TRY(hipMemcpyAsync(ks->keys, keys, count * 32, device < 0 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+    TRY(edk_keyset_build(ks->table, ks->flags, ks->keys, count, st));
+    TRY(hipStreamSynchronize(st));
+    *out = ks;
+    ks = NULL;
+out:
+    if (ks) { HIP_NOTE(hipStreamSynchronize(st)); keyset_free(ks); }
+    leave(&c);
+    return rc;
+}
+
+int eddsa_amd_keyset_create(eddsa_amd_keyset **out, const uint8_t *keys, size_t count)
+{
+    if (out) *out = NULL;
+    if (!out || !keys || count == 0 || count > EDDSA_AMD_KEYSET_MAX_KEYS) return -(int)hipErrorInvalidValue;
+    return keyset_create_on(out, keys, count, -1, NULL);
+}
+
+int eddsa_amd_keyset_create_dev(eddsa_amd_keyset **out, const uint8_t *keys, size_t count, void *stream)
+{
+    int dev = -1, rc;
+    if (out) *out = NULL;
+    if (!out || !keys || count == 0 || count > EDDSA_AMD_KEYSET_MAX_KEYS) return -(int)hipErrorInvalidValue;
+    if ((rc = device_of(keys, &dev))) return rc;
+    return keyset_create_on(out, keys, count, dev, (hipStream_t)stream);
+}
+
+void eddsa_amd_keyset_destroy(eddsa_amd_keyset *ks)
+{
+    int saved = -1;
+    if (!ks) return;
+    HIP_NOTE(hipGetDevice(&saved));
+    HIP_NOTE(hipSetDevice(ks->device));
+    HIP_NOTE(hipDeviceSynchronize());      /* passes that read the set may still be queued */
+    keyset_free(ks);
+    if (saved >= 0) HIP_NOTE(hipSetDevice(saved));
+}
+
+size_t eddsa_amd_keyset_count(const eddsa_amd_keyset *ks) { return ks ? ks->count : 0; }
+int eddsa_amd_keyset_device(const eddsa_amd_keyset *ks) { return ks ? ks->device : -1; }
+
+int ed25519_verify_keyed_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                             const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
+{
+    struct call c;
+    int rc = 0, dev = -1;
+    if (!ks) return -(int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if ((rc = device_of(ok, &dev))) return rc;
+    if (dev != ks->device) return -(int)hipErrorInvalidValue;   /* the key set's tables live on its own device */
+    if ((rc = enter(&c, dev))) return rc;
+    const edk_verify_src src = { sigs, NULL, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL, 0,
+                                 ks->keys, ks->flags, ks->table, ks->count, key_idx };
+    return leave_with(&c, verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
 }
 
 int ed25519_sign_batch_dev(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,

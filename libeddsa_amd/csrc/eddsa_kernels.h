@@ -58,6 +58,8 @@ typedef struct edk_verify_ws {
   int exact_offcurve; /* 1: replay the reference's chain for off-curve keys (default); 0: reject them; 2: replay for every item */
   uint8_t* domdig;    /* capacity * EDK_DOM_DIGEST_BYTES: Ed25519ctx / Ed25519ph passes: the items' SHA-512(dom2 | R | A | M'), written by
                          k_dom_challenge and read by the digest forms of the prepare kernels (kernels.hip: edk_verify) */
+  uint8_t* keybytes;  /* capacity * 32: keyed passes (edk_verify_src.ks_table): the items' key bytes, written by the keyed prepare kernel;
+                         the kernels behind it read `pubs` there with stride 32 */
 } edk_verify_ws;
 
 /* where the items of a verify pass live: item i has its signature at sigs + i * sig_stride, its key
@@ -82,6 +84,15 @@ typedef struct {
                                 k_cofactor_* kernels behind the pass's verdicts and S < l to its policy (kernels.hip: edk_verify), and
                                 sends a group with a non-canonical R to the per-item kernels (rlc.hip).  Filled in by src_at like
                                 `policy`, read beside it; initialisers that stop earlier leave it 0.  Host side only */
+  /* ks_table != NULL (ed25519_verify_keyed*): a KEYED pass - `pubs` is not read; item i's key is entry key_idx[i] of a key set
+     (include/eddsa_amd.h: eddsa_amd_keyset), whose HBM these point to: ks_keys 32 bytes, ks_flags one byte (on the curve),
+     ks_table VERIFY_ITEM_TABLE_WORDS words per key, ks_count keys.  key_idx lies in HBM like the other arrays of the pass and
+     is advanced with them by src_at.  Host side only: the keyed kernels take the pointers as arguments of their own
+     (keyed_kernels.h); initialisers that stop earlier leave them NULL; never set together with `digest` or `dom` */
+  const uint8_t *ks_keys, *ks_flags;
+  const uint32_t* ks_table;
+  size_t ks_count;
+  const uint32_t* key_idx;
 } edk_verify_src;
 
 /* What the kernels take BY VALUE: the nine fields of edk_verify_src that lanes read, 72 bytes as before the flag existed.  The flag stays

@@ -30,6 +30,7 @@
 #include "eddsa_amd.h"
 #include "eddsa_amd_debug.h"
 #include "eddsa_kernels.h"
+#include "edk_keyed.h"
 
 #ifndef CHUNK_MAX                     /* (tests/fake_hip builds one variant with tiny passes: tests/c/multi_passes.c) */
 #define CHUNK_MAX ((size_t)1 << 20)   /* verify items per workspace pass: 1.6 GB of HBM workspace */
@@ -149,6 +150,16 @@ struct multi {
     int (*GroupStart)(void);
     int (*GroupEnd)(void);
     const char *(*GetErrorString)(int);
+};
+
+/* A key set (include/eddsa_amd.h): immutable after eddsa_amd_keyset_create*, owned by the caller, NOT by an engine - its HBM
+ * outlives eddsa_amd_shutdown and is freed by eddsa_amd_keyset_destroy alone.  Passes only read it. */
+struct eddsa_amd_keyset {
+    int device;
+    size_t count;
+    uint8_t *keys;                    /* HBM: count * 32 bytes */
+    uint8_t *flags;                   /* HBM: count bytes, 1 = the key decodes to a curve point */
+    uint32_t *table;                  /* HBM: count * VERIFY_ITEM_TABLE_WORDS words, 0..8 times -A per key */
 };
 
 extern pthread_rwlock_t g_table;

@@ -255,6 +255,7 @@ struct hjob {
     uint32_t *stats;                           /* rlc: host copy of the pass statistics (4 words) or NULL */
     int src_pinned;                            /* every host array of the job is page-locked: no staging */
     const edk_dom *dom;                        /* Ed25519ctx / Ed25519ph: the call's dom2 prefix (lives on the entry point's stack); else NULL */
+    const eddsa_amd_keyset *ks;                /* ed25519_verify_keyed: the caller's key set (in[1] then holds the key indices); else NULL */
 };
 
 static size_t in_w(const struct hjob *j, int i) { return j->op->in_w[i] ? j->op->in_w[i] : j->stride; }
@@ -888,12 +889,12 @@ static int combiner_submit(struct engine *e, const struct hjob *j, size_t n)
     return me.rc;
 }
 
-/* on the default device */
+/* on the default device - a keyed call: on its key set's */
 static int pipe_run(const struct hjob j, size_t n)
 {
     struct call c;
     if (n == 0) return 0;
-    int rc = enter(&c, -1);
+    int rc = enter(&c, j.ks ? j.ks->device : -1);
     if (rc) return rc;
     if (j.op->kind && n <= COMBINE_MAX_N && !(j.op->has_msgs && (j.msg_off || n * j.msg_len > COMBINE_MAX_BYTES)))
         rc = combiner_submit(c.e, &j, n);
@@ -956,6 +957,13 @@ static int run_verify_dom(struct engine *e, const struct hjob *j, const struct c
     const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, j->dom, 0 };
     return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
 }
+/* key-set verification: the chunk's second input is its slice of the key indices, the keys come from the job's key set */
+static int run_verify_keyed(struct engine *e, const struct hjob *j, const struct chunk *c)
+{
+    const edk_verify_src src = { c->d_in[0], NULL, c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, NULL, 0,
+                                 j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1] };
+    return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
+}
 static int run_sign_dom(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     return run_done(sign_dom_on(e, c->d_out, c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, c->m, j->dom, c->st), c);
@@ -979,7 +987,7 @@ RUN_1IN(run_sk_to_x, sk_to_x_on)
  * makes one combination per 2^20 items; it, the records form and the digest forms (their
  * message counterparts with the digests in the message slot, 64 bytes per item) are never merged by the combiner. */
 enum { OP_VERIFY, OP_VERIFY_RLC, OP_VERIFY_RECORDS, OP_VERIFY_DIGESTS, OP_VERIFY_DIGESTS_RLC, OP_SIGN, OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X,
-       OP_VERIFY_DOM, OP_SIGN_DOM };
+       OP_VERIFY_DOM, OP_SIGN_DOM, OP_VERIFY_KEYED };
 static const struct op g_ops[] = {
     [OP_VERIFY] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify, .wipe = WIPE_NONE, .chain = 0,
                     .kind = KIND_VERIFY, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
@@ -1001,6 +1009,9 @@ static const struct op g_ops[] = {
     [OP_VERIFY_DOM] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_dom, .wipe = WIPE_NONE, .chain = 0,
                     .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
     [OP_SIGN_DOM] = { .n_in = 2, .in_w = { 32, 32, 0 }, .out_w = 64, .has_msgs = 1, .run = run_sign_dom, .wipe = WIPE_IN0, .chain = 1, .kind = KIND_NONE },
+    /* key-set verification: signatures and 4-byte key indices; never merged - two small calls may carry different key sets */
+    [OP_VERIFY_KEYED] = { .n_in = 2, .in_w = { 64, 4, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_keyed, .wipe = WIPE_NONE, .chain = 0,
+                    .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
 };
 
 /* a call of operation `id` (in1, msgs, msg_off: NULL where the operation has none) */
@@ -1030,6 +1041,17 @@ int ed25519_verify_batch_rlc(uint8_t *ok, uint32_t stats[4], const uint8_t *sigs
     int rc = pipe_run(j, n);
     if (stats) memcpy(stats, local, sizeof(local));
     return rc;
+}
+
+/* key-set verification (include/eddsa_amd.h): 4 bytes of index per item travel where the other forms upload 32 bytes of key; the
+ * key set travels in the job, and the call runs on the key set's device */
+int ed25519_verify_keyed(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                         const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n)
+{
+    if (!ks) return -(int)hipErrorInvalidValue;
+    struct hjob j = job(OP_VERIFY_KEYED, ok, sigs, (const uint8_t *)key_idx, msgs, msg_off, msg_len);
+    j.ks = ks;
+    return pipe_run(j, n);
 }
 
 int ed25519_verify_digests(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n)

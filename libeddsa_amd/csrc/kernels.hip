@@ -17,7 +17,9 @@
 //   k_pk_to_x        ed25519-sha512.c:187-232 pk_ed25519_to_x25519
 //   k_sk_to_x        ed25519-sha512.c:239-256 sk_ed25519_to_x25519
 //   k_init_tables    generates what the reference ships as lib/ed_lookup64.h
+//   k_keyset_build, k_verify_*_keyed          key-set verification (keyed_kernels.h): the key's table by index
 #include "eddsa_kernels.h"
+#include "edk_keyed.h"
 #include "edk_checked.h"
 #include "kernel_io.h"
 #include "lanes.h"
@@ -1248,6 +1250,8 @@ k_verify_main_sums_quad(uint8_t* ok, const uint32_t* hdigits, const uint32_t* su
 
 }  // namespace ed
 
+#include "keyed_kernels.h"   // key-set verification: kernels of its own beside the ones above
+
 // =============================================================================================
 // launchers (host side of this translation unit)
 // =============================================================================================
@@ -1286,6 +1290,7 @@ struct verify_route {
   int dense;            // k_verify_exact_quad packs its items 16 to the wave whatever their number
   uint32_t main_cost;   // what runs beside k_verify_exact_lane_chain: executed instructions per item, thousands ...
   int main_all;         // ... over the whole pass (1) or over the on-curve list (0)
+  bool keyed;           // the keyed forms of the kernels above (keyed_kernels.h): tab_a is the key's table in the key set
 };
 static_assert(HALF_WINDOWS_SMALL == HALF_BITS_SMALL / 4 + 1 && HALF_WINDOWS == HALF_BITS / 4 + 1, "a bound is chosen together with its count of signed four-bit windows");
 
@@ -1300,9 +1305,15 @@ static_assert(HALF_WINDOWS_SMALL == HALF_BITS_SMALL / 4 + 1 && HALF_WINDOWS == H
 //   algo 0 (2: from 1)        2^18 .. 2^19 - 1    one lane  yes    2^138 / 35       half-length, one lane
 //   algo 0, 2                 >= 2^19             one lane  yes    2^134 / 34       half-length, one lane
 //   algo 1; 3 from 2^18; reject mode              one lane  -      -                full-length: four lanes up to 2^14 items, one above
-constexpr verify_route verify_route_of(size_t n, int algo, int exact_offcurve) {
+// A KEYED pass (ed25519_verify_keyed*) takes the one-lane forms whatever its size and whatever the algo - the four-lane and
+// three-lane kernels have no keyed form, so a small keyed pass pays the latency of the one-lane ones:
+//   keyed, modes 1 and 2      < 2^19              one lane  yes    2^138 / 35       half-length, one lane
+//                             >= 2^19             one lane  yes    2^134 / 34       half-length, one lane
+//   keyed, reject mode        any                 one lane  -      -                full-length, one lane
+constexpr verify_route verify_route_of(size_t n, int algo, int exact_offcurve, bool keyed = false) {
   if (!exact_offcurve) algo = 1;
-  verify_route r = {PREPARE_ONE, false, false, n <= QUAD_MAIN_MAX_N ? EVAL_FULL_QUAD : EVAL_FULL_ONE, 0, 0, 0, 0};
+  if (keyed) algo = exact_offcurve ? 2 : 1;   // (algo 2: the half-length route from one item on)
+  verify_route r = {PREPARE_ONE, false, false, n <= QUAD_MAIN_MAX_N && !keyed ? EVAL_FULL_QUAD : EVAL_FULL_ONE, 0, 0, 0, 0};
   // mid-size passes: the three-lane preparation of the small route (its blocks fill the SIMDs that one lane per item leaves
   // with a single wave) and the one-lane evaluation; algo 3 forces it for measurements
   if ((algo == 3 || (algo == 0 && n > PAIR_ONE_MIN_N)) && n < PAIR_ONE_MAX_N)
@@ -1323,6 +1334,7 @@ constexpr verify_route verify_route_of(size_t n, int algo, int exact_offcurve) {
   const bool half_main = r.eval == EVAL_HALF_ONE || r.eval == EVAL_HALF_ONE_LONG;
   r.main_cost = half_main ? 226u : 323u;
   r.main_all = half_main ? 0 : 1;
+  r.keyed = keyed;
   return r;
 }
 constexpr bool route_is(const verify_route& r, verify_prepare prepare, bool halve, bool wide, verify_eval eval) {
@@ -1338,6 +1350,13 @@ static_assert(route_is(verify_route_of((1 << 18) - 1, 3, 1), PREPARE_PAIR, false
 static_assert(route_is(verify_route_of(1, 3, 1), PREPARE_PAIR, false, true, EVAL_HALF_ONE_LONG) && route_is(verify_route_of(1, 2, 1), PREPARE_ONE, true, true, EVAL_HALF_ONE), "algo 2 and 3 from one item on");
 static_assert(route_is(verify_route_of(2048, 0, 0), PREPARE_ONE, false, false, EVAL_FULL_QUAD) && route_is(verify_route_of(1 << 17, 3, 0), PREPARE_ONE, false, false, EVAL_FULL_ONE) && route_is(verify_route_of(1 << 19, 2, 0), PREPARE_ONE, false, false, EVAL_FULL_ONE), "reject mode");
 static_assert(verify_route_of((1 << 16) - 1, 0, 1).lane_min == 0 && !verify_route_of((1 << 16) - 1, 0, 1).dense && verify_route_of(1 << 16, 0, 1).lane_min == 8192 && verify_route_of(1 << 16, 0, 1).dense, "EXACT_LANE_MIN_N, EXACT_DENSE_MIN_N");
+static_assert(route_is(verify_route_of(1, 0, 1, true), PREPARE_ONE, true, true, EVAL_HALF_ONE) && route_is(verify_route_of(2048, 3, 2, true), PREPARE_ONE, true, true, EVAL_HALF_ONE) &&
+              route_is(verify_route_of((1 << 19) - 1, 0, 1, true), PREPARE_ONE, true, true, EVAL_HALF_ONE) && route_is(verify_route_of(1 << 19, 1, 1, true), PREPARE_ONE, true, false, EVAL_HALF_ONE),
+              "a keyed pass in an exact mode: what verify_route_of(n, 2, 1) gives, whatever the algo");
+static_assert(route_is(verify_route_of(1, 0, 0, true), PREPARE_ONE, false, false, EVAL_FULL_ONE) && route_is(verify_route_of(1 << 14, 2, 0, true), PREPARE_ONE, false, false, EVAL_FULL_ONE) &&
+              route_is(verify_route_of(1 << 20, 0, 0, true), PREPARE_ONE, false, false, EVAL_FULL_ONE), "a keyed pass in reject mode: the one-lane full-length route, also below 2^14 items");
+static_assert(verify_route_of(1 << 20, 0, 1, true).keyed && !verify_route_of(1 << 20, 0, 1).keyed && route_is(verify_route_of(1 << 20, 0, 1, true), PREPARE_ONE, true, false, EVAL_HALF_ONE) &&
+              verify_route_of(1 << 16, 0, 1, true).lane_min == 8192 && verify_route_of(1 << 16, 0, 1, true).main_cost == 226, "keyed: the exact path's hints as for the unkeyed route");
 static_assert(verify_route_of(1 << 16, 0, 1).main_cost == 226 && verify_route_of(1 << 16, 0, 1).main_all == 0 && verify_route_of(1 << 16, 1, 1).main_cost == 323 && verify_route_of(1 << 16, 1, 1).main_all == 1, "the chain's hint follows the evaluation");
 
 // the first kernel of a verify pass: the three-lane preparation or the one-lane one.
@@ -1487,9 +1506,11 @@ hipError_t verify_policy_launch(uint8_t* ok, const uint8_t* sigs, size_t sig_str
 // workspace can be handed out again, and the caller learns that the outputs are unspecified.
 hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const uint32_t* base16,
                       const edk_verify_ws* ws, hipEvent_t* marks, hipEvent_t bulk_done, int bulk_early, hipStream_t stream) {
-  const edk_verify_src src = *srcp;
+  edk_verify_src src = *srcp;
   if (n == 0) return hipSuccess;
-  const verify_route r = verify_route_of(n, ws->algo, ws->exact_offcurve);
+  const bool keyed = src.ks_table != nullptr;     // ed25519_verify_keyed*: the keys come from a key set, by src.key_idx
+  if (keyed && (src.digest || src.dom || !src.key_idx || !src.ks_keys || !src.ks_flags || src.ks_count == 0 || src.ks_count > (size_t)UINT32_MAX)) return hipErrorInvalidValue;
+  const verify_route r = verify_route_of(n, ws->algo, ws->exact_offcurve, keyed);
   const unsigned blocks = blocks_of(n), quad_blocks = blocks_of(4 * n, QUAD_BLOCK);
   // 1. reset: both work lists' lengths, the one-lane exact path's unit counter and its stall flag
   EDK_DO(hipMemsetAsync(ws->offcount, 0, EDK_PASS_WORDS * sizeof(uint32_t), stream));
@@ -1500,7 +1521,17 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
   // 3. prepare.  Caller-supplied digests (ed25519_verify_digests*): the same preparations without the hash; everything after
   // them reads t from the workspace and does not know
   hipError_t prepared;
-  if (src.dom) {
+  if (keyed) {
+    // the keyed prepare takes the key bytes and the on-curve flag from the key set and leaves the bytes in ws->keybytes: every
+    // kernel behind it that reads `pubs` (the cofactored equation, the strict rules) reads them there
+    EDK_LAUNCH(k_verify_prepare_keyed, dim3(blocks), dim3(BLOCK), 0, stream, edk_items_of(&src), n, ws->digits, ws->flags, ws->onlist, ws->offlist,
+               ws->offcount, ws->exact_offcurve, perm, src.ks_keys, src.ks_flags, src.key_idx, (uint32_t)src.ks_count, ws->keybytes, ok);
+    // the items listed for the exact path get a table of their own (none in reject mode, which has no such path)
+    if (ws->exact_offcurve) EDK_LAUNCH(k_keyed_exact_tables, dim3(blocks), dim3(BLOCK), 0, stream, ws->table, ws->keybytes, ws->offlist, ws->offcount);
+    src.pubs = ws->keybytes;
+    src.pub_stride = 32;
+    prepared = hipSuccess;
+  } else if (src.dom) {
     // Ed25519ctx / Ed25519ph: one lane per item hashes dom2 || R || A || M' into the item's 64 bytes of ws->domdig (in order of
     // length, like every hashing kernel); from there on the pass IS a digest pass whose message slot is that area
     EDK_LAUNCH(k_dom_challenge, dim3(blocks), dim3(BLOCK), 0, stream, edk_items_of(&src), n, ws->domdig, perm, *src.dom);
@@ -1513,7 +1544,11 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
   // instead of 8.5 in 10^5; 3 % more instructions in the main kernel): an item without a short pair goes through the exact
   // path's chain, and beside a main kernel of one or two rounds of resident blocks that chain costs the pass 0.3-0.4 ms (the
   // SIMDs its waves sit on finish their tiles that much later and the grid has no slack: profiles/r04_small_grid.txt)
-  if (r.halve) {
+  if (r.halve && r.keyed) {
+    const auto k = r.wide ? k_verify_halve_keyed<HALF_BITS_SMALL> : k_verify_halve_keyed<HALF_BITS>;
+    EDK_LAUNCH(k, dim3(blocks), dim3(BLOCK), 0, stream, src.sigs, src.sig_stride, ws->digits, ws->hdigits, ws->rtable, ws->flags, ws->onlist, ws->offlist, ws->offcount,
+               ws->table, src.ks_table, src.key_idx);
+  } else if (r.halve) {
     const auto k = r.wide ? k_verify_halve<HALF_BITS_SMALL> : k_verify_halve<HALF_BITS>;
     EDK_LAUNCH(k, dim3(blocks), dim3(BLOCK), 0, stream, src.sigs, src.sig_stride, ws->digits, ws->hdigits, ws->rtable, ws->flags, ws->onlist, ws->offlist, ws->offcount);
   }
@@ -1560,11 +1595,19 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
       constexpr unsigned half_lds = MAIN_LDS_RESERVE;
       static_assert(HALF_DIGIT_WORDS * MAIN_HALF_BLOCK * 4 <= half_lds, "k_verify_main_half keeps its digit words in the block's LDS");
       const unsigned hblocks = (blocks * BLOCK + MAIN_HALF_BLOCK - 1) / MAIN_HALF_BLOCK;
+      if (r.keyed) {                             // (EVAL_HALF_ONE only: verify_route_of)
+        const auto kk = r.wide ? k_verify_main_half_keyed<HALF_WINDOWS_SMALL> : k_verify_main_half_keyed<HALF_WINDOWS>;
+        EDK_LAUNCH(kk, dim3(hblocks), dim3(MAIN_HALF_BLOCK), half_lds, stream, ok, ws->hdigits, src.ks_table, src.key_idx, ws->rtable, base16, ws->flags, ws->onlist, ws->offcount);
+        break;
+      }
       const auto k = r.eval == EVAL_HALF_ONE_LONG ? k_verify_main_half<HALF_WINDOWS_SMALL, true> : r.wide ? k_verify_main_half<HALF_WINDOWS_SMALL> : k_verify_main_half<HALF_WINDOWS>;
       EDK_LAUNCH(k, dim3(hblocks), dim3(MAIN_HALF_BLOCK), half_lds, stream, ok, ws->hdigits, ws->table, ws->rtable, base16, ws->flags, ws->onlist, ws->offcount);
     } break;
     case EVAL_FULL_QUAD: EDK_LAUNCH(k_verify_main_quad, dim3(quad_blocks), dim3(QUAD_BLOCK), 0, stream, ws->digits, ws->table, base16, ws->acc, n); break;
-    case EVAL_FULL_ONE: EDK_LAUNCH(k_verify_main, dim3(blocks), dim3(BLOCK), MAIN_LDS_RESERVE, stream, ws->digits, ws->table, base16, ws->acc); break;
+    case EVAL_FULL_ONE:
+      if (r.keyed) EDK_LAUNCH(k_verify_main_keyed, dim3(blocks), dim3(BLOCK), MAIN_LDS_RESERVE, stream, ws->digits, src.ks_table, src.key_idx, (uint32_t)src.ks_count, n, base16, ws->acc);
+      else EDK_LAUNCH(k_verify_main, dim3(blocks), dim3(BLOCK), MAIN_LDS_RESERVE, stream, ws->digits, ws->table, base16, ws->acc);
+      break;
   }
   if (marks) EDK_DO(hipEventRecord(marks[2], stream));
   if (r.eval == EVAL_FULL_ONE || r.eval == EVAL_FULL_QUAD) {
@@ -1590,6 +1633,14 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
   // equation adds S < l for the items the pass itself accepted
   return verify_policy_launch(ok, src.sigs, src.sig_stride, src.pubs, src.pub_stride, n,
                               src.policy | (src.equation ? EDDSA_AMD_VERIFY_S_BELOW_L : 0), stream);
+}
+
+// the tables and flags of a key set (edk_keyed.h): `count` keys of 32 bytes in HBM -> table (count slots of a verify item's
+// table) and flags (one byte per key).  Asynchronous on `stream`
+hipError_t edk_keyset_build(uint32_t* table, uint8_t* flags, const uint8_t* keys, size_t count, hipStream_t stream) {
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_keyset_build, dim3(blocks_of(count)), dim3(BLOCK), 0, stream, table, flags, keys, count);
+  return hipGetLastError();
 }
 
 hipError_t edk_genpub(uint8_t* pubs, const uint8_t* secs, size_t n, const uint32_t* comb, const edk_fixed_ws* ws, hipStream_t stream) {
