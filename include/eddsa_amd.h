@@ -404,6 +404,7 @@ RFC8032_EDDSA_DECL int eddsa_amd_set_verify_equation(int equation);
  *   An item that needs the reference-order chain (a key off the curve in mode 1, every item in mode 2, an item without a short
  *   scalar pair) gets a table of its own in the workspace, as in an unkeyed pass.
  * Out of scope: _rlc, _multi, records, digest, Ed25519ctx / Ed25519ph and single-item forms; tables wider than nine entries.
+ *   (Of these, _rlc has since been added for the message form: ed25519_verify_keyed_rlc, further down.)
  * Measured (profiles/verify_keyed.txt, tools/keyed_rate.py: device-pointer forms, 2^20 valid items in HBM, 32-byte messages, one
  * MI355X, the two passes alternating, repeat spread 0.03-0.04 ms): items under 1024 distinct keys 9.44 ms per pass through
  * ed25519_verify_batch_dev, 8.31 ms through ed25519_verify_keyed_dev (-12.0 %: 126 M instead of 111 M verifies/s); under ONE key
@@ -425,6 +426,48 @@ RFC8032_EDDSA_DECL int ed25519_verify_keyed(uint8_t *ok, const eddsa_amd_keyset 
                                             const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n);
 RFC8032_EDDSA_DECL int ed25519_verify_keyed_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
                                                 const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, void *stream);
+
+/* ---- KEY SETS, BATCH VERIFICATION: ed25519_verify_batch_rlc with item i's key taken from a key set ----
+ * OPT-IN like ed25519_verify_batch_rlc, for the same callers as key sets: large batches of valid signatures from a few hundred or
+ * a few thousand known keys.  The combination of a group of 8192 items is the unkeyed one with the key terms collected per key,
+ *     (sum z_i S_i) B  +  sum_k (sum_{i: key_idx[i] = k} z_i t_i mod 8 l) (-A_k)  +  sum_i z_i (-R_i)  =  0,
+ * so its key side has `count` points per group and window instead of 8192, and a pass decompresses at most `count` keys
+ * instead of one per item.
+ * Verdicts: ok[i] is what ed25519_verify_batch_rlc returns for (sigs[i], keys[key_idx[i]], message i): the same off-curve mode,
+ *   strict rules and equation (those in force when each pass is enqueued), the same bound of 2^-125 per group and the same
+ *   caveat under the cofactorless equation (two or more crafted items of small-order defect in one group may cancel).  Under
+ *   the cofactored equation the verdicts equal the per-item verdicts for every input, as in the unkeyed form.
+ * Out-of-range indices: an item with key_idx[i] >= count gets ok[i] = 0 under every setting; nothing outside the key set is
+ *   read for it, it contributes to no sum, it does not send its group to the per-item kernels, and its neighbours' verdicts are
+ *   unaffected.
+ * Per-item route: a group that fails, a group with an item that refers to a key that is off the curve or of small order, a
+ *   group that holds an R of small order and, under the cofactored equation, a group that holds an R that is no canonical
+ *   encoding are decided by the kernels of ed25519_verify_keyed, and `stats` says so (the four counters of
+ *   ed25519_verify_batch_rlc).  A key set may CONTAIN such keys: a group with no item that refers to one is still combined.
+ * Large key sets: a key set of more than 8192 keys is not combined - the digit rows and bucket lists of a pass index 8192
+ *   entries per group; the call runs as ed25519_verify_keyed and reports every item as decided per item.  Wider sets are out
+ *   of scope here.
+ * Small calls: calls of fewer items than eddsa_amd_set_rlc_min_items go to the keyed per-item kernels - one knob for the keyed
+ *   and the unkeyed form.  Measured crossover under 1024 keys: the keyed combination takes 1.03 ms for 2^16 items where the keyed
+ *   per-item pass takes 0.65 ms, and 1.20 ms for 2^17 where that pass takes 1.48 ms; the default threshold lies above it.
+ * Workspace: 64 bytes per item of workspace capacity (the per-key accumulators) and 1 MiB + 8 KiB (the pass's key points and
+ *   flags) on top of the unkeyed form's, allocated with it.
+ * Everything else follows ed25519_verify_keyed and ed25519_verify_batch_rlc where each covers the point: layout, ragged-table
+ *   rules and clamping, EDDSA_AMD_STALLED and return values; a key set or `ok` on the wrong device, NULL arguments, ownership
+ *   and threading; never merged by the small-call combiner; the device form synchronises `stream` once per pass.
+ * Still out of scope: the digest, records, _multi, Ed25519ctx / Ed25519ph and single-item forms of keyed verification.
+ * Measured (profiles/verify_keyed_rlc.txt, tools/keyed_rlc_rate.py: the three device-pointer forms alternating over the same 2^20
+ * valid items in HBM, 32-byte messages, one MI355X, repeat spread 0.01-0.04 ms for the two combinations): under 1024 keys 3.11 ms
+ * per pass against 4.47 ms through ed25519_verify_batch_rlc_dev (-30 %: 337 M instead of 235 M verifies/s) and 8.71 ms through
+ * ed25519_verify_keyed_dev; under ONE key 2.74 against 4.43 ms (-38 %); under 8192 keys 3.97 against 4.46 ms (-11 %).  The gain is
+ * the per-item square root of the key (k_rlc_points 1.79 -> 0.95 ms) and the -A windows of the bucket launch (2.47 -> 1.52 ms),
+ * less 0.3 ms for the per-key sums.  The two existing calls against the commit before this one, alternating on that box: 4.463
+ * against 4.465 ms and 8.700 against 8.714 ms, inside the older build's own repeats. */
+RFC8032_EDDSA_DECL int ed25519_verify_keyed_rlc(uint8_t *ok, uint32_t stats[4], const eddsa_amd_keyset *ks, const uint32_t *key_idx,
+                                                const uint8_t *sigs, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n);
+RFC8032_EDDSA_DECL int ed25519_verify_keyed_rlc_dev(uint8_t *ok, uint32_t *stats /* device or NULL */, const eddsa_amd_keyset *ks,
+                                                    const uint32_t *key_idx, const uint8_t *sigs, const uint8_t *msgs,
+                                                    const uint64_t *msg_off, size_t msg_len, size_t n, void *stream);
 
 #ifdef __cplusplus
 }

@@ -695,6 +695,40 @@ def ed25519_verify_keyed(sigs, keyset, key_idx, msgs, msg_off=None, msg_len=None
     return out
 
 
+def ed25519_verify_keyed_rlc(sigs, keyset, key_idx, msgs, msg_off=None, msg_len=None, return_stats=False):
+    """OPT-IN batch verification over a key set (include/eddsa_amd.h): ed25519_verify_batch_rlc with item i's key taken as
+    keys[key_idx[i]], for key sets of up to 8192 keys (wider ones run as ed25519_verify_keyed).  Inputs as ed25519_verify_keyed;
+    return_stats as ed25519_verify_batch_rlc."""
+    lib = library()
+    what = "ed25519_verify_keyed_rlc"
+    if _is_torch(sigs):
+        import torch
+        sigs = _torch_check(sigs, 64, "sigs"); msgs = _torch_check(msgs, 0, "msgs")
+        n = sigs.numel() // 64
+        if not _is_torch(key_idx) or key_idx.dtype != torch.int32 or not key_idx.is_cuda or not key_idx.is_contiguous() or key_idx.numel() != n:
+            raise ValueError(f"{what}: key_idx: expected n contiguous int32 indices on the device")
+        _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, True)
+        _torch_off_check(off, n)
+        out = torch.empty((n,), dtype=torch.uint8, device=sigs.device)
+        counts = torch.zeros((4,), dtype=torch.int32, device=sigs.device) if return_stats else None
+        _check(lib.ed25519_verify_keyed_rlc_dev(_c_ptr(out.data_ptr()), _c_ptr(counts.data_ptr()) if return_stats else None, keyset._handle(),
+                                                _c_ptr(key_idx.data_ptr()), _c_ptr(sigs.data_ptr()), _c_ptr(msgs.data_ptr()),
+                                                _c_ptr(off.data_ptr()) if off is not None else None, _c_size(mlen), _c_size(n), _stream()),
+               what + "_dev")
+        return (out, tuple(int(x) for x in counts.cpu())) if return_stats else out
+    sigs = _as_np(sigs, 64, "sigs")
+    n = sigs.size // 64
+    idx = np.ascontiguousarray(np.asarray(key_idx))
+    if idx.dtype != np.uint32 or idx.size != n:
+        raise ValueError(f"{what}: key_idx: expected n uint32 indices")
+    msgs, off, mlen = _host_msgs(msgs, msg_off, msg_len, n)
+    out = np.zeros((n,), dtype=np.uint8)
+    counts = (ctypes.c_uint32 * 4)()
+    _check(lib.ed25519_verify_keyed_rlc(_np_ptr(out), counts, keyset._handle(), _np_ptr(idx), _np_ptr(sigs), _np_ptr(msgs),
+                                        _np_ptr(off) if off is not None else None, _c_size(mlen), _c_size(n)), what)
+    return (out, tuple(int(x) for x in counts)) if return_stats else out
+
+
 def ed25519_verify_records(records, sig_off, pub_off, msg_off, msg_len):
     """loop of ed25519_verify over fixed-size records: `records` is an (n, stride) uint8 array (numpy:
     host path, one upload; CUDA tensor: device path) holding each item's 64-byte signature at

@@ -656,9 +656,10 @@ int rlc_on(struct engine *e, uint8_t *ok, uint32_t *stats, const edk_verify_src 
     int rc = 0;
     struct pass p;
     if (n == 0) return 0;
-    if (n < g_rlc_min_items) {
+    if (n < g_rlc_min_items || (all->ks_table && all->ks_count > EDK_RLC_MAX_KEYS)) {
         /* the combination has about 1 ms of latency of its own (hash tree, one serial Horner per group): below
-         * ~2^17 items the per-item kernels are faster (tools/rlc_sizes.py), so such calls go straight to them */
+         * ~2^17 items the per-item kernels are faster (tools/rlc_sizes.py), so such calls go straight to them - a keyed call
+         * (all->ks_table) to the keyed ones, and so does every call over a key set wider than a group */
         rc = verify_on(e, ok, all, n, st, NULL, 0);
         if (!rc) { hipError_t er = edk_rlc_note_per_item(stats, n, st); if (er != hipSuccess) rc = -(int)er; }
         return rc;
@@ -849,6 +850,22 @@ int ed25519_verify_keyed_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint
     const edk_verify_src src = { sigs, NULL, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL, 0,
                                  ks->keys, ks->flags, ks->table, ks->count, key_idx };
     return leave_with(&c, verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
+}
+
+/* the batch verification over a key set: the checks of ed25519_verify_keyed_dev, the pass of ed25519_verify_batch_rlc_dev */
+int ed25519_verify_keyed_rlc_dev(uint8_t *ok, uint32_t *stats, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                                 const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
+{
+    struct call c;
+    int rc = 0, dev = -1;
+    if (!ks) return -(int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if ((rc = device_of(ok, &dev))) return rc;
+    if (dev != ks->device) return -(int)hipErrorInvalidValue;
+    if ((rc = enter(&c, dev))) return rc;
+    const edk_verify_src src = { sigs, NULL, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL, 0,
+                                 ks->keys, ks->flags, ks->table, ks->count, key_idx };
+    return leave_with(&c, rlc_on(c.e, ok, stats, &src, n, (hipStream_t)stream));
 }
 
 int ed25519_sign_batch_dev(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,

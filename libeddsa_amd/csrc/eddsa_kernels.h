@@ -139,6 +139,8 @@ typedef struct edk_rlc_ws {
   void* host_gok;     /* pinned host memory, one byte per group of the largest pass: the group verdicts */
 } edk_rlc_ws;
 #define EDK_RLC_HOST_BYTES 4096
+#define EDK_RLC_MAX_KEYS 8192       /* a keyed pass of the combination (src.ks_table set) indexes its digit rows and bucket lists by key: at most
+                                       one group's width of keys (rlc.hip: RLC_G); rlc_on sends wider key sets to the per-item kernels */
 /* ragged messages: *perm = ws->perm filled with the pass's items in order of message length, or NULL (kernels.hip) */
 hipError_t edk_msg_order(const uint32_t** perm, const edk_verify_ws* ws, const uint64_t* msg_off, const uint64_t* msg_end, size_t n,
                          hipStream_t stream);

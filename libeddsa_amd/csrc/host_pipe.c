@@ -964,6 +964,13 @@ static int run_verify_keyed(struct engine *e, const struct hjob *j, const struct
                                  j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1] };
     return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
 }
+/* the batch verification over a key set: the inputs of run_verify_keyed, the pass and the statistics of run_verify_rlc */
+static int run_verify_keyed_rlc(struct engine *e, const struct hjob *j, const struct chunk *c)
+{
+    const edk_verify_src src = { c->d_in[0], NULL, c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, NULL, 0,
+                                 j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1] };
+    return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
+}
 static int run_sign_dom(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     return run_done(sign_dom_on(e, c->d_out, c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, c->m, j->dom, c->st), c);
@@ -987,7 +994,7 @@ RUN_1IN(run_sk_to_x, sk_to_x_on)
  * makes one combination per 2^20 items; it, the records form and the digest forms (their
  * message counterparts with the digests in the message slot, 64 bytes per item) are never merged by the combiner. */
 enum { OP_VERIFY, OP_VERIFY_RLC, OP_VERIFY_RECORDS, OP_VERIFY_DIGESTS, OP_VERIFY_DIGESTS_RLC, OP_SIGN, OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X,
-       OP_VERIFY_DOM, OP_SIGN_DOM, OP_VERIFY_KEYED };
+       OP_VERIFY_DOM, OP_SIGN_DOM, OP_VERIFY_KEYED, OP_VERIFY_KEYED_RLC };
 static const struct op g_ops[] = {
     [OP_VERIFY] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify, .wipe = WIPE_NONE, .chain = 0,
                     .kind = KIND_VERIFY, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
@@ -1012,6 +1019,9 @@ static const struct op g_ops[] = {
     /* key-set verification: signatures and 4-byte key indices; never merged - two small calls may carry different key sets */
     [OP_VERIFY_KEYED] = { .n_in = 2, .in_w = { 64, 4, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_keyed, .wipe = WIPE_NONE, .chain = 0,
                     .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
+    /* its batch verification: the inputs of OP_VERIFY_KEYED, one combination per chunk like OP_VERIFY_RLC */
+    [OP_VERIFY_KEYED_RLC] = { .n_in = 2, .in_w = { 64, 4, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_keyed_rlc, .wipe = WIPE_NONE, .chain = 0,
+                    .kind = KIND_NONE, .chunk = CHUNK_MAX, .first_chunk = CHUNK_MAX, .reports = 1 },
 };
 
 /* a call of operation `id` (in1, msgs, msg_off: NULL where the operation has none) */
@@ -1052,6 +1062,19 @@ int ed25519_verify_keyed(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t
     struct hjob j = job(OP_VERIFY_KEYED, ok, sigs, (const uint8_t *)key_idx, msgs, msg_off, msg_len);
     j.ks = ks;
     return pipe_run(j, n);
+}
+
+int ed25519_verify_keyed_rlc(uint8_t *ok, uint32_t stats[4], const eddsa_amd_keyset *ks, const uint32_t *key_idx,
+                             const uint8_t *sigs, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n)
+{
+    uint32_t local[4] = { 0, 0, 0, 0 };
+    if (!ks) return -(int)hipErrorInvalidValue;
+    struct hjob j = job(OP_VERIFY_KEYED_RLC, ok, sigs, (const uint8_t *)key_idx, msgs, msg_off, msg_len);
+    j.ks = ks;
+    j.stats = local;
+    int rc = pipe_run(j, n);
+    if (stats) memcpy(stats, local, sizeof(local));
+    return rc;
 }
 
 int ed25519_verify_digests(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n)

@@ -43,6 +43,8 @@
 // additions per item instead of the per-item kernel's 252 doublings + 80 additions.  Algorithmic HBM
 // bytes: the same 129 per item as verify.  The per-lane arithmetic (decoding and routing flags,
 // coefficients, digit recoding) is in rlc_lanes.h, which the host-check build also compiles.
+// Over a key set (ed25519_verify_keyed_rlc*; edk_verify_src.ks_table set) the key terms of a group are collected per key - one
+// scalar and one point per KEY and window instead of one per item: rlc_keyed.h, included below, and k_rlc_bucket<true>.
 #include "eddsa_kernels.h"
 #include "eddsa_amd_debug.h"                     // (the region numbers of edk_rlc_region)
 #include "edk_checked.h"
@@ -53,6 +55,7 @@
 namespace ed {
 
 constexpr int RLC_G = 8192;                      // items per group
+static_assert(RLC_G == EDK_RLC_MAX_KEYS, "a keyed pass has at most one group's width of keys");
 constexpr int RLC_BUCKETS = 128;                 // |digit| in 1..128
 constexpr int RLC_SEG_WINDOWS = 1;               // windows per workgroup (2 and 4, with the doublings in between, measured slower)
 constexpr int RLC_SEGS_A = RLC_WINDOWS_A / RLC_SEG_WINDOWS, RLC_SEGS_R = RLC_WINDOWS_R / RLC_SEG_WINDOWS;
@@ -69,7 +72,7 @@ constexpr uint8_t RLC_UNDECIDED = 2;             // gok[g]: k_rlc_horner gave th
 // workspace carving (bytes), capacity = a multiple of 2048 items
 struct rlc_layout {
   size_t groups;
-  size_t ts, leaf, niels_a, niels_r, dig, flags, bsum, bdig, gflags, gok, seg, tree, hook, total;
+  size_t ts, leaf, niels_a, niels_r, dig, flags, bsum, bdig, gflags, gok, seg, tree, hook, keypts, keyflags, keyacc, total;
 };
 __host__ __device__ inline size_t rlc_align(size_t x) { return (x + 255) & ~(size_t)255; }
 __host__ inline rlc_layout rlc_carve(size_t cap) {
@@ -89,6 +92,13 @@ __host__ inline rlc_layout rlc_carve(size_t cap) {
   L.seg = o;     o += rlc_align(L.groups * RLC_SEGS * VERIFY_ENTRY_WORDS * 4);      // window points, cached form (packed)
   L.tree = o;    o += rlc_align((cap / RLC_TREE_FAN + 2) * 32 * 2);
   L.hook = o;    o += 256;                                       // word 0: test hook (eddsa_amd_debug_withhold_handoff); word 1: waves of k_rlc_horner that gave up; zeroed at allocation
+  // keyed passes (rlc_keyed.h), BEHIND everything an unkeyed pass uses, so that every offset above is what it was: the pass's key
+  // points, one routing flag per key, and per group up to RLC_G accumulators of 64 bytes (a pass over `count` keys uses the
+  // first groups * count of them, packed) - 64 bytes per item of capacity, rounded up to whole groups, and 1 MiB + 8 KiB.  Not
+  // carved out of the per-item -A area a keyed pass leaves idle: at the smallest capacity (2048 items) that area is 256 KiB
+  L.keypts = o;  o += rlc_align((size_t)RLC_G * 128);
+  L.keyflags = o; o += rlc_align((size_t)RLC_G);
+  L.keyacc = o;  o += rlc_align(L.groups * (size_t)RLC_G * 64);
   L.total = o;
   return L;
 }
@@ -433,9 +443,13 @@ k_rlc_final(size_t n, const uint32_t* segpts, const uint32_t* gflags, uint8_t* g
   rlc_group_verdict(r, q, live, g, n, gflags, gok, stats);
 }
 
+// KEYED (a pass over a key set, rlc_keyed.h): the -A windows' digit rows are indexed by KEY and their points are the pass's
+// `count` key points at niels_a, the same for every group; entries of a row from `count` on are zero and are not scanned.
+// The unkeyed instantiation ignores `count` and is the kernel it was (profiles/verify_keyed_rlc.txt, section 1).
+template <bool KEYED>
 __global__ void __launch_bounds__(RLC_LANES, 2)
 k_rlc_bucket(size_t n, const int8_t* dig, const int8_t* bdig, const uint32_t* niels_a, const uint32_t* niels_r,
-             const uint32_t* base16, uint32_t* segpts, uint32_t* gflags, const uint32_t* hook) {
+             const uint32_t* base16, uint32_t* segpts, uint32_t* gflags, const uint32_t* hook, uint32_t count) {
   __shared__ rlc_lds s;
   const size_t groups = (n + RLC_G - 1) / RLC_G;
   // heaviest windows first (by_weight = 0..47): -A's windows 31..16, then windows 15..0 of -A and -R in turn (k_rlc_horner)
@@ -444,7 +458,9 @@ k_rlc_bucket(size_t n, const int8_t* dig, const int8_t* bdig, const uint32_t* ni
   const bool is_a = by_weight < 16 || ((by_weight - 16) & 1) == 0;
   const int w = by_weight < 16 ? RLC_WINDOWS_A - 1 - by_weight : 15 - ((by_weight - 16) >> 1);
   const int seg = is_a ? RLC_WINDOWS_A - 1 - w : RLC_SEGS_A + RLC_WINDOWS_R - 1 - w;   // the window point's place among the group's
-  const uint32_t* pts = (is_a ? niels_a : niels_r) + g * (size_t)RLC_G * 32;
+  const uint32_t* pts = KEYED && is_a ? niels_a : (is_a ? niels_a : niels_r) + g * (size_t)RLC_G * 32;
+  // lane l's 16-byte loads j cover entries 16 (64 j + l) .. + 15 of the row: those that begin below `count`
+  const int loads = KEYED && is_a ? (int)((count + 16 * RLC_LANES - 1) / (16 * RLC_LANES)) : RLC_G / (16 * RLC_LANES);
   const int8_t* drow = dig + (g * RLC_WINDOWS + (is_a ? 0 : RLC_WINDOWS_A)) * (size_t)RLC_G;
   const int l = (int)threadIdx.x;
   static_assert(RLC_SEG_WINDOWS == 1 && RLC_BUCKETS == 2 * RLC_LANES, "one window per wave, two buckets per lane");
@@ -459,7 +475,7 @@ k_rlc_bucket(size_t n, const int8_t* dig, const int8_t* bdig, const uint32_t* ni
   const uint4* dw = reinterpret_cast<const uint4*>(drow + (size_t)w * RLC_G);
   const int bd = (is_a && l == 0) ? (int)bdig[32 * g + w] : 0;               // lane 0 also files the base point
 #pragma unroll 1
-  for (int j = 0; j < RLC_G / (16 * RLC_LANES); j++) {
+  for (int j = 0; j < loads; j++) {
     const uint4 v = dw[j * RLC_LANES + l];
     const uint32_t dd[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -485,7 +501,7 @@ k_rlc_bucket(size_t n, const int8_t* dig, const int8_t* bdig, const uint32_t* ni
   }
   __syncthreads();
 #pragma unroll 1
-  for (int j = 0; j < RLC_G / (16 * RLC_LANES); j++) {
+  for (int j = 0; j < loads; j++) {
     const uint4 v = dw[j * RLC_LANES + l];
     const uint32_t dd[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -606,10 +622,12 @@ __global__ void __launch_bounds__(RLC_BLOCK)
 k_rlc_verdicts(size_t n, const uint8_t* gok, const uint8_t* flags, uint8_t* ok) {
   const size_t i = (size_t)blockIdx.x * RLC_BLOCK + threadIdx.x;
   if (i >= n) return;
-  if (gok[i / RLC_G]) ok[i] = flags[i] & RLC_R_VALID;
+  if (gok[i / RLC_G] == 1) ok[i] = flags[i] & RLC_R_VALID;    // (an undecided group, RLC_UNDECIDED, fails closed)
 }
 
 }  // namespace ed
+
+#include "rlc_keyed.h"
 
 using namespace ed;
 
@@ -676,9 +694,23 @@ extern "C" hipError_t edk_verify_rlc(uint8_t* ok, uint32_t* stats, const edk_ver
   const unsigned blocks = (unsigned)((n + RLC_BLOCK - 1) / RLC_BLOCK);
   hipError_t e;
 
+  // a pass over a key set (ed25519_verify_keyed_rlc*; rlc_keyed.h): at most RLC_G keys - rlc_on sends wider sets to the per-item kernels
+  const bool keyed = src.ks_table != nullptr;
+  if (keyed && (src.digest || src.dom || !src.key_idx || !src.ks_keys || src.ks_count == 0 || src.ks_count > (size_t)RLC_G)) return hipErrorInvalidValue;
+  const uint32_t count = keyed ? (uint32_t)src.ks_count : 0u;
+  uint32_t* keypts = reinterpret_cast<uint32_t*>(base + L.keypts);
+  uint8_t* keyflags = base + L.keyflags;
+  unsigned long long* keyacc = reinterpret_cast<unsigned long long*>(base + L.keyacc);
+
   EDK_DO(hipMemsetAsync(gflags, 0, groups * RLC_GROUP_WORDS * 4, stream));
   const edk_verify_items items = edk_items_of(&src);
-  if (src.digest) {
+  if (keyed) {
+    EDK_DO(hipMemsetAsync(keyacc, 0, groups * count * (size_t)RLC_KEY_ACC_WORDS * 8, stream));
+    EDK_LAUNCH(k_rlc_keys, dim3((count + RLC_BLOCK - 1) / RLC_BLOCK), dim3(RLC_BLOCK), 0, stream, src.ks_keys, count, keypts, keyflags);
+    const uint32_t* perm = nullptr;
+    EDK_DO(edk_msg_order(&perm, ws, src.msg_off, src.msg_end, n, stream));
+    EDK_LAUNCH(k_rlc_hash_keyed, dim3(blocks), dim3(RLC_BLOCK), 0, stream, items, n, ts, leaf, perm, src.ks_keys, src.key_idx, count, ws->keybytes);
+  } else if (src.digest) {
     EDK_LAUNCH(k_rlc_hash_digest, dim3(blocks), dim3(RLC_BLOCK), 0, stream, items, n, ts, leaf);
   } else {
     const uint32_t* perm = nullptr;
@@ -697,14 +729,24 @@ extern "C" hipError_t edk_verify_rlc(uint8_t* ok, uint32_t* stats, const edk_ver
   }
   const uint32_t* seed = level;
   EDK_DO(hipEventRecord(ws->ev_exact, ws->side));
-  const auto points = src.equation ? k_rlc_points<true> : k_rlc_points<false>;
-  EDK_LAUNCH(points, dim3(blocks), dim3(RLC_BLOCK), 0, stream, items, n, niels_a, niels_r, flags, gflags);
-  EDK_DO(hipStreamWaitEvent(stream, ws->ev_exact, 0));
-  EDK_LAUNCH(k_rlc_scalars, dim3((unsigned)(groups * (RLC_G / RLC_BLOCK))), dim3(RLC_BLOCK), 0, stream, n, ts, seed, flags, dig, bsum);
+  const unsigned group_blocks = (unsigned)(groups * (RLC_G / RLC_BLOCK));
+  if (keyed) {
+    const auto points = src.equation ? k_rlc_points_keyed<true> : k_rlc_points_keyed<false>;
+    EDK_LAUNCH(points, dim3(blocks), dim3(RLC_BLOCK), 0, stream, items, n, src.key_idx, count, keyflags, niels_r, flags, gflags);
+    EDK_DO(hipStreamWaitEvent(stream, ws->ev_exact, 0));
+    EDK_LAUNCH(k_rlc_scalars_keyed, dim3(group_blocks), dim3(RLC_BLOCK), 0, stream, n, ts, seed, flags, src.key_idx, count, dig, bsum, keyacc);
+    EDK_LAUNCH(k_rlc_key_scalars, dim3(group_blocks), dim3(RLC_BLOCK), 0, stream, groups, count, keyacc, dig);
+  } else {
+    const auto points = src.equation ? k_rlc_points<true> : k_rlc_points<false>;
+    EDK_LAUNCH(points, dim3(blocks), dim3(RLC_BLOCK), 0, stream, items, n, niels_a, niels_r, flags, gflags);
+    EDK_DO(hipStreamWaitEvent(stream, ws->ev_exact, 0));
+    EDK_LAUNCH(k_rlc_scalars, dim3(group_blocks), dim3(RLC_BLOCK), 0, stream, n, ts, seed, flags, dig, bsum);
+  }
   EDK_LAUNCH(k_rlc_group_scalar, dim3((unsigned)((groups + 63) / 64)), dim3(64), 0, stream, n, bsum, bdig);
   EDK_DO(hipEventRecord(ws->ev_prepared, stream));
-  EDK_LAUNCH(k_rlc_bucket, dim3((unsigned)(groups * RLC_SEGS)), dim3(RLC_LANES), 0, stream, n, dig, bdig, niels_a, niels_r, base16, segpts, gflags,
-             reinterpret_cast<const uint32_t*>(base + L.hook));
+  const auto bucket = keyed ? k_rlc_bucket<true> : k_rlc_bucket<false>;
+  EDK_LAUNCH(bucket, dim3((unsigned)(groups * RLC_SEGS)), dim3(RLC_LANES), 0, stream, n, dig, bdig, keyed ? keypts : niels_a, niels_r, base16, segpts, gflags,
+             reinterpret_cast<const uint32_t*>(base + L.hook), count);
   EDK_DO(hipStreamWaitEvent(ws->side, ws->ev_prepared, 0));    // (queued after the bucket launch: see k_rlc_horner)
   EDK_LAUNCH(k_rlc_horner, dim3((unsigned)((groups + RLC_HORNER_GROUPS - 1) / RLC_HORNER_GROUPS)), dim3(4 * RLC_HORNER_GROUPS), 0, ws->side,
              n, segpts, gflags, gok, stats, reinterpret_cast<uint32_t*>(base + L.hook) + 1);
@@ -716,7 +758,8 @@ extern "C" hipError_t edk_verify_rlc(uint8_t* ok, uint32_t* stats, const edk_ver
   // the opt-in strict rules over all n items (kernels.hip: k_verify_policy; nothing is queued for policy 0).  An item of a group
   // that edk_verify_rlc_fallback decides again meets them there a second time, which changes nothing.  The cofactored equation
   // forces S < l: with it an accepted group holds, up to the 2^-125 bound, only items that equation accepts one by one
-  if ((e = verify_policy_launch(ok, src.sigs, src.sig_stride, src.pubs, src.pub_stride, n,
+  // (a keyed pass: the items' key bytes are where k_rlc_hash_keyed left them)
+  if ((e = verify_policy_launch(ok, src.sigs, src.sig_stride, keyed ? ws->keybytes : src.pubs, keyed ? 32 : src.pub_stride, n,
                                 src.policy | (src.equation ? (int)POLICY_S_BELOW_L : 0), stream)) != hipSuccess) return e;
 
   // groups the combination did not accept: the per-item kernels decide (edk_verify_rlc_fallback).  This is the
@@ -734,13 +777,14 @@ extern "C" hipError_t edk_verify_rlc_fallback(uint8_t* ok, const edk_verify_src*
   const uint8_t* h_gok = static_cast<const uint8_t*>(rws->host_gok);
   hipError_t e;
   for (size_t g = 0; g < groups;) {
-    if (h_gok[g]) { g++; continue; }
+    if (h_gok[g] == 1) { g++; continue; }     // (anything else - rejected, or RLC_UNDECIDED - is decided per item)
     size_t g1 = g;
-    while (g1 < groups && !h_gok[g1]) g1++;
+    while (g1 < groups && h_gok[g1] != 1) g1++;
     const size_t lo = g * RLC_G, hi = g1 * RLC_G < n ? g1 * RLC_G : n;
     edk_verify_src sub = src;
     sub.sigs += lo * src.sig_stride;
-    sub.pubs += lo * src.pub_stride;
+    if (src.pubs) sub.pubs += lo * src.pub_stride;
+    if (src.key_idx) sub.key_idx += lo;          // (a keyed pass: edk_verify takes the route of ed25519_verify_keyed)
     if (src.msg_off) sub.msg_off += lo; else sub.msgs += lo * src.msg_stride;
     if ((e = edk_verify(ok + lo, &sub, hi - lo, base16, ws, nullptr, nullptr, 0, stream)) != hipSuccess) return e;
     g = g1;
