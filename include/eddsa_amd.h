@@ -469,6 +469,52 @@ RFC8032_EDDSA_DECL int ed25519_verify_keyed_rlc_dev(uint8_t *ok, uint32_t *stats
                                                     const uint32_t *key_idx, const uint8_t *sigs, const uint8_t *msgs,
                                                     const uint64_t *msg_off, size_t msg_len, size_t n, void *stream);
 
+/* ---- KEY SETS WITH A COMB PER KEY: verify without the doubling chain ----
+ * OPT-IN at creation, for key sets of up to 2^14 keys.  A plain key set saves the per-item square root and table, but every valid
+ * item still runs the full chain (132 doublings and about 84 additions on the half-length route, 252 and 80 on the full-length
+ * one).  A key known in advance allows fixed-base arithmetic for BOTH scalars: the 6-bit signed comb that signing uses for B
+ * (44 lookups, 6 doublings), built once per key on -A, makes S B - t A cost 88 additions and 6 doublings - no half-length
+ * scalars, no decompression of R, no per-item table.
+ * What a comb key set is: a key set.  It holds everything a plain one holds (key bytes, flags, the nine-entry tables: the exact
+ *   path, the cofactored kernels and _rlc read those) and, on top, 704 entries of 128 bytes per key: 88 KiB of HBM per key, 88 MiB
+ *   for 1024 keys, 1.375 GiB at the limit of EDDSA_AMD_KEYSET_COMB_MAX_KEYS = 2^14 keys.  eddsa_amd_keyset_bytes reports the HBM a
+ *   set holds (plain sets too), eddsa_amd_keyset_is_comb whether it has the comb.  Callers with more keys use a plain set.
+ * Every call that takes a key set accepts it - ed25519_verify_keyed[_dev], ed25519_verify_keyed_rlc[_dev]; there is no new verify
+ *   entry point.  A keyed pass over a comb set takes the comb route in every mode (off-curve modes 0, 1 and 2) and at every size:
+ *   the keyed prepare kernel, one main kernel that reads S B through the library's comb of B and t (-A) through the key's comb,
+ *   and the finish kernel of the full-length route; in modes 1 and 2 the exact path serves the keys off the curve (mode 2: every
+ *   item) as on that route.  The route is what the caller chose at creation: there is no size switch.  The combination of
+ *   ed25519_verify_keyed_rlc does not use the comb; the groups it sends to the per-item kernels take the comb route.
+ * Verdicts: ok[i] is byte for byte what ed25519_verify_keyed returns over a plain key set of the same keys: in every mode,
+ *   under every strict rule and under both equations; out-of-range indices are rejected as there.
+ * The S reduction: S is not range-checked by default and may be any 256-bit string, while the comb covers 264 bits of S + offset;
+ *   the comb's digits are cut from S mod l (B has order l: (S mod l) B = S B), which every route's prepare kernel computes.  Under
+ *   the strict rules and the cofactored equation S < l is checked on the raw signature bytes, as for every other route.
+ * Creating: eddsa_amd_keyset_create_comb / _create_comb_dev follow eddsa_amd_keyset_create / _create_dev - count == 0,
+ *   count > EDDSA_AMD_KEYSET_COMB_MAX_KEYS, out == NULL or keys == NULL return -hipErrorInvalidValue and leave *out NULL, before any
+ *   device is touched; a failed allocation returns its HIP error with *out NULL.  Lifetime, devices, eddsa_amd_keyset_destroy and
+ *   "survives eddsa_amd_shutdown" are those of a plain key set; the four functions above and plain key sets behave as before.
+ * Out of scope: four-lane forms of the comb route, combs wider than 6 bits, the digest, records, _multi and ctx / ph keyed forms.
+ * Measured (profiles/verify_keyed_comb.txt, tools/keyed_comb_rate.py: device-pointer forms over the same 2^20 valid items in HBM,
+ * 32-byte messages, one MI355X, ed25519_verify_batch_dev / ed25519_verify_keyed_dev over a plain set / the same call over a comb
+ * set alternating, repeat spread 0.01-0.14 ms): under 1024 keys 9.95 / 8.78 / 3.84 ms per pass in mode 1 (-56 % against the plain
+ * set: 273 M instead of 119 M verifies/s), 11.02 / 9.48 / 3.79 ms in mode 0 (-60 %), 11.07 / 9.53 / 3.83 ms under the cofactored
+ * equation (-60 %); under ONE key 9.82 / 8.62 / 3.72 ms; under 16 384 keys - a 1.4 GiB comb read in random order - 9.95 / 8.85 /
+ * 4.21 ms (-52 %).  Per kernel under 1024 keys: prepare 0.23 ms (the plain route: 1.69 with halve), main 3.44 ms (7.02), finish
+ * 0.17 ms.  Small passes under 1024 keys (unkeyed / plain / comb): 2^7 items 0.24 / 0.58 / 0.32 ms, 2^10 0.26 / 0.59 / 0.33,
+ * 2^14 0.33 / 0.60 / 0.34, 2^16 0.64 / 0.62 / 0.35 - the comb route closes most of the small-pass gap of key sets but is NOT
+ * faster than the unkeyed four-lane kernels up to 2^14 items (+32 % at 2^7, +4 % at 2^14); the crossover lies between 2^14 and
+ * 2^16 items, and against a plain key set the comb route is faster at every size and key count measured.
+ * eddsa_amd_keyset_create_comb from host keys: 0.79 ms for 1024 keys (89.2 MiB held), 3.8-114 ms for 16 384 keys (1426.5 MiB
+ * held; the allocation dominates and varies), where the plain sets take 0.10 and 0.14 ms.  The two unchanged calls against the
+ * commit before this one, alternating in fresh processes on that box: 9.923 against 9.917 ms (that build's own repeats:
+ * 9.870-10.021) and 8.708 against 8.725 ms (8.690-8.802). */
+#define EDDSA_AMD_KEYSET_COMB_MAX_KEYS ((size_t)1 << 14)     /* 88 KiB per key: 1.375 GiB at the limit */
+RFC8032_EDDSA_DECL int eddsa_amd_keyset_create_comb(eddsa_amd_keyset **out, const uint8_t *keys /* host */, size_t count);
+RFC8032_EDDSA_DECL int eddsa_amd_keyset_create_comb_dev(eddsa_amd_keyset **out, const uint8_t *keys /* device */, size_t count, void *stream);
+RFC8032_EDDSA_DECL int eddsa_amd_keyset_is_comb(const eddsa_amd_keyset *ks);   /* 1 / 0; NULL: 0 */
+RFC8032_EDDSA_DECL size_t eddsa_amd_keyset_bytes(const eddsa_amd_keyset *ks);  /* HBM the set holds; NULL: 0 */
+
 #ifdef __cplusplus
 }
 #endif

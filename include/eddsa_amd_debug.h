@@ -84,6 +84,10 @@ EDDSA_AMD_DECL int eddsa_amd_combiner_stats(uint64_t out[2]);
  * i < 22, k < 32 (the reference's ed_lookup[i][k], lib/ed.c:41-43, is (k+1)*256^i*B: the same comb with 4-bit windows;
  * row 0 coincides for k < 8); each entry 32 words: 10 radix-2^25.5 limbs of y-x, y+x, 2dxy, then 2 words of padding */
 EDDSA_AMD_DECL int eddsa_amd_dump_tables(uint32_t *base16_words, uint32_t *comb_words);
+/* copy ONE key's comb of a comb key set (eddsa_amd_keyset_create_comb) out: 704 entries of 32 words, entry 32 row + m - 1 =
+ * m * 4096^row * (-A), row < 22, m = 1..32, each Y-X | Y+X | 2dT | 2Z as eight little-endian words of a value below 2^255.
+ * -hipErrorInvalidValue for NULL, a plain key set or key >= count */
+EDDSA_AMD_DECL int eddsa_amd_debug_keyset_comb_read(const eddsa_amd_keyset *ks, size_t key, uint32_t *words);
 /* What the LAST pass of the batch verification (ed25519_verify_batch_rlc*, ed25519_verify_digests_rlc*; csrc/rlc.hip) of this process
  * on the default device left in its workspace, so that the tests can hold every device stage of it against integers: the hash tree,
  * the scalars and their digits, the window points of the bucket kernel, the group verdicts.  Read-only: waits for the device and

@@ -612,6 +612,7 @@ def ed25519_verify_digests_rlc(sigs, pubs, digests, return_stats=False):
 
 
 KEYSET_MAX_KEYS = 1 << 20                      # EDDSA_AMD_KEYSET_MAX_KEYS, include/eddsa_amd.h
+KEYSET_COMB_MAX_KEYS = 1 << 14                 # EDDSA_AMD_KEYSET_COMB_MAX_KEYS: a comb key set holds 88 KiB of HBM per key
 
 
 class Keyset:
@@ -636,6 +637,18 @@ class Keyset:
     def device(self):
         return int(library().eddsa_amd_keyset_device(self._handle()))
 
+    @property
+    def comb(self):
+        """whether the set holds a comb per key (keyset_create(keys, comb=True)): keyed passes over it take the comb route"""
+        return bool(library().eddsa_amd_keyset_is_comb(self._handle()))
+
+    @property
+    def nbytes(self):
+        """the HBM the set holds"""
+        lib = library()
+        lib.eddsa_amd_keyset_bytes.restype = ctypes.c_size_t
+        return int(lib.eddsa_amd_keyset_bytes(self._handle()))
+
     def close(self):
         if self._h is not None:
             library().eddsa_amd_keyset_destroy(self._h)
@@ -649,18 +662,21 @@ class Keyset:
         return False
 
 
-def keyset_create(keys):
+def keyset_create(keys, comb=False):
     """keys: count x 32 bytes, numpy / bytes (host form, on the default device) or a CUDA uint8 tensor (on its device) -> Keyset.
-    Any 32-byte strings may be registered; returns once the tables are built."""
+    Any 32-byte strings may be registered; returns once the tables are built.  comb=True: a comb key set (at most
+    KEYSET_COMB_MAX_KEYS keys, 88 KiB of HBM per key on top) - the same verdicts from 88 additions and 6 doublings per item."""
     lib = library()
     h = _c_ptr()
+    suffix = "_comb" if comb else ""
     if _is_torch(keys):
         keys = _torch_check(keys, 32, "keys")
-        _check(lib.eddsa_amd_keyset_create_dev(ctypes.byref(h), _c_ptr(keys.data_ptr()), _c_size(keys.numel() // 32), _stream()),
-               "eddsa_amd_keyset_create_dev")
+        fn = getattr(lib, "eddsa_amd_keyset_create" + suffix + "_dev")
+        _check(fn(ctypes.byref(h), _c_ptr(keys.data_ptr()), _c_size(keys.numel() // 32), _stream()), "eddsa_amd_keyset_create" + suffix + "_dev")
     else:
         keys = _as_np(keys, 32, "keys")
-        _check(lib.eddsa_amd_keyset_create(ctypes.byref(h), _np_ptr(keys), _c_size(keys.size // 32)), "eddsa_amd_keyset_create")
+        fn = getattr(lib, "eddsa_amd_keyset_create" + suffix)
+        _check(fn(ctypes.byref(h), _np_ptr(keys), _c_size(keys.size // 32)), "eddsa_amd_keyset_create" + suffix)
     return Keyset(h)
 
 

@@ -522,6 +522,7 @@ int verify_on(struct engine *e, uint8_t *ok, const edk_verify_src *all, size_t n
     if ((rc = take_async_error(e))) return rc;   /* an earlier pass's kernels gave up: see engine.h */
     if ((rc = pass_open(&p, e, n, PASS_WS, st))) return rc;
     p.v->ws.exact_offcurve = pass_offcurve_mode();
+    p.v->ws.comb = e->comb;
     p.v->ws.algo = p.v->ws.exact_offcurve ? g_verify_algo : 1;   /* the reject mode has no exact path for the items the pair search gives up on */
     for (size_t done = 0; done < n; done += CHUNK_MAX) {
         const size_t m = n - done < CHUNK_MAX ? n - done : CHUNK_MAX;
@@ -673,6 +674,7 @@ int rlc_on(struct engine *e, uint8_t *ok, uint32_t *stats, const edk_verify_src 
      * like every pass, and verify_route_of takes the full-length route) */
     p.v->ws.exact_offcurve = g_verify_equation ? pass_offcurve_mode() : g_offcurve_mode ? g_offcurve_mode : 1;
     p.v->ws.algo = g_verify_algo;
+    p.v->ws.comb = e->comb;   /* groups sent to the per-item kernels over a comb key set take the comb route */
     for (size_t done = 0; done < n; done += CHUNK_MAX) {
         const size_t m = n - done < CHUNK_MAX ? n - done : CHUNK_MAX;
         const edk_verify_src src = src_at(all, n, done);
@@ -772,22 +774,25 @@ int ed25519_verify_digests_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *
 /* edk_keyset_build is a WEAK reference, like edk_rlc_region below: the host side is also linked without the HIP translation
  * unit (tests/fake_hip) - creating a key set is then hipErrorNotSupported */
 extern __typeof__(edk_keyset_build) edk_keyset_build __attribute__((weak));
+extern __typeof__(edk_keyset_comb_build) edk_keyset_comb_build __attribute__((weak));
 
 static void keyset_free(eddsa_amd_keyset *ks)
 {
     if (ks->keys) HIP_NOTE(hipFree(ks->keys));
     if (ks->flags) HIP_NOTE(hipFree(ks->flags));
     if (ks->table) HIP_NOTE(hipFree(ks->table));
+    if (ks->comb) HIP_NOTE(hipFree(ks->comb));
     free(ks);
 }
 
-/* device < 0: host keys, on the default device; else device keys on `device`.  Returns once the tables are built. */
-static int keyset_create_on(eddsa_amd_keyset **out, const uint8_t *keys, size_t count, int device, hipStream_t st)
+/* device < 0: host keys, on the default device; else device keys on `device`.  comb != 0: a comb key set - everything a plain one
+ * holds, and KEYSET_COMB_WORDS words per key on top.  Returns once the tables are built. */
+static int keyset_create_on(eddsa_amd_keyset **out, const uint8_t *keys, size_t count, int device, hipStream_t st, int comb)
 {
     struct call c;
     int rc;
     eddsa_amd_keyset *ks;
-    if (!edk_keyset_build) return -(int)hipErrorNotSupported;
+    if (!edk_keyset_build || (comb && !edk_keyset_comb_build)) return -(int)hipErrorNotSupported;
     if ((rc = enter(&c, device))) return rc;
     ks = (eddsa_amd_keyset *)calloc(1, sizeof(*ks));
     if (!ks) { rc = -(int)hipErrorOutOfMemory; goto out; }
@@ -797,7 +802,13 @@ static int keyset_create_on(eddsa_amd_keyset **out, const uint8_t *keys, size_t 
     TRY(hipMalloc((void **)&ks->flags, count));
     TRY(hipMalloc((void **)&ks->table, count * VERIFY_ITEM_TABLE_WORDS * sizeof(uint32_t)));
     TRY(hipMemcpyAsync(ks->keys, keys, count * 32, device < 0 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+    ks->bytes = count * (32 + 1 + VERIFY_ITEM_TABLE_WORDS * sizeof(uint32_t));
+    if (comb) {
+        TRY(hipMalloc((void **)&ks->comb, count * KEYSET_COMB_WORDS * sizeof(uint32_t)));
+        ks->bytes += count * KEYSET_COMB_WORDS * sizeof(uint32_t);
+    }
     TRY(edk_keyset_build(ks->table, ks->flags, ks->keys, count, st));
+    if (comb) TRY(edk_keyset_comb_build(ks->comb, ks->keys, count, st));
     TRY(hipStreamSynchronize(st));
     *out = ks;
     ks = NULL;
@@ -811,7 +822,7 @@ int eddsa_amd_keyset_create(eddsa_amd_keyset **out, const uint8_t *keys, size_t 
 {
     if (out) *out = NULL;
     if (!out || !keys || count == 0 || count > EDDSA_AMD_KEYSET_MAX_KEYS) return -(int)hipErrorInvalidValue;
-    return keyset_create_on(out, keys, count, -1, NULL);
+    return keyset_create_on(out, keys, count, -1, NULL, 0);
 }
 
 int eddsa_amd_keyset_create_dev(eddsa_amd_keyset **out, const uint8_t *keys, size_t count, void *stream)
@@ -820,7 +831,24 @@ int eddsa_amd_keyset_create_dev(eddsa_amd_keyset **out, const uint8_t *keys, siz
     if (out) *out = NULL;
     if (!out || !keys || count == 0 || count > EDDSA_AMD_KEYSET_MAX_KEYS) return -(int)hipErrorInvalidValue;
     if ((rc = device_of(keys, &dev))) return rc;
-    return keyset_create_on(out, keys, count, dev, (hipStream_t)stream);
+    return keyset_create_on(out, keys, count, dev, (hipStream_t)stream, 0);
+}
+
+/* comb key sets: the same checks with the comb's limit (88 KiB of HBM per key) */
+int eddsa_amd_keyset_create_comb(eddsa_amd_keyset **out, const uint8_t *keys, size_t count)
+{
+    if (out) *out = NULL;
+    if (!out || !keys || count == 0 || count > EDDSA_AMD_KEYSET_COMB_MAX_KEYS) return -(int)hipErrorInvalidValue;
+    return keyset_create_on(out, keys, count, -1, NULL, 1);
+}
+
+int eddsa_amd_keyset_create_comb_dev(eddsa_amd_keyset **out, const uint8_t *keys, size_t count, void *stream)
+{
+    int dev = -1, rc;
+    if (out) *out = NULL;
+    if (!out || !keys || count == 0 || count > EDDSA_AMD_KEYSET_COMB_MAX_KEYS) return -(int)hipErrorInvalidValue;
+    if ((rc = device_of(keys, &dev))) return rc;
+    return keyset_create_on(out, keys, count, dev, (hipStream_t)stream, 1);
 }
 
 void eddsa_amd_keyset_destroy(eddsa_amd_keyset *ks)
@@ -836,6 +864,8 @@ void eddsa_amd_keyset_destroy(eddsa_amd_keyset *ks)
 
 size_t eddsa_amd_keyset_count(const eddsa_amd_keyset *ks) { return ks ? ks->count : 0; }
 int eddsa_amd_keyset_device(const eddsa_amd_keyset *ks) { return ks ? ks->device : -1; }
+int eddsa_amd_keyset_is_comb(const eddsa_amd_keyset *ks) { return ks && ks->comb ? 1 : 0; }
+size_t eddsa_amd_keyset_bytes(const eddsa_amd_keyset *ks) { return ks ? ks->bytes : 0; }
 
 int ed25519_verify_keyed_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
                              const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
@@ -848,7 +878,7 @@ int ed25519_verify_keyed_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint
     if (dev != ks->device) return -(int)hipErrorInvalidValue;   /* the key set's tables live on its own device */
     if ((rc = enter(&c, dev))) return rc;
     const edk_verify_src src = { sigs, NULL, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL, 0,
-                                 ks->keys, ks->flags, ks->table, ks->count, key_idx };
+                                 ks->keys, ks->flags, ks->table, ks->count, key_idx, ks->comb };
     return leave_with(&c, verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
 }
 
@@ -864,7 +894,7 @@ int ed25519_verify_keyed_rlc_dev(uint8_t *ok, uint32_t *stats, const eddsa_amd_k
     if (dev != ks->device) return -(int)hipErrorInvalidValue;
     if ((rc = enter(&c, dev))) return rc;
     const edk_verify_src src = { sigs, NULL, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL, 0,
-                                 ks->keys, ks->flags, ks->table, ks->count, key_idx };
+                                 ks->keys, ks->flags, ks->table, ks->count, key_idx, ks->comb };
     return leave_with(&c, rlc_on(c.e, ok, stats, &src, n, (hipStream_t)stream));
 }
 
@@ -1182,6 +1212,19 @@ int eddsa_amd_dump_tables(uint32_t *base16_words, uint32_t *comb_words)
     if (rc) return rc;
     TRY(hipMemcpy(base16_words, c.e->base16, (size_t)TABLE_BASE16_ENTRIES * TABLE_ENTRY_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
     TRY(hipMemcpy(comb_words, c.e->comb, TABLE_COMB_ENTRIES * TABLE_ENTRY_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+out:
+    leave(&c);
+    return rc;
+}
+
+/* one key's comb of a comb key set, for the tests that hold it against integers: reads only, on the key set's device */
+int eddsa_amd_debug_keyset_comb_read(const eddsa_amd_keyset *ks, size_t key, uint32_t *words)
+{
+    struct call c;
+    int rc;
+    if (!ks || !ks->comb || !words || key >= ks->count) return -(int)hipErrorInvalidValue;
+    if ((rc = enter(&c, ks->device))) return rc;
+    TRY(hipMemcpy(words, ks->comb + key * KEYSET_COMB_WORDS, KEYSET_COMB_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
 out:
     leave(&c);
     return rc;

@@ -60,6 +60,8 @@ typedef struct edk_verify_ws {
                          k_dom_challenge and read by the digest forms of the prepare kernels (kernels.hip: edk_verify) */
   uint8_t* keybytes;  /* capacity * 32: keyed passes (edk_verify_src.ks_table): the items' key bytes, written by the keyed prepare kernel;
                          the kernels behind it read `pubs` there with stride 32 */
+  const uint32_t* comb; /* the engine's comb of the base point in its global layout (edk_init_tables), not owned: keyed passes over a comb
+                         key set (edk_verify_src.ks_comb) read S*B through it */
 } edk_verify_ws;
 
 /* where the items of a verify pass live: item i has its signature at sigs + i * sig_stride, its key
@@ -93,6 +95,9 @@ typedef struct {
   const uint32_t* ks_table;
   size_t ks_count;
   const uint32_t* key_idx;
+  const uint32_t* ks_comb;   /* != NULL: the key set is a COMB key set (eddsa_amd_keyset_create_comb) - KEYSET_COMB_WORDS words per key,
+                                [key][row][m - 1] = m * 2^(2 COMB_W row) * (-A); the pass takes the comb route (kernels.hip: verify_route_of).
+                                NULL for plain sets; initialisers that stop earlier leave it NULL */
 } edk_verify_src;
 
 /* What the kernels take BY VALUE: the nine fields of edk_verify_src that lanes read, 72 bytes as before the flag existed.  The flag stays

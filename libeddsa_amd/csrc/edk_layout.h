@@ -31,6 +31,9 @@
 #define VERIFY_ITEM_TABLE_WORDS (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS)   /* 1152 contiguous bytes per item */
 #define VERIFY_TABLE_WORDS_PER_TILE (VERIFY_TABLE_ENTRIES * VERIFY_ENTRY_WORDS * 256)
 #define HALF_DIGIT_WORDS 28        /* hdigits [item]: the half-length scalars and their status word (lanes.h: verify_half_scalars_lane) */
+#define KEYSET_COMB_ENTRIES TABLE_COMB_ENTRIES   /* a comb key set (eddsa_amd_keyset_create_comb), comb [key][row][m - 1]: m * 2^(2*COMB_W*row) * (-A_key),
+                                                   row < COMB_ROWS, m = 1..COMB_HALF, each the cached form of a verify table entry */
+#define KEYSET_COMB_WORDS (KEYSET_COMB_ENTRIES * VERIFY_ENTRY_WORDS)          /* 88 KiB per key */
 #define ACC_WORDS 40               /* acc [tile][word][lane VERIFY_TILE], the point workspace: X, Y, Z and one slot (W) for the finish
                                       kernels' prefix products, ten limbs each */
 
@@ -59,6 +62,8 @@
 
 EDK_LAYOUT_ASSERT(EDK_DOM_WORDS * 4 >= EDK_DOM_FIXED_BYTES + EDK_DOM_CONTEXT_MAX, "the longest prefix fits its words");
 EDK_LAYOUT_ASSERT(VERIFY_ITEM_TABLE_WORDS * VERIFY_TILE == VERIFY_TABLE_WORDS_PER_TILE, "a tile of the table is its items' slots");
+EDK_LAYOUT_ASSERT(KEYSET_COMB_WORDS * 4 == 704 * 128 && COMB_ROWS * COMB_HALF == 704, "a key's comb is 704 entries of one 128-byte line");
+EDK_LAYOUT_ASSERT(TABLE_ENTRY_WORDS == VERIFY_ENTRY_WORDS, "an entry of the base point's comb and one of a key's comb are loaded alike");
 EDK_LAYOUT_ASSERT(EDK_BENTRY_WORD + VERIFY_ENTRY_WORDS <= EDK_OFFCOUNT_WORDS, "the base-point entry lies inside offcount");
 EDK_LAYOUT_ASSERT(EDK_OFFLIST_WORD < EDK_PASS_WORDS && EDK_ONLIST_WORD < EDK_PASS_WORDS && EDK_EXACT_UNIT_WORD < EDK_PASS_WORDS &&
                   EDK_STALL_WORD < EDK_PASS_WORDS && EDK_PASS_WORDS == 4, "every pass zeroes its four words");

@@ -160,6 +160,8 @@ struct eddsa_amd_keyset {
     uint8_t *keys;                    /* HBM: count * 32 bytes */
     uint8_t *flags;                   /* HBM: count bytes, 1 = the key decodes to a curve point */
     uint32_t *table;                  /* HBM: count * VERIFY_ITEM_TABLE_WORDS words, 0..8 times -A per key */
+    uint32_t *comb;                   /* comb key sets (eddsa_amd_keyset_create_comb), else NULL.  HBM: count * KEYSET_COMB_WORDS words */
+    size_t bytes;                     /* HBM the set holds: what eddsa_amd_keyset_bytes reports */
 };
 
 extern pthread_rwlock_t g_table;

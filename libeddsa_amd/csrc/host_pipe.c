@@ -961,14 +961,14 @@ static int run_verify_dom(struct engine *e, const struct hjob *j, const struct c
 static int run_verify_keyed(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     const edk_verify_src src = { c->d_in[0], NULL, c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, NULL, 0,
-                                 j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1] };
+                                 j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1], j->ks->comb };
     return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
 }
 /* the batch verification over a key set: the inputs of run_verify_keyed, the pass and the statistics of run_verify_rlc */
 static int run_verify_keyed_rlc(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     const edk_verify_src src = { c->d_in[0], NULL, c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, NULL, 0,
-                                 j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1] };
+                                 j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1], j->ks->comb };
     return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
 }
 static int run_sign_dom(struct engine *e, const struct hjob *j, const struct chunk *c)

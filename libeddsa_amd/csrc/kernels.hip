@@ -18,6 +18,7 @@
 //   k_sk_to_x        ed25519-sha512.c:239-256 sk_ed25519_to_x25519
 //   k_init_tables    generates what the reference ships as lib/ed_lookup64.h
 //   k_keyset_build, k_verify_*_keyed          key-set verification (keyed_kernels.h): the key's table by index
+//   k_keyset_comb_build, k_verify_main_comb_keyed   comb key sets (keyed_kernels.h): a comb per key, both scalars fixed-base
 #include "eddsa_kernels.h"
 #include "edk_keyed.h"
 #include "edk_checked.h"
@@ -1280,7 +1281,8 @@ static_assert(EXACT_LANE_MIN_LISTED <= (size_t)EDK_EXACT_SLOTS && EXACT_LANE_MIN
 enum verify_prepare { PREPARE_ONE, PREPARE_PAIR };     // k_verify_prepare | k_verify_prepare_pair (three lanes per item)
 enum verify_eval { EVAL_FULL_ONE, EVAL_FULL_QUAD,      // k_verify_main | k_verify_main_quad, then k_verify_finish
                    EVAL_HALF_ONE, EVAL_HALF_ONE_LONG,  // k_verify_main_half | the same with the long loop in place (WITH_LONG)
-                   EVAL_HALF_QUAD, EVAL_SUMS_QUAD };   // k_verify_main_half_quad | k_verify_window_sums + k_verify_main_sums_quad
+                   EVAL_HALF_QUAD, EVAL_SUMS_QUAD,     // k_verify_main_half_quad | k_verify_window_sums + k_verify_main_sums_quad
+                   EVAL_COMB_ONE };                    // k_verify_main_comb_keyed (a comb key set), then k_verify_finish
 struct verify_route {
   verify_prepare prepare;
   bool halve;           // k_verify_halve runs
@@ -1310,7 +1312,17 @@ static_assert(HALF_WINDOWS_SMALL == HALF_BITS_SMALL / 4 + 1 && HALF_WINDOWS == H
 //   keyed, modes 1 and 2      < 2^19              one lane  yes    2^138 / 35       half-length, one lane
 //                             >= 2^19             one lane  yes    2^134 / 34       half-length, one lane
 //   keyed, reject mode        any                 one lane  -      -                full-length, one lane
-constexpr verify_route verify_route_of(size_t n, int algo, int exact_offcurve, bool keyed = false) {
+// A keyed pass over a COMB key set (eddsa_amd_keyset_create_comb) is the full-length route with another main kernel, in every
+// off-curve mode and at every size; in modes 1 and 2 the off-list and the exact path work as on the full-length route:
+//   keyed, comb key set       any                 one lane  -      -                both combs, one lane (keyed_lanes.h: verify_comb_lane)
+constexpr uint32_t COMB_MAIN_COST = 127;   // k_verify_main_comb_keyed, executed instructions per item, thousands: the static count of its blocks times their trip counts (profiles/verify_keyed_comb.txt, section 1)
+constexpr verify_route verify_route_of(size_t n, int algo, int exact_offcurve, bool keyed = false, bool comb = false) {
+  if (keyed && comb) {
+    verify_route c = {PREPARE_ONE, false, false, EVAL_COMB_ONE, 0, 0, COMB_MAIN_COST, 1, true};
+    c.lane_min = n >= EXACT_LANE_MIN_N ? (uint32_t)EXACT_LANE_MIN_LISTED : 0u;
+    c.dense = n >= EXACT_DENSE_MIN_N;
+    return c;
+  }
   if (!exact_offcurve) algo = 1;
   if (keyed) algo = exact_offcurve ? 2 : 1;   // (algo 2: the half-length route from one item on)
   verify_route r = {PREPARE_ONE, false, false, n <= QUAD_MAIN_MAX_N && !keyed ? EVAL_FULL_QUAD : EVAL_FULL_ONE, 0, 0, 0, 0};
@@ -1357,6 +1369,12 @@ static_assert(route_is(verify_route_of(1, 0, 0, true), PREPARE_ONE, false, false
               route_is(verify_route_of(1 << 20, 0, 0, true), PREPARE_ONE, false, false, EVAL_FULL_ONE), "a keyed pass in reject mode: the one-lane full-length route, also below 2^14 items");
 static_assert(verify_route_of(1 << 20, 0, 1, true).keyed && !verify_route_of(1 << 20, 0, 1).keyed && route_is(verify_route_of(1 << 20, 0, 1, true), PREPARE_ONE, true, false, EVAL_HALF_ONE) &&
               verify_route_of(1 << 16, 0, 1, true).lane_min == 8192 && verify_route_of(1 << 16, 0, 1, true).main_cost == 226, "keyed: the exact path's hints as for the unkeyed route");
+static_assert(route_is(verify_route_of(1, 0, 0, true, true), PREPARE_ONE, false, false, EVAL_COMB_ONE) && route_is(verify_route_of(1 << 14, 3, 1, true, true), PREPARE_ONE, false, false, EVAL_COMB_ONE) &&
+              route_is(verify_route_of(1 << 20, 0, 2, true, true), PREPARE_ONE, false, false, EVAL_COMB_ONE) && verify_route_of(1 << 20, 0, 1, true, true).keyed,
+              "a keyed pass over a comb key set: one route in every off-curve mode, at every size, whatever the algo");
+static_assert(route_is(verify_route_of(1 << 20, 0, 1, false, true), PREPARE_ONE, true, false, EVAL_HALF_ONE) && !verify_route_of(1 << 20, 0, 1, false, true).keyed, "no comb route without a key set");
+static_assert(verify_route_of((1 << 16) - 1, 0, 1, true, true).lane_min == 0 && verify_route_of(1 << 16, 0, 1, true, true).lane_min == 8192 && verify_route_of(1 << 16, 0, 1, true, true).dense &&
+              verify_route_of(1 << 16, 0, 1, true, true).main_cost == COMB_MAIN_COST && verify_route_of(1 << 16, 0, 1, true, true).main_all == 1, "comb: the exact path's hints, the main kernel runs over the whole pass");
 static_assert(verify_route_of(1 << 16, 0, 1).main_cost == 226 && verify_route_of(1 << 16, 0, 1).main_all == 0 && verify_route_of(1 << 16, 1, 1).main_cost == 323 && verify_route_of(1 << 16, 1, 1).main_all == 1, "the chain's hint follows the evaluation");
 
 // the first kernel of a verify pass: the three-lane preparation or the one-lane one.
@@ -1510,7 +1528,9 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
   if (n == 0) return hipSuccess;
   const bool keyed = src.ks_table != nullptr;     // ed25519_verify_keyed*: the keys come from a key set, by src.key_idx
   if (keyed && (src.digest || src.dom || !src.key_idx || !src.ks_keys || !src.ks_flags || src.ks_count == 0 || src.ks_count > (size_t)UINT32_MAX)) return hipErrorInvalidValue;
-  const verify_route r = verify_route_of(n, ws->algo, ws->exact_offcurve, keyed);
+  const bool comb = keyed && src.ks_comb != nullptr;   // ... and the set holds a comb per key: both scalars by fixed-base arithmetic
+  if (comb && !ws->comb) return hipErrorInvalidValue;
+  const verify_route r = verify_route_of(n, ws->algo, ws->exact_offcurve, keyed, comb);
   const unsigned blocks = blocks_of(n), quad_blocks = blocks_of(4 * n, QUAD_BLOCK);
   // 1. reset: both work lists' lengths, the one-lane exact path's unit counter and its stall flag
   EDK_DO(hipMemsetAsync(ws->offcount, 0, EDK_PASS_WORDS * sizeof(uint32_t), stream));
@@ -1608,9 +1628,12 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
       if (r.keyed) EDK_LAUNCH(k_verify_main_keyed, dim3(blocks), dim3(BLOCK), MAIN_LDS_RESERVE, stream, ws->digits, src.ks_table, src.key_idx, (uint32_t)src.ks_count, n, base16, ws->acc);
       else EDK_LAUNCH(k_verify_main, dim3(blocks), dim3(BLOCK), MAIN_LDS_RESERVE, stream, ws->digits, ws->table, base16, ws->acc);
       break;
+    case EVAL_COMB_ONE:
+      EDK_LAUNCH(k_verify_main_comb_keyed, dim3(blocks), dim3(BLOCK), 0, stream, ws->digits, src.ks_comb, src.ks_table, src.key_idx, (uint32_t)src.ks_count, n, ws->comb, ws->acc);
+      break;
   }
   if (marks) EDK_DO(hipEventRecord(marks[2], stream));
-  if (r.eval == EVAL_FULL_ONE || r.eval == EVAL_FULL_QUAD) {
+  if (r.eval == EVAL_FULL_ONE || r.eval == EVAL_FULL_QUAD || r.eval == EVAL_COMB_ONE) {
     const finish_shape f = finish_shape_of(n);
     EDK_LAUNCH(k_verify_finish, dim3(f.grid), dim3(BLOCK), 0, stream, ok, src.sigs, src.sig_stride, ws->acc, ws->flags, n, ws->exact_offcurve, f.k);
   }
@@ -1640,6 +1663,13 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
 hipError_t edk_keyset_build(uint32_t* table, uint8_t* flags, const uint8_t* keys, size_t count, hipStream_t stream) {
   if (count == 0) return hipSuccess;
   hipLaunchKernelGGL(k_keyset_build, dim3(blocks_of(count)), dim3(BLOCK), 0, stream, table, flags, keys, count);
+  return hipGetLastError();
+}
+
+// the combs of a comb key set (edk_keyed.h): KEYSET_COMB_WORDS words per key.  Asynchronous on `stream`
+hipError_t edk_keyset_comb_build(uint32_t* comb, const uint8_t* keys, size_t count, hipStream_t stream) {
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_keyset_comb_build, dim3(blocks_of(count * COMB_ROWS)), dim3(BLOCK), 0, stream, comb, keys, count);
   return hipGetLastError();
 }
 

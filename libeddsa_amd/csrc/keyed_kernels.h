@@ -6,6 +6,8 @@
 //   k_keyed_exact_tables     the items that kernel listed for the exact path get a table of their own, as in an unkeyed pass
 //   k_verify_halve_keyed     k_verify_halve; an item it hands to the exact path gets a copy of its key's table in its own slot
 //   k_verify_main_half_keyed, k_verify_main_keyed   the one-lane evaluations with tab_a = the key's table in the key set
+//   k_keyset_comb_build      once per COMB key set, one lane per (key, row): the key's comb, 704 entries m * 4096^row * (-A)
+//   k_verify_main_comb_keyed the evaluation of a pass over a comb key set: both scalars through combs, 88 additions and 6 doublings
 // Kernels of their own rather than one more template argument of the unkeyed ones: their argument lists differ, and the unkeyed
 // instantiations keep the code objects they had (profiles/verify_keyed.txt, section 1).  What a lane computes is lanes.h's,
 // unchanged: verify_half_main_lane and verify_main_lane take tab_a as a pointer of its own.
@@ -151,6 +153,40 @@ k_verify_main_keyed(const uint32_t* digits, const uint32_t* keytab, const uint32
   k = k < count ? k : 0u;
   ge acc;
   verify_main_lane(acc, digits + digit_slot(i), keytab + table_slot(k), base16);
+  acc_put_xyz(acc_column(accout, tile, threadIdx.x), acc);
+}
+
+// ---- comb key sets (eddsa_amd_keyset_create_comb; keyed_lanes.h) ----
+
+// Once per comb key set, one lane per (key, row): the row's COMB_HALF entries of the key's comb.
+__global__ void __launch_bounds__(BLOCK, 2)
+k_keyset_comb_build(uint32_t* comb, const uint8_t* keys, size_t count) {
+  const size_t id = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  const size_t k = id / COMB_ROWS;
+  const int row = (int)(id % COMB_ROWS);
+  if (k >= count) return;
+  uint32_t aw[8];
+  load32(aw, keys, k, 32);
+  keyset_comb_row_lane(comb + comb_slot(k) + (size_t)row * COMB_HALF * VERIFY_ENTRY_WORDS, aw, row);
+}
+
+// k_verify_main_keyed for a comb key set: the same tile of BLOCK lanes per block and the same result in accout for
+// k_verify_finish, from 88 additions and 6 doublings (verify_comb_lane).  bcomb: the engine's comb of the base point in its
+// global layout (88 KiB, shared by every lane).  Slots past the pass and items whose index names no key walk key 0's comb.
+// Two accumulators and two entries in flight: two blocks per CU; the scalars wait in LDS (18 KiB per block), not in registers.
+__global__ void __launch_bounds__(BLOCK, 2)
+k_verify_main_comb_keyed(const uint32_t* digits, const uint32_t* keycomb, const uint32_t* keytab, const uint32_t* key_idx, uint32_t count,
+                         size_t n, const uint32_t* bcomb, uint32_t* accout) {
+  const size_t tile = blockIdx.x;
+  const size_t i = tile * BLOCK + threadIdx.x;   // < workspace capacity
+  uint32_t k = i < n ? key_idx[i] : 0u;
+  k = k < count ? k : 0u;
+  __shared__ uint32_t comb_words[2 * 9 * BLOCK];   // [t | S][word][lane]: the lane's two scalars plus the comb's offset
+  uint32_t* yt = comb_words + threadIdx.x;
+  uint32_t* ys = yt + 9 * BLOCK;
+  verify_comb_words_lane(yt, ys, BLOCK, digits + digit_slot(i));
+  ge acc;
+  verify_comb_lane(acc, yt, ys, BLOCK, keycomb + comb_slot(k), keytab + table_slot(k), bcomb);
   acc_put_xyz(acc_column(accout, tile, threadIdx.x), acc);
 }
 
