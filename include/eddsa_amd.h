@@ -404,7 +404,8 @@ RFC8032_EDDSA_DECL int eddsa_amd_set_verify_equation(int equation);
  *   An item that needs the reference-order chain (a key off the curve in mode 1, every item in mode 2, an item without a short
  *   scalar pair) gets a table of its own in the workspace, as in an unkeyed pass.
  * Out of scope: _rlc, _multi, records, digest, Ed25519ctx / Ed25519ph and single-item forms; tables wider than nine entries.
- *   (Of these, _rlc has since been added for the message form: ed25519_verify_keyed_rlc, further down.)
+ *   (Of these, _rlc has since been added for the message form: ed25519_verify_keyed_rlc, further down; the digest forms with
+ *   their _rlc, Ed25519ctx and Ed25519ph at the end of this header: ed25519_verify_keyed_digests and its neighbours.)
  * Measured (profiles/verify_keyed.txt, tools/keyed_rate.py: device-pointer forms, 2^20 valid items in HBM, 32-byte messages, one
  * MI355X, the two passes alternating, repeat spread 0.03-0.04 ms): items under 1024 distinct keys 9.44 ms per pass through
  * ed25519_verify_batch_dev, 8.31 ms through ed25519_verify_keyed_dev (-12.0 %: 126 M instead of 111 M verifies/s); under ONE key
@@ -456,6 +457,8 @@ RFC8032_EDDSA_DECL int ed25519_verify_keyed_dev(uint8_t *ok, const eddsa_amd_key
  *   rules and clamping, EDDSA_AMD_STALLED and return values; a key set or `ok` on the wrong device, NULL arguments, ownership
  *   and threading; never merged by the small-call combiner; the device form synchronises `stream` once per pass.
  * Still out of scope: the digest, records, _multi, Ed25519ctx / Ed25519ph and single-item forms of keyed verification.
+ *   (Of these, the digest forms - with their own _rlc - and Ed25519ctx / Ed25519ph have since been added: ed25519_verify_keyed_digests
+ *   and its neighbours, at the end of this header.)
  * Measured (profiles/verify_keyed_rlc.txt, tools/keyed_rlc_rate.py: the three device-pointer forms alternating over the same 2^20
  * valid items in HBM, 32-byte messages, one MI355X, repeat spread 0.01-0.04 ms for the two combinations): under 1024 keys 3.11 ms
  * per pass against 4.47 ms through ed25519_verify_batch_rlc_dev (-30 %: 337 M instead of 235 M verifies/s) and 8.71 ms through
@@ -495,6 +498,7 @@ RFC8032_EDDSA_DECL int ed25519_verify_keyed_rlc_dev(uint8_t *ok, uint32_t *stats
  *   device is touched; a failed allocation returns its HIP error with *out NULL.  Lifetime, devices, eddsa_amd_keyset_destroy and
  *   "survives eddsa_amd_shutdown" are those of a plain key set; the four functions above and plain key sets behave as before.
  * Out of scope: four-lane forms of the comb route, combs wider than 6 bits, the digest, records, _multi and ctx / ph keyed forms.
+ *   (The digest and ctx / ph keyed forms have since been added and take the comb route over a comb set: the end of this header.)
  * Measured (profiles/verify_keyed_comb.txt, tools/keyed_comb_rate.py: device-pointer forms over the same 2^20 valid items in HBM,
  * 32-byte messages, one MI355X, ed25519_verify_batch_dev / ed25519_verify_keyed_dev over a plain set / the same call over a comb
  * set alternating, repeat spread 0.01-0.14 ms): under 1024 keys 9.95 / 8.78 / 3.84 ms per pass in mode 1 (-56 % against the plain
@@ -514,6 +518,69 @@ RFC8032_EDDSA_DECL int eddsa_amd_keyset_create_comb(eddsa_amd_keyset **out, cons
 RFC8032_EDDSA_DECL int eddsa_amd_keyset_create_comb_dev(eddsa_amd_keyset **out, const uint8_t *keys /* device */, size_t count, void *stream);
 RFC8032_EDDSA_DECL int eddsa_amd_keyset_is_comb(const eddsa_amd_keyset *ks);   /* 1 / 0; NULL: 0 */
 RFC8032_EDDSA_DECL size_t eddsa_amd_keyset_bytes(const eddsa_amd_keyset *ks);  /* HBM the set holds; NULL: 0 */
+
+/* ---- KEY SETS: the digest, Ed25519ctx and Ed25519ph forms ----
+ * The forms of verification that take something other than plain Ed25519 over message bytes, over a key set: caller-supplied
+ * digests (ed25519_verify_digests, ed25519_verify_digests_rlc) and the two context variants of RFC 8032 5.1
+ * (ed25519ctx_verify_batch, ed25519ph_verify_batch), with `pubs` replaced by a key set and one uint32 index per item.  A caller
+ * that hashes its messages while they stream in, or signs under a domain-separating context, keeps what the key set buys: no
+ * per-item square root and table, the comb route over a comb set, one scalar per key in the combination.
+ * Verdicts: ok[i] is byte for byte what the unkeyed form of the same name returns for (sigs[i], keys[key_idx[i]], digest /
+ *   message / prehash i) - ed25519_verify_digests, ed25519_verify_digests_rlc, ed25519ctx_verify_batch, ed25519ph_verify_batch -
+ *   under the off-curve mode (0, 1, 2), the strict rules and the equation in force when each pass is enqueued, over plain key sets
+ *   and over comb key sets.  A comb set takes the comb route in the per-item forms; the combination does not use the comb, and
+ *   the groups it sends to the per-item kernels take the comb route, as in ed25519_verify_keyed_rlc.
+ * The digest forms: the caller vouches that digests[i] = SHA-512(R_i || keys[key_idx[i]] || M_i) - the statement of
+ *   ed25519_verify_digests with the key set's bytes in the place of pubs[i]; any 64 bytes are legal input, and a digest over other
+ *   bytes (another key's, say) is simply verified as the challenge it is: the item is rejected, its neighbours are not affected.
+ * Out-of-range indices: key_idx[i] >= count gives ok[i] = 0 under every setting, and nothing outside the key set is read for
+ *   that item.  In the _rlc form it contributes to no sum and does not send its group to the per-item kernels.  In the ctx / ph
+ *   forms its challenge hash runs over the bytes that stand for "no key" in every keyed pass (02 00 .. 00, a string that is no
+ *   curve point), so the cofactored re-evaluation rejects it too.
+ * Everything else follows the existing key-set forms: a key set or `ok` on the wrong device returns -hipErrorInvalidValue; NULL
+ *   arguments (ks, ok, key_idx, sigs, digests / prehashes, fixed-length messages) are checked before any device is touched;
+ *   host-pointer calls run on the key set's device and are never merged by the small-call combiner; a key set of more than 8192
+ *   keys makes the _rlc form run as the per-item form, with every item counted as decided per item; eddsa_amd_set_rlc_min_items
+ *   governs the _rlc form as it does the other two; the _rlc device form synchronises `stream` once per pass; `context` is a host
+ *   pointer in every form, and context_len > 255 (or a NULL context with a length) returns -hipErrorInvalidValue before anything
+ *   is touched.  The host-pointer forms upload 64 bytes of signature, 4 of index and 64 of digest or prehash per item.
+ * Kernels: the keyed prepare kernel and the keyed hash kernel of the combination in digest forms that take t from the 64 bytes
+ *   unhashed, and one kernel in front of the ctx / ph pass that hashes dom2 || R || keys[key_idx] || M' per item; everything
+ *   behind them is the keyed pass as it was.  The seed and the coefficients of a keyed digest combination equal those of
+ *   ed25519_verify_digests_rlc over the expanded keys (the leaf is SHA-512(digest || S) in both).
+ * Out of scope: _rlc forms of ctx / ph (the unkeyed forms have none either); _multi, records and single-item keyed forms.
+ * Measured (profiles/verify_keyed_forms.txt, tools/keyed_forms_rate.py: device-pointer forms alternating over the same 2^20 valid
+ * items in HBM under 1024 keys, one MI355X, repeat spread 0.01-0.07 ms): digests against 32-byte messages 8.47 against 8.49 ms over
+ * a plain set, 3.73 against 3.73 ms over a comb set (281 M verifies/s), 2.98 against 3.09 ms in the combination (352 M verifies/s) -
+ * no digest form is slower than its message form.  Ed25519ctx / Ed25519ph over a plain set 8.77 / 8.79 ms (+3.6 / +3.9 % on the
+ * keyed message form, -10.5 % on the unkeyed ctx / ph forms), over a comb set 4.02 / 4.00 ms (+7.3 / +6.6 %, -59 %): the hashing
+ * kernel in front costs 0.25-0.3 ms, against 0.2 ms in the unkeyed forms.  What the forms are for - 2^16 items of which one in
+ * 1024 is 1 MiB long, over a comb set: 62.0 ms through ed25519_verify_keyed_dev, 0.37 ms from the caller's digests and 0.38 ms from
+ * its prehashes (the caller's own hashing, done while the messages stream in, is in neither figure).  The unchanged calls against
+ * the commit before this one, alternating in fresh processes on that box: 9.639 against 9.652 ms (ed25519_verify_batch_dev), 8.485
+ * against 8.481 and 3.753 against 3.750 ms (ed25519_verify_keyed_dev, plain and comb), 3.088 against 3.091 ms
+ * (ed25519_verify_keyed_rlc_dev), each inside the older build's own repeats. */
+RFC8032_EDDSA_DECL int ed25519_verify_keyed_digests(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                                                    const uint8_t *digests /* 64 bytes per item */, size_t n);
+RFC8032_EDDSA_DECL int ed25519_verify_keyed_digests_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                                                        const uint8_t *digests, size_t n, void *stream);
+RFC8032_EDDSA_DECL int ed25519_verify_keyed_digests_rlc(uint8_t *ok, uint32_t stats[4], const eddsa_amd_keyset *ks, const uint32_t *key_idx,
+                                                        const uint8_t *sigs, const uint8_t *digests, size_t n);
+RFC8032_EDDSA_DECL int ed25519_verify_keyed_digests_rlc_dev(uint8_t *ok, uint32_t *stats /* device or NULL */, const eddsa_amd_keyset *ks,
+                                                            const uint32_t *key_idx, const uint8_t *sigs, const uint8_t *digests, size_t n,
+                                                            void *stream);
+RFC8032_EDDSA_DECL int ed25519ctx_verify_keyed(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                                               const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n,
+                                               const uint8_t *context /* host */, size_t context_len);
+RFC8032_EDDSA_DECL int ed25519ctx_verify_keyed_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                                                   const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n,
+                                                   const uint8_t *context /* host */, size_t context_len, void *stream);
+RFC8032_EDDSA_DECL int ed25519ph_verify_keyed(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                                              const uint8_t *prehashes /* 64 bytes per item */, size_t n,
+                                              const uint8_t *context /* host */, size_t context_len);
+RFC8032_EDDSA_DECL int ed25519ph_verify_keyed_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                                                  const uint8_t *prehashes, size_t n, const uint8_t *context /* host */, size_t context_len,
+                                                  void *stream);
 
 #ifdef __cplusplus
 }

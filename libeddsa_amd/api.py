@@ -861,6 +861,87 @@ def ed25519ph_verify_batch(sigs, pubs, prehashes, context=b""):
 
 
 # ---------------------------------------------------------------------------------------------
+# key sets: the digest, Ed25519ctx and Ed25519ph forms (include/eddsa_amd.h)
+# ---------------------------------------------------------------------------------------------
+
+def _run_keyed_forms(name, sigs, keyset, key_idx, data, fixed=None, data_name="msgs", msg_off=None, msg_len=None, context=None,
+                     stats=None):
+    """common driver of the keyed forms that are not plain Ed25519 over messages: sigs, key indices and `data` - digests or
+    prehashes (`fixed` = 64 bytes per item, no offsets) or messages (fixed None) - under `context` (None: the C function takes
+    none) -> (n,) uint8.  numpy / bytes: the host form `name`; CUDA tensors: `name`_dev on torch's stream.  stats: as in
+    _run_msgs.  The checks are those of ed25519_verify_keyed and of _run_digests / _run_dom."""
+    ctx_args = []
+    if context is not None:
+        context = _context(context)
+        ctx_args = [ctypes.c_char_p(context), _c_size(len(context))]
+    handle = keyset._handle()
+    on_device = _is_torch(sigs)
+    if on_device:
+        import torch
+        sigs = _torch_check(sigs, 64, "sigs"); data = _torch_check(data, fixed or 0, data_name)
+        n, total = sigs.numel() // 64, data.numel()
+        if not _is_torch(key_idx) or key_idx.dtype != torch.int32 or not key_idx.is_cuda or not key_idx.is_contiguous() or key_idx.numel() != n:
+            raise ValueError(f"{name}: key_idx: expected n contiguous int32 indices on the device")
+    else:
+        sigs = _as_np(sigs, 64, "sigs"); data = _as_np(data, fixed or 0, data_name)
+        n, total = sigs.size // 64, data.size
+        key_idx = np.ascontiguousarray(np.asarray(key_idx))
+        if key_idx.dtype != np.uint32 or key_idx.size != n:
+            raise ValueError(f"{name}: key_idx: expected n uint32 indices")
+    if fixed and total != fixed * n:
+        raise ValueError(f"{name}: sigs and {data_name} disagree on the batch size ({n}, {total // fixed} items)")
+    lib = library()
+    msg_args = []
+    if on_device:
+        if not fixed:
+            _, off, mlen = _msg_args(data, msg_off, msg_len, n, True)
+            _torch_off_check(off, n)
+            msg_args = [_c_ptr(off.data_ptr()) if off is not None else None, _c_size(mlen)]
+        out = torch.empty((n,), dtype=torch.uint8, device=sigs.device)
+        counts = torch.zeros((4,), dtype=torch.int32, device=sigs.device) if stats else None
+        head = [_c_ptr(out.data_ptr())] + ([_c_ptr(counts.data_ptr()) if stats else None] if stats is not None else [])
+        _check(getattr(lib, name + "_dev")(*head, handle, _c_ptr(key_idx.data_ptr()), _c_ptr(sigs.data_ptr()), _c_ptr(data.data_ptr()),
+                                           *msg_args, _c_size(n), *ctx_args, _stream()), name + "_dev")
+        return (out, tuple(int(x) for x in counts.cpu())) if stats else out
+    if not fixed:
+        data, off, mlen = _host_msgs(data, msg_off, msg_len, n)
+        msg_args = [_np_ptr(off) if off is not None else None, _c_size(mlen)]
+    out = np.zeros((n,), dtype=np.uint8)
+    counts = (ctypes.c_uint32 * 4)()
+    head = [_np_ptr(out)] + ([counts] if stats is not None else [])
+    _check(getattr(lib, name)(*head, handle, _np_ptr(key_idx), _np_ptr(sigs), _np_ptr(data), *msg_args, _c_size(n), *ctx_args), name)
+    return (out, tuple(int(x) for x in counts)) if stats else out
+
+
+def ed25519_verify_keyed_digests(sigs, keyset, key_idx, digests):
+    """ed25519_verify_digests with item i's key taken from a key set: the caller vouches that digests[i] =
+    SHA-512(R_i || keys[key_idx[i]] || M_i) (64 bytes per item) -> (n,) uint8, 1 = accept; an index outside the key set rejects
+    its item.  A comb key set takes the comb route.  Inputs as ed25519_verify_keyed (numpy: host form, CUDA tensors: device form)."""
+    return _run_keyed_forms("ed25519_verify_keyed_digests", sigs, keyset, key_idx, digests, fixed=64, data_name="digests")
+
+
+def ed25519_verify_keyed_digests_rlc(sigs, keyset, key_idx, digests, return_stats=False):
+    """ed25519_verify_keyed_rlc from caller-supplied digests (see ed25519_verify_keyed_digests): the verdicts and statistics of
+    ed25519_verify_digests_rlc over keys[key_idx]; key sets of more than 8192 keys run as ed25519_verify_keyed_digests."""
+    return _run_keyed_forms("ed25519_verify_keyed_digests_rlc", sigs, keyset, key_idx, digests, fixed=64, data_name="digests",
+                            stats=bool(return_stats))
+
+
+def ed25519ctx_verify_keyed(sigs, keyset, key_idx, msgs, context, msg_off=None, msg_len=None):
+    """ed25519ctx_verify_batch with item i's key taken from a key set -> (n,) uint8, 1 = accept; `context`: host bytes, 0..255;
+    messages as in ed25519_verify_keyed"""
+    return _run_keyed_forms("ed25519ctx_verify_keyed", sigs, keyset, key_idx, msgs, msg_off=msg_off, msg_len=msg_len,
+                            context=context if context is not None else b"")
+
+
+def ed25519ph_verify_keyed(sigs, keyset, key_idx, prehashes, context=b""):
+    """ed25519ph_verify_batch with item i's key taken from a key set: prehashes[i] = SHA-512(M_i), 64 bytes per item
+    -> (n,) uint8, 1 = accept"""
+    return _run_keyed_forms("ed25519ph_verify_keyed", sigs, keyset, key_idx, prehashes, fixed=PREHASH_BYTES, data_name="prehashes",
+                            context=context if context is not None else b"")
+
+
+# ---------------------------------------------------------------------------------------------
 # several devices in one process (include/eddsa_amd.h: *_multi), after init_devices()
 # ---------------------------------------------------------------------------------------------
 

@@ -898,6 +898,55 @@ int ed25519_verify_keyed_rlc_dev(uint8_t *ok, uint32_t *stats, const eddsa_amd_k
     return leave_with(&c, rlc_on(c.e, ok, stats, &src, n, (hipStream_t)stream));
 }
 
+/* The digest, Ed25519ctx and Ed25519ph forms over a key set (include/eddsa_amd.h): one body - the checks of
+ * ed25519_verify_keyed_dev in its order with the NULL arguments refused before any device is asked, then the edk_verify_src of the
+ * unkeyed form of the same name (digests: msg_len 64, no offset table, digest = 1; ctx / ph: the call's dom2 prefix) with the
+ * ks_* fields set.  rlc != 0: the combination (the digest form only). */
+static int keyed_forms_dev(uint8_t *ok, uint32_t *stats, int rlc, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                           const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, int digest, const edk_dom *dom, void *stream)
+{
+    struct call c;
+    int rc = 0, dev = -1;
+    if (!ks) return -(int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if (!ok || !key_idx || !sigs || (!msgs && msg_len && !msg_off)) return -(int)hipErrorInvalidValue;   /* (fixed-length items need their buffer) */
+    if ((rc = device_of(ok, &dev))) return rc;
+    if (dev != ks->device) return -(int)hipErrorInvalidValue;   /* the key set's tables live on its own device */
+    if ((rc = enter(&c, dev))) return rc;
+    const edk_verify_src src = { sigs, NULL, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, digest, 0, dom, 0,
+                                 ks->keys, ks->flags, ks->table, ks->count, key_idx, ks->comb };
+    return leave_with(&c, rlc ? rlc_on(c.e, ok, stats, &src, n, (hipStream_t)stream) : verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
+}
+
+int ed25519_verify_keyed_digests_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                                     const uint8_t *digests, size_t n, void *stream)
+{
+    return keyed_forms_dev(ok, NULL, 0, ks, key_idx, sigs, digests, NULL, 64, n, 1, NULL, stream);
+}
+
+int ed25519_verify_keyed_digests_rlc_dev(uint8_t *ok, uint32_t *stats, const eddsa_amd_keyset *ks, const uint32_t *key_idx,
+                                         const uint8_t *sigs, const uint8_t *digests, size_t n, void *stream)
+{
+    return keyed_forms_dev(ok, stats, 1, ks, key_idx, sigs, digests, NULL, 64, n, 1, NULL, stream);
+}
+
+/* (the prefix is built first: a context of more than 255 bytes ends the call before anything else is looked at) */
+int ed25519ctx_verify_keyed_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs, const uint8_t *msgs,
+                                const uint64_t *msg_off, size_t msg_len, size_t n, const uint8_t *context, size_t context_len, void *stream)
+{
+    edk_dom dom;
+    const int rc = dom2_fill(&dom, 0, context, context_len);
+    return rc ? rc : keyed_forms_dev(ok, NULL, 0, ks, key_idx, sigs, msgs, msg_off, msg_len, n, 0, &dom, stream);
+}
+
+int ed25519ph_verify_keyed_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                               const uint8_t *prehashes, size_t n, const uint8_t *context, size_t context_len, void *stream)
+{
+    edk_dom dom;
+    const int rc = dom2_fill(&dom, 1, context, context_len);
+    return rc ? rc : keyed_forms_dev(ok, NULL, 0, ks, key_idx, sigs, prehashes, NULL, EDDSA_PREHASH_BYTES, n, 0, &dom, stream);
+}
+
 int ed25519_sign_batch_dev(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
                            const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {

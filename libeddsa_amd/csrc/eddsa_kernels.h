@@ -57,7 +57,7 @@ typedef struct edk_verify_ws {
                          3: the mid-size arrangement below 2^18 items, full-length from there on.  The table: kernels.hip, verify_route_of */
   int exact_offcurve; /* 1: replay the reference's chain for off-curve keys (default); 0: reject them; 2: replay for every item */
   uint8_t* domdig;    /* capacity * EDK_DOM_DIGEST_BYTES: Ed25519ctx / Ed25519ph passes: the items' SHA-512(dom2 | R | A | M'), written by
-                         k_dom_challenge and read by the digest forms of the prepare kernels (kernels.hip: edk_verify) */
+                         k_dom_challenge[_keyed] and read by the digest forms of the prepare kernels (kernels.hip: edk_verify) */
   uint8_t* keybytes;  /* capacity * 32: keyed passes (edk_verify_src.ks_table): the items' key bytes, written by the keyed prepare kernel;
                          the kernels behind it read `pubs` there with stride 32 */
   const uint32_t* comb; /* the engine's comb of the base point in its global layout (edk_init_tables), not owned: keyed passes over a comb
@@ -90,7 +90,9 @@ typedef struct {
      (include/eddsa_amd.h: eddsa_amd_keyset), whose HBM these point to: ks_keys 32 bytes, ks_flags one byte (on the curve),
      ks_table VERIFY_ITEM_TABLE_WORDS words per key, ks_count keys.  key_idx lies in HBM like the other arrays of the pass and
      is advanced with them by src_at.  Host side only: the keyed kernels take the pointers as arguments of their own
-     (keyed_kernels.h); initialisers that stop earlier leave them NULL; never set together with `digest` or `dom` */
+     (keyed_kernels.h); initialisers that stop earlier leave them NULL.  With `digest` (ed25519_verify_keyed_digests*) or `dom`
+     (ed25519ctx_verify_keyed*, ed25519ph_verify_keyed*) the keyed kernels run in their digest forms; the combination takes
+     `digest` and refuses `dom` (rlc.hip: edk_verify_rlc) */
   const uint8_t *ks_keys, *ks_flags;
   const uint32_t* ks_table;
   size_t ks_count;

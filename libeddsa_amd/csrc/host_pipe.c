@@ -971,6 +971,26 @@ static int run_verify_keyed_rlc(struct engine *e, const struct hjob *j, const st
                                  j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1], j->ks->comb };
     return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
 }
+/* the digest forms over a key set: run_verify_digests / run_verify_digests_rlc with the second input of run_verify_keyed */
+static int run_verify_keyed_digests(struct engine *e, const struct hjob *j, const struct chunk *c)
+{
+    const edk_verify_src src = { c->d_in[0], NULL, c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1, 0, NULL, 0,
+                                 j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1], j->ks->comb };
+    return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
+}
+static int run_verify_keyed_digests_rlc(struct engine *e, const struct hjob *j, const struct chunk *c)
+{
+    const edk_verify_src src = { c->d_in[0], NULL, c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1, 0, NULL, 0,
+                                 j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1], j->ks->comb };
+    return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
+}
+/* Ed25519ctx / Ed25519ph over a key set: run_verify_keyed under the call's dom2 prefix (j->ks and j->dom are both set) */
+static int run_verify_keyed_dom(struct engine *e, const struct hjob *j, const struct chunk *c)
+{
+    const edk_verify_src src = { c->d_in[0], NULL, c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, j->dom, 0,
+                                 j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1], j->ks->comb };
+    return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
+}
 static int run_sign_dom(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     return run_done(sign_dom_on(e, c->d_out, c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, c->m, j->dom, c->st), c);
@@ -994,7 +1014,8 @@ RUN_1IN(run_sk_to_x, sk_to_x_on)
  * makes one combination per 2^20 items; it, the records form and the digest forms (their
  * message counterparts with the digests in the message slot, 64 bytes per item) are never merged by the combiner. */
 enum { OP_VERIFY, OP_VERIFY_RLC, OP_VERIFY_RECORDS, OP_VERIFY_DIGESTS, OP_VERIFY_DIGESTS_RLC, OP_SIGN, OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X,
-       OP_VERIFY_DOM, OP_SIGN_DOM, OP_VERIFY_KEYED, OP_VERIFY_KEYED_RLC };
+       OP_VERIFY_DOM, OP_SIGN_DOM, OP_VERIFY_KEYED, OP_VERIFY_KEYED_RLC, OP_VERIFY_KEYED_DIGESTS, OP_VERIFY_KEYED_DIGESTS_RLC,
+       OP_VERIFY_KEYED_DOM };
 static const struct op g_ops[] = {
     [OP_VERIFY] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify, .wipe = WIPE_NONE, .chain = 0,
                     .kind = KIND_VERIFY, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
@@ -1022,6 +1043,14 @@ static const struct op g_ops[] = {
     /* its batch verification: the inputs of OP_VERIFY_KEYED, one combination per chunk like OP_VERIFY_RLC */
     [OP_VERIFY_KEYED_RLC] = { .n_in = 2, .in_w = { 64, 4, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_keyed_rlc, .wipe = WIPE_NONE, .chain = 0,
                     .kind = KIND_NONE, .chunk = CHUNK_MAX, .first_chunk = CHUNK_MAX, .reports = 1 },
+    /* the digest and ctx / ph forms over a key set: the rows of OP_VERIFY_KEYED and OP_VERIFY_KEYED_RLC - the digests or prehashes
+     * travel in the message slot, EDDSA_DIGEST_BYTES wide; never merged (key sets and contexts differ from call to call) */
+    [OP_VERIFY_KEYED_DIGESTS] = { .n_in = 2, .in_w = { 64, 4, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_keyed_digests, .wipe = WIPE_NONE, .chain = 0,
+                    .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
+    [OP_VERIFY_KEYED_DIGESTS_RLC] = { .n_in = 2, .in_w = { 64, 4, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_keyed_digests_rlc, .wipe = WIPE_NONE, .chain = 0,
+                    .kind = KIND_NONE, .chunk = CHUNK_MAX, .first_chunk = CHUNK_MAX, .reports = 1 },
+    [OP_VERIFY_KEYED_DOM] = { .n_in = 2, .in_w = { 64, 4, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_keyed_dom, .wipe = WIPE_NONE, .chain = 0,
+                    .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
 };
 
 /* a call of operation `id` (in1, msgs, msg_off: NULL where the operation has none) */
@@ -1075,6 +1104,53 @@ int ed25519_verify_keyed_rlc(uint8_t *ok, uint32_t stats[4], const eddsa_amd_key
     int rc = pipe_run(j, n);
     if (stats) memcpy(stats, local, sizeof(local));
     return rc;
+}
+
+/* the digest, Ed25519ctx and Ed25519ph forms over a key set (include/eddsa_amd.h): NULL arguments end the call before any device
+ * is asked; the ctx / ph prefix is built before that (a context of more than 255 bytes ends the call there) and lives on the entry
+ * point's frame for the length of the call */
+static int keyed_forms_run(int op, uint8_t *ok, uint32_t *stats, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                           const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, const edk_dom *dom)
+{
+    uint32_t local[4] = { 0, 0, 0, 0 };
+    if (!ks) return -(int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if (!ok || !key_idx || !sigs || (!msgs && msg_len && !msg_off)) return -(int)hipErrorInvalidValue;   /* (fixed-length items need their buffer) */
+    struct hjob j = job(op, ok, sigs, (const uint8_t *)key_idx, msgs, msg_off, msg_len);
+    j.ks = ks;
+    j.dom = dom;
+    if (op == OP_VERIFY_KEYED_DIGESTS_RLC) j.stats = local;
+    int rc = pipe_run(j, n);
+    if (stats) memcpy(stats, local, sizeof(local));
+    return rc;
+}
+
+int ed25519_verify_keyed_digests(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
+                                 const uint8_t *digests, size_t n)
+{
+    return keyed_forms_run(OP_VERIFY_KEYED_DIGESTS, ok, NULL, ks, key_idx, sigs, digests, NULL, EDDSA_DIGEST_BYTES, n, NULL);
+}
+
+int ed25519_verify_keyed_digests_rlc(uint8_t *ok, uint32_t stats[4], const eddsa_amd_keyset *ks, const uint32_t *key_idx,
+                                     const uint8_t *sigs, const uint8_t *digests, size_t n)
+{
+    return keyed_forms_run(OP_VERIFY_KEYED_DIGESTS_RLC, ok, stats, ks, key_idx, sigs, digests, NULL, EDDSA_DIGEST_BYTES, n, NULL);
+}
+
+int ed25519ctx_verify_keyed(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs, const uint8_t *msgs,
+                            const uint64_t *msg_off, size_t msg_len, size_t n, const uint8_t *context, size_t context_len)
+{
+    edk_dom dom;
+    const int rc = dom2_fill(&dom, 0, context, context_len);
+    return rc ? rc : keyed_forms_run(OP_VERIFY_KEYED_DOM, ok, NULL, ks, key_idx, sigs, msgs, msg_off, msg_len, n, &dom);
+}
+
+int ed25519ph_verify_keyed(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs, const uint8_t *prehashes,
+                           size_t n, const uint8_t *context, size_t context_len)
+{
+    edk_dom dom;
+    const int rc = dom2_fill(&dom, 1, context, context_len);
+    return rc ? rc : keyed_forms_run(OP_VERIFY_KEYED_DOM, ok, NULL, ks, key_idx, sigs, prehashes, NULL, EDDSA_PREHASH_BYTES, n, &dom);
 }
 
 int ed25519_verify_digests(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n)

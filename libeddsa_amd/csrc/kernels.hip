@@ -1527,7 +1527,7 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
   edk_verify_src src = *srcp;
   if (n == 0) return hipSuccess;
   const bool keyed = src.ks_table != nullptr;     // ed25519_verify_keyed*: the keys come from a key set, by src.key_idx
-  if (keyed && (src.digest || src.dom || !src.key_idx || !src.ks_keys || !src.ks_flags || src.ks_count == 0 || src.ks_count > (size_t)UINT32_MAX)) return hipErrorInvalidValue;
+  if (keyed && (!src.key_idx || !src.ks_keys || !src.ks_flags || src.ks_count == 0 || src.ks_count > (size_t)UINT32_MAX)) return hipErrorInvalidValue;
   const bool comb = keyed && src.ks_comb != nullptr;   // ... and the set holds a comb per key: both scalars by fixed-base arithmetic
   if (comb && !ws->comb) return hipErrorInvalidValue;
   const verify_route r = verify_route_of(n, ws->algo, ws->exact_offcurve, keyed, comb);
@@ -1544,8 +1544,19 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
   if (keyed) {
     // the keyed prepare takes the key bytes and the on-curve flag from the key set and leaves the bytes in ws->keybytes: every
     // kernel behind it that reads `pubs` (the cofactored equation, the strict rules) reads them there
-    EDK_LAUNCH(k_verify_prepare_keyed, dim3(blocks), dim3(BLOCK), 0, stream, edk_items_of(&src), n, ws->digits, ws->flags, ws->onlist, ws->offlist,
-               ws->offcount, ws->exact_offcurve, perm, src.ks_keys, src.ks_flags, src.key_idx, (uint32_t)src.ks_count, ws->keybytes, ok);
+    // Its digest form serves ed25519_verify_keyed_digests* (the caller's digests in the message slot) and, behind
+    // k_dom_challenge_keyed, the ctx / ph keyed forms: one lane per item hashes dom2 || R || keys[key_idx] || M' into the item's
+    // 64 bytes of ws->domdig, and the pass goes on as a keyed digest pass over that area, as the unkeyed one does below
+    edk_verify_items items = edk_items_of(&src);
+    if (src.dom) {
+      EDK_LAUNCH(k_dom_challenge_keyed, dim3(blocks), dim3(BLOCK), 0, stream, items, n, ws->domdig, perm, *src.dom, src.ks_keys, src.key_idx,
+                 (uint32_t)src.ks_count);
+      items = { src.sigs, nullptr, ws->domdig, nullptr, EDK_DOM_DIGEST_BYTES, src.sig_stride, src.pub_stride, EDK_DOM_DIGEST_BYTES, nullptr };
+    }
+    const auto prepare = src.digest || src.dom ? k_verify_prepare_keyed<true> : k_verify_prepare_keyed<false>;
+    EDK_LAUNCH(prepare, dim3(blocks), dim3(BLOCK), 0, stream, items, n, ws->digits, ws->flags, ws->onlist, ws->offlist, ws->offcount,
+               ws->exact_offcurve, src.digest || src.dom ? nullptr : perm, src.ks_keys, src.ks_flags, src.key_idx, (uint32_t)src.ks_count,
+               ws->keybytes, ok);
     // the items listed for the exact path get a table of their own (none in reject mode, which has no such path)
     if (ws->exact_offcurve) EDK_LAUNCH(k_keyed_exact_tables, dim3(blocks), dim3(BLOCK), 0, stream, ws->table, ws->keybytes, ws->offlist, ws->offcount);
     src.pubs = ws->keybytes;

@@ -2,7 +2,8 @@
 // kernels.hip's translation unit (it uses that file's BLOCK, wave_append and launch shapes) and included by nothing else.
 //
 //   k_keyset_build           once per key set, one lane per key: the table 0..8 * (-A) and the on-curve flag (keyed_lanes.h)
-//   k_verify_prepare_keyed   k_verify_prepare with the key taken by index: no square root and no table
+//   k_verify_prepare_keyed   k_verify_prepare with the key taken by index: no square root and no table; <true>: its digest form
+//   k_dom_challenge_keyed    k_dom_challenge with the key taken by index (ed25519ctx_verify_keyed*, ed25519ph_verify_keyed*)
 //   k_keyed_exact_tables     the items that kernel listed for the exact path get a table of their own, as in an unkeyed pass
 //   k_verify_halve_keyed     k_verify_halve; an item it hands to the exact path gets a copy of its key's table in its own slot
 //   k_verify_main_half_keyed, k_verify_main_keyed   the one-lane evaluations with tab_a = the key's table in the key set
@@ -31,6 +32,11 @@ k_keyset_build(uint32_t* keytab, uint8_t* keyflags, const uint8_t* keys, size_t 
 // src.pubs is not read.  An item whose index names no key (key_idx >= count) is decided HERE: ok = 0, on neither work list, and
 // the bytes of keyed_no_key in its key-bytes slot, so that the cofactored equation, which decides every rejected item again from
 // those bytes, rejects it too.  The kernel holds no square root and builds no table: see k_keyed_exact_tables.
+// DIGEST (ed25519_verify_keyed_digests*, and behind k_dom_challenge_keyed): as in k_verify_prepare, the item's 64 bytes of
+// SHA-512(R || A || M) lie in the message slot of src and nothing is hashed; perm is not used (the launcher passes none).  Which
+// instantiation runs is the launcher's choice (src.digest), never a lane's; <false> is the kernel it was
+// (profiles/verify_keyed_forms.txt, section 1).
+template <bool DIGEST>
 __global__ void __launch_bounds__(BLOCK, 2)
 k_verify_prepare_keyed(edk_verify_items src, size_t n, uint32_t* digits, uint8_t* flags, uint32_t* onlist, uint32_t* offlist,
                        uint32_t* offcount, int offcurve_mode, const uint32_t* perm, const uint8_t* keys, const uint8_t* keyflags,
@@ -48,7 +54,12 @@ k_verify_prepare_keyed(edk_verify_items src, size_t n, uint32_t* digits, uint8_t
   asm volatile("" : "+v"(kf));
   store32(keybytes, i, 32, aw);
   if (g < n && !known) ok[i] = 0;
-  {
+  if constexpr (DIGEST) {
+    uint32_t dw[16];
+    load32(dw, src.msgs, item, src.msg_stride);
+    load32(dw + 8, src.msgs + 32, item, src.msg_stride);
+    verify_digest_lane(tw, dw);
+  } else {
     uint32_t rw[8];
     const uint8_t* m; size_t mlen;
     load32(rw, src.sigs, item, src.sig_stride);
@@ -69,6 +80,30 @@ k_verify_prepare_keyed(edk_verify_items src, size_t n, uint32_t* digits, uint8_t
   if (live && windowed) onlist[on_slot] = (uint32_t)i;
   const uint32_t off_slot = wave_append(offcount + EDK_OFFLIST_WORD, live && exact);
   if (live && exact) offlist[off_slot] = (uint32_t)i;
+}
+
+// k_dom_challenge (kernels.hip) with A taken by index: position g hashes item perm[g] (ragged messages in order of length) or
+// item g under the dom2 prefix, and SHA-512(dom2 || R || A || M') goes to the ITEM's 64 bytes of `digests` (ws->domdig), which
+// k_verify_prepare_keyed<true> reads behind it.  An index outside the key set hashes the bytes of keyed_no_key - what that
+// kernel leaves in the item's key-bytes slot, so the cofactored equation decides the item from the same t - and reads nothing
+// of the key set.
+__global__ void __launch_bounds__(BLOCK, 2)
+k_dom_challenge_keyed(edk_verify_items src, size_t n, uint8_t* digests, const uint32_t* perm, edk_dom dom, const uint8_t* keys,
+                      const uint32_t* key_idx, uint32_t count) {
+  __shared__ uint32_t lds_dom[EDK_DOM_WORDS];
+  stage_dom(lds_dom, dom);
+  const size_t g = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (g >= n) return;
+  const size_t item = perm ? perm[g] : g;
+  uint32_t rw[8], aw[8], dig[16];
+  const uint8_t* m; size_t mlen;
+  const uint32_t k = key_idx[item];
+  if (k < count) load32(aw, keys, k, 32); else keyed_no_key(aw);
+  load32(rw, src.sigs, item, src.sig_stride);
+  msg_span(m, mlen, src.msgs, src.msg_off, src.msg_end, src.msg_len, src.msg_stride, item);
+  verify_dom_hash_lane(dig, lds_dom, dom.len, rw, aw, m, mlen);
+  store32(digests, item, EDK_DOM_DIGEST_BYTES, dig);
+  store32(digests + 32, item, EDK_DOM_DIGEST_BYTES, dig + 8);
 }
 
 // The exact path reads - and writes over - the item's OWN table, which k_verify_prepare builds for every item.  In a keyed pass

@@ -696,7 +696,7 @@ extern "C" hipError_t edk_verify_rlc(uint8_t* ok, uint32_t* stats, const edk_ver
 
   // a pass over a key set (ed25519_verify_keyed_rlc*; rlc_keyed.h): at most RLC_G keys - rlc_on sends wider sets to the per-item kernels
   const bool keyed = src.ks_table != nullptr;
-  if (keyed && (src.digest || src.dom || !src.key_idx || !src.ks_keys || src.ks_count == 0 || src.ks_count > (size_t)RLC_G)) return hipErrorInvalidValue;
+  if (keyed && (src.dom || !src.key_idx || !src.ks_keys || src.ks_count == 0 || src.ks_count > (size_t)RLC_G)) return hipErrorInvalidValue;
   const uint32_t count = keyed ? (uint32_t)src.ks_count : 0u;
   uint32_t* keypts = reinterpret_cast<uint32_t*>(base + L.keypts);
   uint8_t* keyflags = base + L.keyflags;
@@ -707,9 +707,10 @@ extern "C" hipError_t edk_verify_rlc(uint8_t* ok, uint32_t* stats, const edk_ver
   if (keyed) {
     EDK_DO(hipMemsetAsync(keyacc, 0, groups * count * (size_t)RLC_KEY_ACC_WORDS * 8, stream));
     EDK_LAUNCH(k_rlc_keys, dim3((count + RLC_BLOCK - 1) / RLC_BLOCK), dim3(RLC_BLOCK), 0, stream, src.ks_keys, count, keypts, keyflags);
-    const uint32_t* perm = nullptr;
-    EDK_DO(edk_msg_order(&perm, ws, src.msg_off, src.msg_end, n, stream));
-    EDK_LAUNCH(k_rlc_hash_keyed, dim3(blocks), dim3(RLC_BLOCK), 0, stream, items, n, ts, leaf, perm, src.ks_keys, src.key_idx, count, ws->keybytes);
+    const uint32_t* perm = nullptr;            // (caller-supplied digests, ed25519_verify_keyed_digests_rlc*: nothing to order)
+    if (!src.digest) EDK_DO(edk_msg_order(&perm, ws, src.msg_off, src.msg_end, n, stream));
+    const auto hash = src.digest ? k_rlc_hash_keyed<true> : k_rlc_hash_keyed<false>;
+    EDK_LAUNCH(hash, dim3(blocks), dim3(RLC_BLOCK), 0, stream, items, n, ts, leaf, perm, src.ks_keys, src.key_idx, count, ws->keybytes);
   } else if (src.digest) {
     EDK_LAUNCH(k_rlc_hash_digest, dim3(blocks), dim3(RLC_BLOCK), 0, stream, items, n, ts, leaf);
   } else {

@@ -4,7 +4,7 @@
 //   k_rlc_keys            once per pass, one lane per key of the set (at most RLC_G): -A_k as an affine niels point and the key's
 //                         routing flag - the square roots of a pass are `count`, not one per item
 //   k_rlc_hash_keyed      k_rlc_hash with the key bytes taken by index; leaves them in edk_verify_ws.keybytes like
-//                         k_verify_prepare_keyed, where k_verify_policy reads `pubs`
+//                         k_verify_prepare_keyed, where k_verify_policy reads `pubs`; <true>: its digest form
 //   k_rlc_points_keyed    -R only; the item's flags are R's OR its key's routing flag
 //   k_rlc_scalars_keyed   k_rlc_scalars, but the key term z t mod 8 l is ADDED to the accumulator of (group, key) instead of
 //                         recoded per item
@@ -30,6 +30,11 @@ k_rlc_keys(const uint8_t* keys, uint32_t count, uint32_t* keypts, uint8_t* keyfl
   niels_store(keypts + 32 * (size_t)k, nl);
 }
 
+// DIGEST (ed25519_verify_keyed_digests_rlc*): k_rlc_hash_digest's t, S and leaf - item i's 64 bytes of SHA-512(R || A || M) lie
+// in the message slot of src, nothing but the leaf is hashed, perm is not used - with the key bytes still taken by index and left
+// in keybytes.  The leaf is SHA-512(digest || S) in both forms, as in the unkeyed kernels: the seed and the coefficients of a
+// keyed pass are those of the unkeyed pass over the expanded keys.  The launcher chooses the instantiation (src.digest).
+template <bool DIGEST>
 __global__ void __launch_bounds__(RLC_BLOCK, 2)
 k_rlc_hash_keyed(edk_verify_items src, size_t n, uint32_t* ts, uint32_t* leaf, const uint32_t* perm, const uint8_t* keys,
                  const uint32_t* key_idx, uint32_t count, uint8_t* keybytes) {
@@ -40,11 +45,19 @@ k_rlc_hash_keyed(edk_verify_items src, size_t n, uint32_t* ts, uint32_t* leaf, c
   const uint32_t k = key_idx[i];
   if (k < count) load32(aw, keys, k, 32); else keyed_no_key(aw);
   store32(keybytes, i, 32, aw);
-  load32(rw, src.sigs, i, src.sig_stride);
-  load32(sw, src.sigs + 32, i, src.sig_stride);
-  const uint8_t* m; size_t mlen;
-  msg_span(m, mlen, src.msgs, src.msg_off, src.msg_end, src.msg_len, src.msg_stride, i);
-  rlc_hash_lane(tw, sw, lf, rw, aw, src.sigs + i * src.sig_stride + 32, m, mlen);
+  if constexpr (DIGEST) {
+    uint32_t dw[16];
+    load32(dw, src.msgs, i, src.msg_stride);
+    load32(dw + 8, src.msgs + 32, i, src.msg_stride);
+    load32(sw, src.sigs + 32, i, src.sig_stride);
+    rlc_digest_lane(tw, sw, lf, dw, src.sigs + i * src.sig_stride + 32);
+  } else {
+    load32(rw, src.sigs, i, src.sig_stride);
+    load32(sw, src.sigs + 32, i, src.sig_stride);
+    const uint8_t* m; size_t mlen;
+    msg_span(m, mlen, src.msgs, src.msg_off, src.msg_end, src.msg_len, src.msg_stride, i);
+    rlc_hash_lane(tw, sw, lf, rw, aw, src.sigs + i * src.sig_stride + 32, m, mlen);
+  }
   rlc_hash_store(ts, leaf, i, tw, sw, lf);
 }
 
