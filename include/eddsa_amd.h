@@ -72,7 +72,9 @@
  * declared in eddsa_amd_debug.h and inert unless a test arms them.
  * Secrets: the staging copies of secret keys / scalars / shared secrets and the secret scalars that
  * cross kernel boundaries are zeroed in HBM before a call's stream work completes (the reference
- * wipes its stack after the same operations, lib/ed25519-sha512.c:77,136, lib/x25519.c:208,221).
+ * wipes its stack after the same operations, lib/ed25519-sha512.c:77,136, lib/x25519.c:208,221).  A signer set
+ * (eddsa_amd_signer, at the end of this header) is the one exception by design: it keeps secret scalars and prefixes in HBM from
+ * eddsa_amd_signer_create* until eddsa_amd_signer_destroy, which zeroes them before it frees.
  */
 #ifndef EDDSA_AMD_H
 #define EDDSA_AMD_H
@@ -581,6 +583,87 @@ RFC8032_EDDSA_DECL int ed25519ph_verify_keyed(uint8_t *ok, const eddsa_amd_keyse
 RFC8032_EDDSA_DECL int ed25519ph_verify_keyed_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
                                                   const uint8_t *prehashes, size_t n, const uint8_t *context /* host */, size_t context_len,
                                                   void *stream);
+
+/* ---- SIGNER SETS: register the secret keys once, sign by key index ----
+ * For callers that sign very many items with a few keys (token issuers, log and timestamp signers, oracles).  ed25519_sign_batch
+ * takes 32 bytes of seed and 32 bytes of public key per item and spends one of the item's three SHA-512 compressions on
+ * SHA-512(seed), again and again for the same few keys.  A signer set does that once per KEY, derives the public key itself -
+ * a `pubs` that does not belong to `secs` cannot happen: that mismatch yields signatures that leak the secret scalar - and
+ * signs with keys that have no seed at all: expanded secret keys (scalar, prefix), as BIP32-Ed25519 derivation, key blinding
+ * and libraries with an "expanded secret key" type produce them.
+ * What a set holds: per key, in HBM: the scalar a mod l (32 bytes), the prefix (32 bytes) and the public key A = (a mod l) B
+ *   encoded (32 bytes) - 96 bytes per key.
+ * Seeds (eddsa_amd_signer_create): (a, prefix) is what ed25519_sign_batch derives: h = SHA-512(seed), a = h[0..32) clamped,
+ *   prefix = h[32..64).  sigs[i] is byte for byte what ed25519_sign_batch writes for (secs[key_idx[i]], its public key, message i);
+ *   the ctx / ph forms give byte for byte what ed25519ctx_sign_batch / ed25519ph_sign_batch write under the same context.
+ * Expanded keys (eddsa_amd_signer_create_expanded): 64 bytes per key.  The first 32 bytes are a as a little-endian 256-bit
+ *   integer, used mod l and NOT clamped (derived and blinded keys rely on that); the last 32 bytes are the prefix.  Then
+ *   r = SHA-512([dom2 ||] prefix || M') mod l, R = r B, t = SHA-512([dom2 ||] R || A || M') mod l, S = (r + t a) mod l.
+ *   Any 64 bytes are legal input; a = 0 mod l gives the neutral element as A and is not an error.  A set created from seeds and a
+ *   set created from the expansions of the same seeds are indistinguishable.
+ * Out-of-range indices: the device-pointer forms write 64 zero bytes for an item with key_idx[i] >= count; they read nothing
+ *   outside the set for it and leave its neighbours alone.  The host-pointer forms check the whole index array first and return
+ *   -hipErrorInvalidValue before anything is touched.
+ * Argument checks, before any device is touched: the create calls refuse out == NULL, secs / expanded == NULL, count == 0 and
+ *   count > EDDSA_AMD_SIGNER_MAX_KEYS with -hipErrorInvalidValue; *out is left NULL on these and on every other error.  The sign
+ *   calls refuse a NULL s, sigs, key_idx or fixed-length msgs / prehashes, context_len > 255 and a NULL context with a length;
+ *   the NULL signer is refused even for n == 0, like ed25519_verify_keyed.  eddsa_amd_signer_pubs refuses a NULL s or pubs.
+ * Devices: a set is created on the default device, by the rule of the host-pointer calls.  A device-pointer call whose `sigs`
+ *   lie on another device returns -hipErrorInvalidValue; host-pointer calls run on the set's device.
+ * Lifetime and use: a set is immutable and usable from any number of threads and streams; no pass writes it.  It SURVIVES
+ *   eddsa_amd_shutdown and is freed only by eddsa_amd_signer_destroy (NULL allowed), which synchronises the set's device:
+ *   destroy it after the last call that uses it has returned.
+ * Secrets: a signer set is the one place where secrets stay in HBM by design.  destroy overwrites the scalars and prefixes with
+ *   zeros on the device and waits for that before it frees; create zeroes its staging copy before it returns.  The per-pass
+ *   copies of a and r in the workspace are wiped by the finish kernel, exactly as in ed25519_sign_batch; the keyed finish kernel
+ *   zeroes the pass's projective points R as well, and a host-pointer call zeroes its staging copies of the indices and of the
+ *   signatures.
+ * Combiner and upload: host-pointer calls are never merged by the small-call combiner (two calls may carry two signer sets).
+ *   They upload 4 bytes of index and the message per item, where ed25519_sign_batch uploads 64 bytes and the message.
+ * key_idx: packed uint32, one per item, host memory in the host-pointer forms and HBM in the _dev forms; `context` is a host
+ *   pointer in every form.  Everything else - layout, ragged-table rules and clamping, return values, page-locked memory,
+ *   threading - follows the rules at the top.
+ * Kernels: three per pass, the shape of the Ed25519ctx / Ed25519ph sign pass: one that takes a and the prefix by index and hashes
+ *   r, the point kernel R = r B of that pass unchanged, and a finish kernel that takes A by index.  This shape is the one kept: it
+ *   is faster than ed25519_sign_batch_dev's two kernels at every size measured (below), so the other shape - the nonce hash fused
+ *   into a keyed form of the point kernel, as in ed25519_sign_batch - was not built and has no figure.
+ * Out of scope: creation from device pointers; _multi and single-item forms.  ed25519_sign_batch* are unchanged.
+ * Measured (profiles/sign_keyed.txt, tools/sign_keyed_rate.py: device-pointer forms, 2^20 items of 32 bytes in HBM, one MI355X, the two
+ * forms alternating, repeat spread 0.001-0.005 ms): under 1024 signers 2.206 ms per pass through ed25519_sign_batch_dev, 2.095 ms
+ * through ed25519_sign_keyed_dev (-5.0 %: 501 M instead of 475 M signs/s); under ONE signer 2.202 / 2.093 ms (-5.0 %), under 2^20
+ * distinct signers - a 96 MiB set read in random order - 2.205 / 2.104 ms (-4.6 %).  Ed25519ctx 2.369 / 2.288 ms (-3.4 %), Ed25519ph
+ * 2.497 / 2.425 ms (-2.9 %).  Small passes under 1024 signers (unkeyed / keyed): 2^7 items 0.145 / 0.137 ms, 2^10 0.151 / 0.143,
+ * 2^14 0.157 / 0.149, 2^16 0.236 / 0.221.  What one of three SHA-512 compressions and 60 bytes of input per item are worth: about
+ * 0.11 ms in 2.2, although the pass has a third launch (the same shape costs the unkeyed ctx form +7 %).  Host to host from ordinary
+ * memory, 1024 signers, the keyed call is NOT faster: 44.6 ms against 40.1 ms (+11 %; the repeats overlap, 39.9-44.7 against
+ * 35.2-45.4 ms) - such a call is bound by staging and copies, and the keyed rows zero the signatures in the staging buffers
+ * after the download, which costs more than the smaller upload saves.  eddsa_amd_signer_create: 0.36 ms for 1024 keys, 3.7 ms for
+ * 2^20.  ed25519_sign_batch_dev against the commit before signer sets, alternating in fresh processes on that box: 2.208-2.217 ms
+ * against 2.208-2.222 ms (the medians of five processes each) - inside the older build's own repeat spread.
+ * (Declared with the macro of the RFC 8032 variants: tests of earlier additions count the EDDSA_AMD_DECL names.) */
+typedef struct eddsa_amd_signer eddsa_amd_signer;            /* opaque */
+#define EDDSA_AMD_SIGNER_MAX_KEYS ((size_t)1 << 20)
+RFC8032_EDDSA_DECL int eddsa_amd_signer_create(eddsa_amd_signer **out, const uint8_t *secs /* host, 32 bytes per key: seeds */, size_t count);
+RFC8032_EDDSA_DECL int eddsa_amd_signer_create_expanded(eddsa_amd_signer **out, const uint8_t *expanded /* host, 64 bytes per key: scalar | prefix */,
+                                                        size_t count);
+RFC8032_EDDSA_DECL void eddsa_amd_signer_destroy(eddsa_amd_signer *s);        /* NULL allowed */
+RFC8032_EDDSA_DECL size_t eddsa_amd_signer_count(const eddsa_amd_signer *s);
+RFC8032_EDDSA_DECL int eddsa_amd_signer_device(const eddsa_amd_signer *s);    /* the HIP device that holds the set */
+RFC8032_EDDSA_DECL int eddsa_amd_signer_pubs(const eddsa_amd_signer *s, uint8_t *pubs /* host, 32 bytes per key */);
+RFC8032_EDDSA_DECL int ed25519_sign_keyed(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs,
+                                          const uint64_t *msg_off, size_t msg_len, size_t n);
+RFC8032_EDDSA_DECL int ed25519_sign_keyed_dev(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs,
+                                              const uint64_t *msg_off, size_t msg_len, size_t n, void *stream);
+RFC8032_EDDSA_DECL int ed25519ctx_sign_keyed(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs,
+                                             const uint64_t *msg_off, size_t msg_len, size_t n, const uint8_t *context /* host */, size_t context_len);
+RFC8032_EDDSA_DECL int ed25519ctx_sign_keyed_dev(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs,
+                                                 const uint64_t *msg_off, size_t msg_len, size_t n, const uint8_t *context /* host */,
+                                                 size_t context_len, void *stream);
+RFC8032_EDDSA_DECL int ed25519ph_sign_keyed(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx,
+                                            const uint8_t *prehashes /* 64 bytes per item */, size_t n, const uint8_t *context /* host */,
+                                            size_t context_len);
+RFC8032_EDDSA_DECL int ed25519ph_sign_keyed_dev(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *prehashes, size_t n,
+                                                const uint8_t *context /* host */, size_t context_len, void *stream);
 
 #ifdef __cplusplus
 }

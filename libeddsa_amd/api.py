@@ -942,6 +942,129 @@ def ed25519ph_verify_keyed(sigs, keyset, key_idx, prehashes, context=b""):
 
 
 # ---------------------------------------------------------------------------------------------
+# signer sets (include/eddsa_amd.h: eddsa_amd_signer): secret keys registered once, signed with by key index
+# ---------------------------------------------------------------------------------------------
+
+SIGNER_MAX_KEYS = 1 << 20                      # EDDSA_AMD_SIGNER_MAX_KEYS
+
+
+class Signer:
+    """A signer set (include/eddsa_amd.h: eddsa_amd_signer): secret keys registered once - per key the scalar a mod l, the prefix
+    and the public key it derives, in HBM - for ed25519_sign_keyed and its ctx / ph forms.  Immutable; lives until close() (or the
+    end of a `with` block), also across shutdown(); close() zeroes the secrets on the device."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("Signer: already closed")
+        return self._h
+
+    @property
+    def count(self):
+        lib = library()
+        lib.eddsa_amd_signer_count.restype = ctypes.c_size_t
+        return int(lib.eddsa_amd_signer_count(self._handle()))
+
+    @property
+    def device(self):
+        return int(library().eddsa_amd_signer_device(self._handle()))
+
+    def pubs(self):
+        """the public keys the set derived, (count, 32) uint8: what a verifier registers (keyset_create(signer.pubs()))"""
+        out = np.zeros((self.count, 32), dtype=np.uint8)
+        _check(library().eddsa_amd_signer_pubs(self._handle(), _np_ptr(out)), "eddsa_amd_signer_pubs")
+        return out
+
+    def close(self):
+        if self._h is not None:
+            library().eddsa_amd_signer_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def signer_create(secs=None, expanded=None):
+    """secs: count x 32 bytes of seeds, or expanded: count x 64 bytes of scalar | prefix (the scalar is used mod l, not clamped);
+    numpy / bytes, host memory; exactly one of the two -> Signer, on the default device."""
+    if (secs is None) == (expanded is None):
+        raise ValueError("signer_create: pass either secs or expanded")
+    lib = library()
+    h = _c_ptr()
+    name, keys, width = ("eddsa_amd_signer_create", secs, 32) if expanded is None else ("eddsa_amd_signer_create_expanded", expanded, 64)
+    keys = _as_np(keys, width, "secs" if expanded is None else "expanded")
+    _check(getattr(lib, name)(ctypes.byref(h), _np_ptr(keys), _c_size(keys.size // width)), name)
+    return Signer(h)
+
+
+def _run_sign_keyed(name, signer, key_idx, data, fixed=None, data_name="msgs", msg_off=None, msg_len=None, context=None):
+    """common driver of the three keyed sign calls: key indices and `data` - messages (fixed None) or prehashes (`fixed` = 64 bytes
+    per item, no offsets) - under `context` (None: the C function takes none) -> (n, 64) uint8.  numpy / bytes (key_idx: uint32):
+    the host form `name`; CUDA tensors (key_idx: int32, read as unsigned): `name`_dev on torch's stream."""
+    ctx_args = []
+    if context is not None:
+        context = _context(context)
+        ctx_args = [ctypes.c_char_p(context), _c_size(len(context))]
+    handle = signer._handle()
+    lib = library()
+    msg_args = []
+    if _is_torch(key_idx):
+        import torch
+        if key_idx.dtype != torch.int32 or not key_idx.is_cuda or not key_idx.is_contiguous():
+            raise ValueError(f"{name}: key_idx: expected contiguous int32 indices on the device")
+        n = key_idx.numel()
+        data = _torch_check(data, fixed or 0, data_name)
+        if fixed and data.numel() != fixed * n:
+            raise ValueError(f"{name}: key_idx and {data_name} disagree on the batch size ({n}, {data.numel() // fixed} items)")
+        if not fixed:
+            _, off, mlen = _msg_args(data, msg_off, msg_len, n, True)
+            _torch_off_check(off, n)
+            msg_args = [_c_ptr(off.data_ptr()) if off is not None else None, _c_size(mlen)]
+        out = torch.empty((n, 64), dtype=torch.uint8, device=key_idx.device)
+        _check(getattr(lib, name + "_dev")(_c_ptr(out.data_ptr()), handle, _c_ptr(key_idx.data_ptr()), _c_ptr(data.data_ptr()), *msg_args,
+                                           _c_size(n), *ctx_args, _stream()), name + "_dev")
+        return out
+    key_idx = np.ascontiguousarray(np.asarray(key_idx))
+    if key_idx.dtype != np.uint32:
+        raise ValueError(f"{name}: key_idx: expected uint32 indices")
+    n = key_idx.size
+    data = _as_np(data, fixed or 0, data_name)
+    if fixed and data.size != fixed * n:
+        raise ValueError(f"{name}: key_idx and {data_name} disagree on the batch size ({n}, {data.size // fixed} items)")
+    if not fixed:
+        data, off, mlen = _host_msgs(data, msg_off, msg_len, n)
+        msg_args = [_np_ptr(off) if off is not None else None, _c_size(mlen)]
+    out = np.zeros((n, 64), dtype=np.uint8)
+    _check(getattr(lib, name)(_np_ptr(out), handle, _np_ptr(key_idx), _np_ptr(data), *msg_args, _c_size(n), *ctx_args), name)
+    return out
+
+
+def ed25519_sign_keyed(signer, key_idx, msgs, msg_off=None, msg_len=None):
+    """ed25519_sign_batch with item i's key taken from a signer set: the signatures of (key key_idx[i], message i) -> (n, 64) uint8.
+    numpy inputs take the host form (an index outside the set: EddsaAmdError, nothing is signed), CUDA tensors the device form
+    (such an item gets 64 zero bytes).  msgs / msg_off / msg_len: as in ed25519_sign_batch."""
+    return _run_sign_keyed("ed25519_sign_keyed", signer, key_idx, msgs, msg_off=msg_off, msg_len=msg_len)
+
+
+def ed25519ctx_sign_keyed(signer, key_idx, msgs, context, msg_off=None, msg_len=None):
+    """ed25519ctx_sign_batch with item i's key taken from a signer set -> (n, 64) uint8; `context`: host bytes, 0..255"""
+    return _run_sign_keyed("ed25519ctx_sign_keyed", signer, key_idx, msgs, msg_off=msg_off, msg_len=msg_len,
+                           context=context if context is not None else b"")
+
+
+def ed25519ph_sign_keyed(signer, key_idx, prehashes, context=b""):
+    """ed25519ph_sign_batch with item i's key taken from a signer set: prehashes[i] = SHA-512(M_i), 64 bytes per item -> (n, 64) uint8"""
+    return _run_sign_keyed("ed25519ph_sign_keyed", signer, key_idx, prehashes, fixed=PREHASH_BYTES, data_name="prehashes",
+                           context=context if context is not None else b"")
+
+
+# ---------------------------------------------------------------------------------------------
 # several devices in one process (include/eddsa_amd.h: *_multi), after init_devices()
 # ---------------------------------------------------------------------------------------------
 

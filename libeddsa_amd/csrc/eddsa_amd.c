@@ -563,6 +563,24 @@ static hipError_t sign_step(struct engine *e, size_t done, size_t m, const void 
                     e->comb_img, &with_dom, st);
 }
 
+struct sign_keyed_ctx { uint8_t *sigs; const edk_signer_set *set; const uint32_t *key_idx; const uint8_t *msgs; const uint64_t *msg_off, *msg_end;
+                        size_t msg_len; const edk_dom *dom; };
+
+/* edk_sign_keyed is a WEAK reference (edk_signer.h): without the HIP translation unit no signer set can exist, so no pass gets here */
+extern __typeof__(edk_signer_build) edk_signer_build __attribute__((weak));
+extern __typeof__(edk_sign_keyed) edk_sign_keyed __attribute__((weak));
+
+static hipError_t sign_keyed_step(struct engine *e, size_t done, size_t m, const void *vctx, const edk_fixed_ws *fws, hipStream_t st)
+{
+    const struct sign_keyed_ctx *c = (const struct sign_keyed_ctx *)vctx;
+    const uint8_t *mp = c->msg_off ? c->msgs : c->msgs + done * c->msg_len;
+    const uint64_t *op = c->msg_off ? c->msg_off + done : NULL;
+    edk_fixed_ws with_dom = *fws;                  /* as in sign_step */
+    with_dom.dom = c->dom;
+    if (!edk_sign_keyed) return hipErrorNotSupported;
+    return edk_sign_keyed(c->sigs + 64 * done, c->set, c->key_idx + done, mp, op, c->msg_end, c->msg_len, m, e->comb_img, &with_dom, st);
+}
+
 struct io_ctx { uint8_t *out; const uint8_t *in; };
 struct io2_ctx { uint8_t *out; const uint8_t *a, *b; };
 
@@ -597,6 +615,13 @@ int sign_on(struct engine *e, uint8_t *sigs, const uint8_t *secs, const uint8_t 
                    const uint64_t *msg_off, size_t msg_len, size_t n, hipStream_t st)
 {
     return sign_dom_on(e, sigs, secs, pubs, msgs, msg_off, msg_len, n, NULL, st);
+}
+
+int sign_keyed_on(struct engine *e, uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs,
+                  const uint64_t *msg_off, size_t msg_len, size_t n, const edk_dom *dom, hipStream_t st)
+{
+    struct sign_keyed_ctx c = { sigs, &s->set, key_idx, msgs, msg_off, msg_off ? msg_off + n : NULL, msg_len, dom };
+    return fixed_on(e, n, sign_keyed_step, &c, st);
 }
 
 /* dom2(flag, context) of RFC 8032 section 2 as the kernels take it (eddsa_kernels.h: edk_dom); a context of more than 255 bytes,
@@ -1001,6 +1026,126 @@ int ed25519ph_sign_batch_dev(uint8_t *sigs, const uint8_t *secs, const uint8_t *
                              const uint8_t *context, size_t context_len, void *stream)
 {
     return dom_sign_dev(1, sigs, secs, pubs, prehashes, NULL, EDDSA_PREHASH_BYTES, n, context, context_len, stream);
+}
+
+/* ------------------------------------------------------------------------------------------
+ * signer sets (include/eddsa_amd.h): secret keys registered once, signed with by index
+ * ---------------------------------------------------------------------------------------- */
+
+static void signer_free(eddsa_amd_signer *s)
+{
+    if (s->mem) wipe_free(s->mem, s->count * 64);  /* the scalars and the prefixes are zeroed on the device before the memory goes back */
+    free(s);
+}
+
+/* keys: host memory, `width` bytes per key (32: seeds, 64: scalar | prefix); on the default device.  The keys are staged through a
+ * device buffer that is zeroed before the call returns; the caller's memory is not page-locked and nothing else copies it. */
+static int signer_create_on(eddsa_amd_signer **out, const uint8_t *keys, size_t count, size_t width)
+{
+    struct call c;
+    int rc;
+    eddsa_amd_signer *s;
+    uint8_t *stage = NULL;
+    if (!edk_signer_build || !edk_sign_keyed) return -(int)hipErrorNotSupported;
+    if ((rc = enter(&c, -1))) return rc;
+    s = (eddsa_amd_signer *)calloc(1, sizeof(*s));
+    if (!s) { rc = -(int)hipErrorOutOfMemory; goto out; }
+    s->device = c.e->device;
+    s->count = count;
+    TRY(hipMalloc((void **)&s->mem, count * 96));
+    TRY(hipMalloc((void **)&stage, count * width));
+    s->set.a = (const uint32_t *)s->mem;
+    s->set.prefix = (const uint32_t *)(s->mem + count * 32);
+    s->set.pubs = s->mem + count * 64;
+    s->set.count = count;
+    TRY(hipMemcpyAsync(stage, keys, count * width, hipMemcpyHostToDevice, NULL));
+    TRY(edk_signer_build((uint32_t *)s->mem, (uint32_t *)(s->mem + count * 32), s->mem + count * 64, stage, count, width == 64, c.e->comb_img, NULL));
+    TRY(hipStreamSynchronize(NULL));
+    *out = s;
+    s = NULL;
+out:
+    if (stage) { HIP_NOTE(hipStreamSynchronize(NULL)); wipe_free(stage, count * width); }
+    if (s) signer_free(s);
+    leave(&c);
+    return rc;
+}
+
+int eddsa_amd_signer_create(eddsa_amd_signer **out, const uint8_t *secs, size_t count)
+{
+    if (out) *out = NULL;
+    if (!out || !secs || count == 0 || count > EDDSA_AMD_SIGNER_MAX_KEYS) return -(int)hipErrorInvalidValue;
+    return signer_create_on(out, secs, count, 32);
+}
+
+int eddsa_amd_signer_create_expanded(eddsa_amd_signer **out, const uint8_t *expanded, size_t count)
+{
+    if (out) *out = NULL;
+    if (!out || !expanded || count == 0 || count > EDDSA_AMD_SIGNER_MAX_KEYS) return -(int)hipErrorInvalidValue;
+    return signer_create_on(out, expanded, count, 64);
+}
+
+void eddsa_amd_signer_destroy(eddsa_amd_signer *s)
+{
+    int saved = -1;
+    if (!s) return;
+    HIP_NOTE(hipGetDevice(&saved));
+    HIP_NOTE(hipSetDevice(s->device));
+    HIP_NOTE(hipDeviceSynchronize());      /* passes that read the set may still be queued */
+    signer_free(s);
+    if (saved >= 0) HIP_NOTE(hipSetDevice(saved));
+}
+
+size_t eddsa_amd_signer_count(const eddsa_amd_signer *s) { return s ? s->count : 0; }
+int eddsa_amd_signer_device(const eddsa_amd_signer *s) { return s ? s->device : -1; }
+
+int eddsa_amd_signer_pubs(const eddsa_amd_signer *s, uint8_t *pubs)
+{
+    int saved = -1, rc = 0;
+    if (!s || !pubs) return -(int)hipErrorInvalidValue;
+    TRY(hipGetDevice(&saved));
+    TRY(hipSetDevice(s->device));
+    TRY(hipMemcpy(pubs, s->set.pubs, s->count * 32, hipMemcpyDeviceToHost));
+out:
+    if (saved >= 0) HIP_NOTE(hipSetDevice(saved));
+    return rc;
+}
+
+/* the three device-pointer forms: the NULL arguments are refused before any device is asked, the signer even for an empty batch */
+static int sign_keyed_dev(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
+                          size_t msg_len, size_t n, const edk_dom *dom, void *stream)
+{
+    struct call c;
+    int rc = 0, dev = -1;
+    if (!s) return -(int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if (!sigs || !key_idx || (!msgs && msg_len && !msg_off)) return -(int)hipErrorInvalidValue;   /* (fixed-length items need their buffer) */
+    if ((rc = device_of(sigs, &dev))) return rc;
+    if (dev != s->device) return -(int)hipErrorInvalidValue;   /* the set's secrets live on its own device */
+    if ((rc = enter(&c, dev))) return rc;
+    return leave_with(&c, sign_keyed_on(c.e, sigs, s, key_idx, msgs, msg_off, msg_len, n, dom, (hipStream_t)stream));
+}
+
+int ed25519_sign_keyed_dev(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
+                           size_t msg_len, size_t n, void *stream)
+{
+    return sign_keyed_dev(sigs, s, key_idx, msgs, msg_off, msg_len, n, NULL, stream);
+}
+
+/* (the prefix is built first: a context of more than 255 bytes ends the call before anything else is looked at) */
+int ed25519ctx_sign_keyed_dev(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
+                              size_t msg_len, size_t n, const uint8_t *context, size_t context_len, void *stream)
+{
+    edk_dom dom;
+    const int rc = dom2_fill(&dom, 0, context, context_len);
+    return rc ? rc : sign_keyed_dev(sigs, s, key_idx, msgs, msg_off, msg_len, n, &dom, stream);
+}
+
+int ed25519ph_sign_keyed_dev(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *prehashes, size_t n,
+                             const uint8_t *context, size_t context_len, void *stream)
+{
+    edk_dom dom;
+    const int rc = dom2_fill(&dom, 1, context, context_len);
+    return rc ? rc : sign_keyed_dev(sigs, s, key_idx, prehashes, NULL, EDDSA_PREHASH_BYTES, n, &dom, stream);
 }
 
 int ed25519_genpub_batch_dev(uint8_t *pubs, const uint8_t *secs, size_t n, void *stream)

@@ -31,6 +31,7 @@
 #include "eddsa_amd_debug.h"
 #include "eddsa_kernels.h"
 #include "edk_keyed.h"
+#include "edk_signer.h"
 
 #ifndef CHUNK_MAX                     /* (tests/fake_hip builds one variant with tiny passes: tests/c/multi_passes.c) */
 #define CHUNK_MAX ((size_t)1 << 20)   /* verify items per workspace pass: 1.6 GB of HBM workspace */
@@ -164,6 +165,15 @@ struct eddsa_amd_keyset {
     size_t bytes;                     /* HBM the set holds: what eddsa_amd_keyset_bytes reports */
 };
 
+/* A signer set (include/eddsa_amd.h): immutable after eddsa_amd_signer_create*, owned by the caller like a key set - it outlives
+ * eddsa_amd_shutdown and is freed by eddsa_amd_signer_destroy alone, which zeroes the secrets first.  Passes only read it. */
+struct eddsa_amd_signer {
+    int device;
+    size_t count;
+    uint8_t *mem;                     /* HBM, one allocation of count * 96 bytes: a | prefix | pubs, count * 32 bytes each */
+    edk_signer_set set;               /* the three parts of mem as the launcher takes them */
+};
+
 extern pthread_rwlock_t g_table;
 extern struct engine *g_eng[MAX_DEVICES];
 extern struct multi g_multi;
@@ -197,6 +207,9 @@ int sign_on(struct engine *e, uint8_t *sigs, const uint8_t *secs, const uint8_t 
 int sign_dom_on(struct engine *e, uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
                 const uint64_t *msg_off, size_t msg_len, size_t n, const edk_dom *dom, hipStream_t st);
 int dom2_fill(edk_dom *d, int flag, const uint8_t *context, size_t context_len);
+/* sign_dom_on with the secret scalar, the prefix and the public key of item i taken from a signer set by key_idx[i] (HBM) */
+int sign_keyed_on(struct engine *e, uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs,
+                  const uint64_t *msg_off, size_t msg_len, size_t n, const edk_dom *dom, hipStream_t st);
 int genpub_on(struct engine *e, uint8_t *pubs, const uint8_t *secs, size_t n, hipStream_t st);
 int x25519_on(struct engine *e, uint8_t *out, const uint8_t *scalars, const uint8_t *points, size_t n, hipStream_t st);
 int xbase_on(struct engine *e, uint8_t *out, const uint8_t *scalars, size_t n, hipStream_t st);

@@ -256,6 +256,7 @@ struct hjob {
     int src_pinned;                            /* every host array of the job is page-locked: no staging */
     const edk_dom *dom;                        /* Ed25519ctx / Ed25519ph: the call's dom2 prefix (lives on the entry point's stack); else NULL */
     const eddsa_amd_keyset *ks;                /* ed25519_verify_keyed: the caller's key set (in[1] then holds the key indices); else NULL */
+    const eddsa_amd_signer *sg;                /* ed25519_sign_keyed: the caller's signer set (in[0] then holds the key indices); else NULL */
 };
 
 static size_t in_w(const struct hjob *j, int i) { return j->op->in_w[i] ? j->op->in_w[i] : j->stride; }
@@ -889,12 +890,12 @@ static int combiner_submit(struct engine *e, const struct hjob *j, size_t n)
     return me.rc;
 }
 
-/* on the default device - a keyed call: on its key set's */
+/* on the default device - a keyed call: on its key set's or its signer set's */
 static int pipe_run(const struct hjob j, size_t n)
 {
     struct call c;
     if (n == 0) return 0;
-    int rc = enter(&c, j.ks ? j.ks->device : -1);
+    int rc = enter(&c, j.ks ? j.ks->device : j.sg ? j.sg->device : -1);
     if (rc) return rc;
     if (j.op->kind && n <= COMBINE_MAX_N && !(j.op->has_msgs && (j.msg_off || n * j.msg_len > COMBINE_MAX_BYTES)))
         rc = combiner_submit(c.e, &j, n);
@@ -995,6 +996,12 @@ static int run_sign_dom(struct engine *e, const struct hjob *j, const struct chu
 {
     return run_done(sign_dom_on(e, c->d_out, c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, c->m, j->dom, c->st), c);
 }
+/* signing over a signer set: the chunk's one input is its slice of the key indices, the secrets come from the job's signer set;
+ * j->dom NULL: Ed25519, else Ed25519ctx / Ed25519ph under the call's prefix */
+static int run_sign_keyed(struct engine *e, const struct hjob *j, const struct chunk *c)
+{
+    return run_done(sign_keyed_on(e, c->d_out, j->sg, (const uint32_t *)c->d_in[0], c->d_msgs, c->d_off, j->msg_len, c->m, j->dom, c->st), c);
+}
 static int run_x25519(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
     (void)j;
@@ -1015,7 +1022,7 @@ RUN_1IN(run_sk_to_x, sk_to_x_on)
  * message counterparts with the digests in the message slot, 64 bytes per item) are never merged by the combiner. */
 enum { OP_VERIFY, OP_VERIFY_RLC, OP_VERIFY_RECORDS, OP_VERIFY_DIGESTS, OP_VERIFY_DIGESTS_RLC, OP_SIGN, OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X,
        OP_VERIFY_DOM, OP_SIGN_DOM, OP_VERIFY_KEYED, OP_VERIFY_KEYED_RLC, OP_VERIFY_KEYED_DIGESTS, OP_VERIFY_KEYED_DIGESTS_RLC,
-       OP_VERIFY_KEYED_DOM };
+       OP_VERIFY_KEYED_DOM, OP_SIGN_KEYED, OP_SIGN_KEYED_DOM };
 static const struct op g_ops[] = {
     [OP_VERIFY] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify, .wipe = WIPE_NONE, .chain = 0,
                     .kind = KIND_VERIFY, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
@@ -1051,6 +1058,13 @@ static const struct op g_ops[] = {
                     .kind = KIND_NONE, .chunk = CHUNK_MAX, .first_chunk = CHUNK_MAX, .reports = 1 },
     [OP_VERIFY_KEYED_DOM] = { .n_in = 2, .in_w = { 64, 4, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_keyed_dom, .wipe = WIPE_NONE, .chain = 0,
                     .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
+    /* signing over a signer set: the rows of OP_SIGN and OP_SIGN_DOM with 4 bytes of key index per item where those upload 64 bytes
+     * of keys; never merged - two small calls may carry different signer sets.  A signing process keeps nothing of a call in the
+     * staging buffers: which key signed what, and the signatures, are zeroed there like the other operations' secrets */
+    [OP_SIGN_KEYED] = { .n_in = 1, .in_w = { 4, 0, 0 }, .out_w = 64, .has_msgs = 1, .run = run_sign_keyed, .wipe = WIPE_IN0 | WIPE_OUT, .chain = 1,
+                    .kind = KIND_NONE },
+    [OP_SIGN_KEYED_DOM] = { .n_in = 1, .in_w = { 4, 0, 0 }, .out_w = 64, .has_msgs = 1, .run = run_sign_keyed, .wipe = WIPE_IN0 | WIPE_OUT, .chain = 1,
+                    .kind = KIND_NONE },
 };
 
 /* a call of operation `id` (in1, msgs, msg_off: NULL where the operation has none) */
@@ -1181,6 +1195,46 @@ int ed25519_sign_batch(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, 
                        const uint64_t *msg_off, size_t msg_len, size_t n)
 {
     return pipe_run(job(OP_SIGN, sigs, secs, pubs, msgs, msg_off, msg_len), n);
+}
+
+/* signing over a signer set (include/eddsa_amd.h): NULL arguments end the call before any device is asked, the signer even for an
+ * empty batch; then the WHOLE index array is checked - an index outside the set ends the call before anything is touched (the
+ * device-pointer forms, which cannot look, write 64 zero bytes for such an item) */
+static int sign_keyed_run(int op, uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
+                          size_t msg_len, size_t n, const edk_dom *dom)
+{
+    uint32_t bad = 0;
+    if (!s) return -(int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    if (!sigs || !key_idx || (!msgs && msg_len && !msg_off)) return -(int)hipErrorInvalidValue;   /* (fixed-length items need their buffer) */
+    for (size_t i = 0; i < n; i++) bad |= (uint32_t)(key_idx[i] >= s->count);
+    if (bad) return -(int)hipErrorInvalidValue;
+    struct hjob j = job(op, sigs, (const uint8_t *)key_idx, NULL, msgs, msg_off, msg_len);
+    j.sg = s;
+    j.dom = dom;
+    return pipe_run(j, n);
+}
+
+int ed25519_sign_keyed(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
+                       size_t msg_len, size_t n)
+{
+    return sign_keyed_run(OP_SIGN_KEYED, sigs, s, key_idx, msgs, msg_off, msg_len, n, NULL);
+}
+
+int ed25519ctx_sign_keyed(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
+                          size_t msg_len, size_t n, const uint8_t *context, size_t context_len)
+{
+    edk_dom dom;
+    const int rc = dom2_fill(&dom, 0, context, context_len);
+    return rc ? rc : sign_keyed_run(OP_SIGN_KEYED_DOM, sigs, s, key_idx, msgs, msg_off, msg_len, n, &dom);
+}
+
+int ed25519ph_sign_keyed(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *prehashes, size_t n,
+                         const uint8_t *context, size_t context_len)
+{
+    edk_dom dom;
+    const int rc = dom2_fill(&dom, 1, context, context_len);
+    return rc ? rc : sign_keyed_run(OP_SIGN_KEYED_DOM, sigs, s, key_idx, prehashes, NULL, EDDSA_PREHASH_BYTES, n, &dom);
 }
 
 /* Ed25519ctx / Ed25519ph (include/eddsa_amd.h): the prefix is built before anything is touched - a context of more than 255

@@ -19,8 +19,10 @@
 //   k_init_tables    generates what the reference ships as lib/ed_lookup64.h
 //   k_keyset_build, k_verify_*_keyed          key-set verification (keyed_kernels.h): the key's table by index
 //   k_keyset_comb_build, k_verify_main_comb_keyed   comb key sets (keyed_kernels.h): a comb per key, both scalars fixed-base
+//   k_signer_build, k_sign_keyed_*            signer sets (signer_kernels.h): the secret scalar, the prefix and A by key index
 #include "eddsa_kernels.h"
 #include "edk_keyed.h"
+#include "edk_signer.h"
 #include "edk_checked.h"
 #include "kernel_io.h"
 #include "lanes.h"
@@ -1252,6 +1254,7 @@ k_verify_main_sums_quad(uint8_t* ok, const uint32_t* hdigits, const uint32_t* su
 }  // namespace ed
 
 #include "keyed_kernels.h"   // key-set verification: kernels of its own beside the ones above
+#include "signer_kernels.h"  // signer sets: likewise, beside the sign kernels
 
 // =============================================================================================
 // launchers (host side of this translation unit)
@@ -1706,6 +1709,44 @@ hipError_t edk_sign(uint8_t* sigs, const uint8_t* secs, const uint8_t* pubs, con
   }
   if (const hipError_t e = launch_point(k_sign_point<POINT_SPLIT>, k_sign_point<1>, n, ws, stream, ws->acc, ws->aux, secs, msgs, msg_off, msg_end, msg_len, n, comb, perm); e != hipSuccess) return e;
   hipLaunchKernelGGL(k_sign_finish, dim3(f.grid), dim3(BLOCK), 0, stream, sigs, ws->acc, ws->aux, pubs, msgs, msg_off, msg_end, msg_len, n, f.k, perm);
+  return hipGetLastError();
+}
+
+// a signer set (edk_signer.h): `count` seeds or expanded keys in HBM -> a mod l, the prefixes and the encoded public keys.
+// Asynchronous on `stream`
+hipError_t edk_signer_build(uint32_t* a, uint32_t* prefix, uint8_t* pubs, const uint8_t* keys, size_t count, int expanded, const uint32_t* comb,
+                            hipStream_t stream) {
+  if (count == 0) return hipSuccess;
+  const dim3 grid(blocks_of(count, POINT_BLOCK)), block(POINT_BLOCK);
+  if (expanded) hipLaunchKernelGGL(k_signer_build<true>, grid, block, 0, stream, a, prefix, pubs, keys, count, comb);
+  else hipLaunchKernelGGL(k_signer_build<false>, grid, block, 0, stream, a, prefix, pubs, keys, count, comb);
+  return hipGetLastError();
+}
+
+// edk_sign over a signer set: scalars, point, finish - the shapes of the Ed25519ctx / Ed25519ph pass, whose point kernel it
+// shares.  The fused shape (hash and comb in one kernel, as k_sign_point) was not built: include/eddsa_amd.h has the figures
+hipError_t edk_sign_keyed(uint8_t* sigs, const edk_signer_set* set, const uint32_t* key_idx, const uint8_t* msgs, const uint64_t* msg_off,
+                          const uint64_t* msg_end, size_t msg_len, size_t n, const uint32_t* comb, const edk_fixed_ws* ws, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  const finish_shape f = finish_shape_of(n);
+  const uint32_t count = (uint32_t)set->count;
+  const uint32_t* perm = nullptr;                  // ragged messages: both hashing kernels take their items in order of length
+  if (const hipError_t e = msg_order(&perm, ws->perm, ws->lenbins, msg_off, msg_end, n, stream); e != hipSuccess) return e;
+  static const edk_dom no_dom = {};
+  const edk_dom& dom = ws->dom ? *ws->dom : no_dom;
+  if (ws->dom)
+    hipLaunchKernelGGL(k_sign_keyed_scalars<true>, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, ws->aux, set->a, set->prefix, count, key_idx, msgs,
+                       msg_off, msg_end, msg_len, n, perm, dom);
+  else
+    hipLaunchKernelGGL(k_sign_keyed_scalars<false>, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, ws->aux, set->a, set->prefix, count, key_idx, msgs,
+                       msg_off, msg_end, msg_len, n, perm, dom);
+  if (const hipError_t e = launch_point(k_sign_dom_point<POINT_SPLIT>, k_sign_dom_point<1>, n, ws, stream, ws->acc, (const uint32_t*)ws->aux, n, comb); e != hipSuccess) return e;
+  if (ws->dom)
+    hipLaunchKernelGGL(k_sign_keyed_finish<true>, dim3(f.grid), dim3(BLOCK), 0, stream, sigs, ws->acc, ws->aux, set->pubs, count, key_idx, msgs,
+                       msg_off, msg_end, msg_len, n, f.k, perm, dom);
+  else
+    hipLaunchKernelGGL(k_sign_keyed_finish<false>, dim3(f.grid), dim3(BLOCK), 0, stream, sigs, ws->acc, ws->aux, set->pubs, count, key_idx, msgs,
+                       msg_off, msg_end, msg_len, n, f.k, perm, dom);
   return hipGetLastError();
 }
 
