@@ -11,9 +11,7 @@ LIB     := libeddsa_amd/libeddsa_amd.so
 # -amdgpu-dpp-combine=false: the combiner's v_subrev_u32_dpp computes dpp(src1) - src0 on this hardware instead of
 # src1 - dpp(src0) (tools/microbench/dpp_subrev.hip); the lane exchanges of quad_lanes.h stay separate v_mov_b32_dpp
 HIPFLAGS := -O3 --offload-arch=$(ARCH) -fPIC -fvisibility=hidden -DEDDSA_BUILD -Iinclude -I$(CSRC) -mllvm -amdgpu-dpp-combine=false
-# -Wno-missing-field-initializers: initialisers of edk_verify_src stop at the last field their form uses and leave the trailing
-# ones (dom, the key set) zero, as eddsa_kernels.h says
-CFLAGS   := -std=c11 -O2 -fPIC -fvisibility=hidden -Wall -Wextra -Wno-missing-field-initializers -DEDDSA_BUILD -Iinclude -I$(CSRC) -I$(ROCM)/include
+CFLAGS   := -std=c11 -O2 -fPIC -fvisibility=hidden -Wall -Wextra -DEDDSA_BUILD -Iinclude -I$(CSRC) -I$(ROCM)/include
 
 PROBE   := libeddsa_amd/libeddsa_amd_probe.so
 # The same objects plus the test and measurement hooks of include/eddsa_amd_debug.h (-DEDDSA_AMD_DEBUG_BUILD compiles them into

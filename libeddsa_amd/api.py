@@ -418,34 +418,30 @@ def _torch_check(t, width, name):
     return t
 
 
-def _torch_off_check(off, n):
-    """ragged-message offsets on the device: n+1 64-bit words (the kernels read them as uint64)"""
-    import torch
-    if off is None:
-        return
-    if not _is_torch(off) or not off.is_cuda or not off.is_contiguous() or \
-            off.dtype not in (torch.int64, torch.uint64) or off.numel() != n + 1:
-        raise ValueError("msg_off: expected n+1 contiguous int64/uint64 offsets on the device")
-
-
 def _stream():
     import torch
     return _c_ptr(torch.cuda.current_stream().cuda_stream)
 
 
-def _msg_args(msgs, msg_off, msg_len, n, on_device):
-    """-> (msgs_ptr_holder, off_ptr_holder, msg_len)"""
+def _msg_span(total, msg_off, msg_len, n, on_device):
+    """how `total` message bytes are cut into n messages -> (the offset table or None, msg_len): msg_len bytes each (default
+    total / n), or ragged by msg_off[0..n] - on the device n+1 64-bit words (the kernels read them as uint64)"""
     if msg_off is None:
         if msg_len is None:
-            total = msgs.numel() if on_device else msgs.size
-            if n == 0:
-                msg_len = 0
-            elif total % n:
+            if n and total % n:
                 raise ValueError("msgs: size is not a multiple of the batch size; pass msg_len or msg_off")
-            else:
-                msg_len = total // n
-        return msgs, None, int(msg_len)
-    return msgs, msg_off, 0
+            msg_len = total // n if n else 0
+        return None, int(msg_len)
+    if on_device:
+        import torch
+        if not _is_torch(msg_off) or not msg_off.is_cuda or not msg_off.is_contiguous() or \
+                msg_off.dtype not in (torch.int64, torch.uint64) or msg_off.numel() != n + 1:
+            raise ValueError("msg_off: expected n+1 contiguous int64/uint64 offsets on the device")
+        return msg_off, 0
+    off = np.ascontiguousarray(np.asarray(msg_off, dtype=np.uint64))
+    if off.size != n + 1 or (n and int(off[-1]) > total):
+        raise ValueError("msg_off: expected n+1 offsets within msgs")
+    return off, 0
 
 
 def _run_32(fn_host, fn_dev, what, inputs, out_width, n_from):
@@ -474,76 +470,73 @@ def _run_32(fn_host, fn_dev, what, inputs, out_width, n_from):
     return out
 
 
-def _host_msgs(msgs, msg_off, msg_len, n):
-    msgs = _as_np(msgs, 0, "msgs")
-    _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, False)
-    if off is not None:
-        off = np.ascontiguousarray(np.asarray(off, dtype=np.uint64))
-        if off.size != n + 1 or (n and int(off[-1]) > msgs.size):
-            raise ValueError("msg_off: expected n+1 offsets within msgs")
-    return msgs, off, mlen
-
-
-def _run_msgs(fn_host, fn_dev, what, first, first_w, first_name, pubs, msgs, msg_off, msg_len, out_shape, stats=None,
-              msgs_first=False):
-    """common driver for the calls that carry messages: `first` (sigs or secs: first_w bytes per item), pubs and msgs
-    -> (n,) + out_shape uint8.  fn_dev None: host pointers only.  stats (None: the C function takes no statistics): true
-    -> (output, the four counters); false on the device path: NULL is passed, nothing is counted.  msgs_first: the host path
-    looks at msgs before it compares the batch sizes (which complaint a doubly wrong call gets)."""
-    lib = library()
-    if fn_dev and _is_torch(first):
-        import torch
-        first = _torch_check(first, first_w, first_name); pubs = _torch_check(pubs, 32, "pubs")
-        msgs = _torch_check(msgs, 0, "msgs")
-        n = first.numel() // first_w
-        if pubs.numel() // 32 != n:
-            raise ValueError(f"{what}: {first_name} and pubs disagree on the batch size")
-        _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, True)
-        _torch_off_check(off, n)
-        out = torch.empty((n,) + out_shape, dtype=torch.uint8, device=first.device)
-        counts = torch.zeros((4,), dtype=torch.int32, device=first.device) if stats else None
-        args = [out] + ([counts] if stats is not None else []) + [first, pubs, msgs, off]
-        args = [_c_ptr(t.data_ptr()) if t is not None else None for t in args] + [_c_size(mlen), _c_size(n), _stream()]
-        _check(getattr(lib, fn_dev)(*args), what)
-        return (out, tuple(int(x) for x in counts.cpu())) if stats else out
-    first = _as_np(first, first_w, first_name); pubs = _as_np(pubs, 32, "pubs")
-    if msgs_first:
-        msgs = _as_np(msgs, 0, "msgs")
-    n = first.size // first_w
-    if pubs.size // 32 != n:
-        raise ValueError(f"{what}: {first_name} and pubs disagree on the batch size")
-    msgs, off, mlen = _host_msgs(msgs, msg_off, msg_len, n)
-    out = np.zeros((n,) + out_shape, dtype=np.uint8)
-    counts = (ctypes.c_uint32 * 4)()
-    args = [_np_ptr(out)] + ([counts] if stats is not None else []) + [_np_ptr(first), _np_ptr(pubs), _np_ptr(msgs)]
-    _check(getattr(lib, fn_host)(*args, _np_ptr(off) if off is not None else None, _c_size(mlen), _c_size(n)), what)
-    return (out, tuple(int(x) for x in counts)) if stats else out
-
-
-def _run_digests(fn_host, fn_dev, what, sigs, pubs, digests, stats=None):
-    """common driver for the calls that take caller-supplied digests instead of messages: sigs (64 bytes per item), pubs (32)
-    and digests (64) -> (n,) uint8.  fn_dev None: host pointers only.  stats: as in _run_msgs."""
-    inputs = [(sigs, 64, "sigs"), (pubs, 32, "pubs"), (digests, 64, "digests")]
-    on_device = bool(fn_dev) and _is_torch(sigs)
-    arrs = [_torch_check(a, w, nm) if on_device else _as_np(a, w, nm) for a, w, nm in inputs]
-    counts_of = [(a.numel() if on_device else a.size) // w for a, (_, w, _) in zip(arrs, inputs)]
-    n = counts_of[0]
-    if counts_of[1] != n or counts_of[2] != n:
-        raise ValueError(f"{what}: sigs, pubs and digests disagree on the batch size ({counts_of[0]}, {counts_of[1]}, {counts_of[2]} items)")
-    lib = library()
+def _key_indices(name, key_idx, n, on_device):
+    """the key indices of a keyed call, uint32 on the host and int32 (read as unsigned) on the device -> (the array, its length);
+    n None: the array sets the batch size, else it must hold n indices"""
     if on_device:
         import torch
-        out = torch.empty((n,), dtype=torch.uint8, device=arrs[0].device)
+        if not _is_torch(key_idx) or key_idx.dtype != torch.int32 or not key_idx.is_cuda or not key_idx.is_contiguous():
+            raise ValueError(f"{name}: key_idx: expected contiguous int32 indices on the device")
+        count = key_idx.numel()
+    else:
+        key_idx = np.ascontiguousarray(np.asarray(key_idx))
+        if key_idx.dtype != np.uint32:
+            raise ValueError(f"{name}: key_idx: expected uint32 indices")
+        count = key_idx.size
+    if n is not None and count != n:
+        raise ValueError(f"{name}: key_idx holds {count} indices, expected {n}")
+    return key_idx, count
+
+
+def _run_items(name, lead, data, out_shape, keyed=None, fixed=None, data_name="msgs", msg_off=None, msg_len=None, context=None,
+               stats=None, dev=True, sizes_first=False):
+    """The one driver of the calls that carry items and messages -> (n,) + out_shape uint8.  numpy / bytes: the host form `name`;
+    CUDA tensors (dev false: host pointers only): `name`_dev on torch's stream.  The C argument list is
+        out [, stats] [, handle, key_idx] , lead arrays... , data [, msg_off, msg_len] , n [, context, context_len] [, stream]
+    lead     the fixed-width arrays [(array, bytes per item, name), ...] in the C order
+    keyed    (Keyset or Signer, key_idx) of a keyed call; without a lead array key_idx sets the batch size
+    data     ragged / fixed-length messages (msg_off, msg_len), or `fixed` bytes per item under the name data_name (digests,
+             prehashes), which the C function takes without offsets and length
+    context  None: the C function takes none; else what _context() made of the caller's
+    stats    None: the C function takes no statistics; true -> (output, the four counters); false on the device: NULL is
+             passed, nothing is counted
+    sizes_first  the batch sizes are compared before `data` is looked at (which complaint a doubly wrong call gets)"""
+    ctx_args = [] if context is None else [ctypes.c_char_p(context), _c_size(len(context))]
+    handle = [keyed[0]._handle()] if keyed else []
+    on_device = dev and _is_torch(lead[0][0] if lead else keyed[1])
+    check, size, ptr = (_torch_check, lambda t: t.numel(), lambda t: _c_ptr(t.data_ptr())) if on_device else \
+                       (_as_np, lambda a: a.size, _np_ptr)
+    arrs = [check(a, w, nm) for a, w, nm in lead]
+    if not sizes_first:
+        data = check(data, fixed or 0, data_name)
+    n = size(arrs[0]) // lead[0][1] if lead else None
+    for a, (_, w, nm) in zip(arrs[1:], lead[1:]):
+        if size(a) // w != n:
+            raise ValueError(f"{name}: {lead[0][2]} and {nm} disagree on the batch size")
+    if keyed:
+        key_idx, n = _key_indices(name, keyed[1], n, on_device)
+        arrs.insert(0, key_idx)
+    if sizes_first:
+        data = check(data, fixed or 0, data_name)
+    if fixed:
+        if size(data) != fixed * n:
+            raise ValueError(f"{name}: {data_name} holds {size(data) // fixed} items of {fixed} bytes, expected {n}")
+        msg_args = []
+    else:
+        off, mlen = _msg_span(size(data), msg_off, msg_len, n, on_device)
+        msg_args = [ptr(off) if off is not None else None, _c_size(mlen)]
+    if on_device:
+        import torch
+        out = torch.empty((n,) + out_shape, dtype=torch.uint8, device=arrs[0].device)
         counts = torch.zeros((4,), dtype=torch.int32, device=arrs[0].device) if stats else None
-        args = [out] + ([counts] if stats is not None else []) + arrs
-        args = [_c_ptr(t.data_ptr()) if t is not None else None for t in args] + [_c_size(n), _stream()]
-        _check(getattr(lib, fn_dev)(*args), what)
-        return (out, tuple(int(x) for x in counts.cpu())) if stats else out
-    out = np.zeros((n,), dtype=np.uint8)
-    counts = (ctypes.c_uint32 * 4)()
-    args = [_np_ptr(out)] + ([counts] if stats is not None else []) + [_np_ptr(a) for a in arrs]
-    _check(getattr(lib, fn_host)(*args, _c_size(n)), what)
-    return (out, tuple(int(x) for x in counts)) if stats else out
+    else:
+        out = np.zeros((n,) + out_shape, dtype=np.uint8)
+        counts = np.zeros(4, dtype=np.uint32)
+    stats_args = [] if stats is None else [ptr(counts) if counts is not None else None]
+    fn = getattr(library(), name + "_dev" if on_device else name)
+    _check(fn(ptr(out), *stats_args, *handle, *[ptr(a) for a in arrs], ptr(data), *msg_args, _c_size(n), *ctx_args,
+              *([_stream()] if on_device else [])), name)
+    return (out, tuple(int(x) for x in (counts.cpu() if on_device else counts))) if stats else out
 
 
 # ---------------------------------------------------------------------------------------------
@@ -585,8 +578,7 @@ def ed25519_verify_batch(sigs, pubs, msgs, msg_off=None, msg_len=None):
 
     msgs is the concatenation of all messages; either every message has msg_len bytes
     (default: len(msgs) / n) or msg_off[0..n] (uint64) gives the ragged boundaries."""
-    return _run_msgs("ed25519_verify_batch", "ed25519_verify_batch_dev", "ed25519_verify_batch",
-                     sigs, 64, "sigs", pubs, msgs, msg_off, msg_len, (), msgs_first=True)
+    return _run_items("ed25519_verify_batch", [(sigs, 64, "sigs"), (pubs, 32, "pubs")], msgs, (), msg_off=msg_off, msg_len=msg_len)
 
 
 def ed25519_verify_batch_rlc(sigs, pubs, msgs, msg_off=None, msg_len=None, return_stats=False):
@@ -594,21 +586,21 @@ def ed25519_verify_batch_rlc(sigs, pubs, msgs, msg_off=None, msg_len=None, retur
     lib/ed25519-sha512.c:13-14): same arguments and verdicts as ed25519_verify_batch, groups that do not
     pass fall back to the per-item kernels.  return_stats=True -> (ok, (items decided by the combination,
     items decided per item, groups sent to the per-item kernels, groups decided by the combination))."""
-    return _run_msgs("ed25519_verify_batch_rlc", "ed25519_verify_batch_rlc_dev", "ed25519_verify_batch_rlc",
-                     sigs, 64, "sigs", pubs, msgs, msg_off, msg_len, (), stats=bool(return_stats))
+    return _run_items("ed25519_verify_batch_rlc", [(sigs, 64, "sigs"), (pubs, 32, "pubs")], msgs, (), msg_off=msg_off, msg_len=msg_len,
+                      stats=bool(return_stats), sizes_first=True)
 
 
 def ed25519_verify_digests(sigs, pubs, digests):
     """loop of ed25519_verify for callers that already hold digests[i] = SHA-512(R_i || A_i || M_i) (64 bytes per item, as
     hashlib.sha512(...).digest() returns them): no message is uploaded or hashed -> (n,) uint8, 1 = accept.  The caller vouches
     that each digest was computed over the R and A bytes of this call's sigs[i] and pubs[i] (include/eddsa_amd.h)."""
-    return _run_digests("ed25519_verify_digests", "ed25519_verify_digests_dev", "ed25519_verify_digests", sigs, pubs, digests)
+    return _run_items("ed25519_verify_digests", [(sigs, 64, "sigs"), (pubs, 32, "pubs")], digests, (), fixed=64, data_name="digests")
 
 
 def ed25519_verify_digests_rlc(sigs, pubs, digests, return_stats=False):
     """ed25519_verify_batch_rlc from caller-supplied digests (see ed25519_verify_digests): same verdicts, same statistics"""
-    return _run_digests("ed25519_verify_digests_rlc", "ed25519_verify_digests_rlc_dev", "ed25519_verify_digests_rlc",
-                        sigs, pubs, digests, stats=bool(return_stats))
+    return _run_items("ed25519_verify_digests_rlc", [(sigs, 64, "sigs"), (pubs, 32, "pubs")], digests, (), fixed=64, data_name="digests",
+                      stats=bool(return_stats))
 
 
 KEYSET_MAX_KEYS = 1 << 20                      # EDDSA_AMD_KEYSET_MAX_KEYS, include/eddsa_amd.h
@@ -684,65 +676,15 @@ def ed25519_verify_keyed(sigs, keyset, key_idx, msgs, msg_off=None, msg_len=None
     """ed25519_verify_batch with item i's key taken from a key set: keys[key_idx[i]] -> (n,) uint8, 1 = accept; an index outside
     the key set rejects its item.  numpy inputs (key_idx: uint32) take the host form, CUDA tensors (key_idx: int32, read as
     unsigned) the device form on torch's current stream.  msgs / msg_off / msg_len: as in ed25519_verify_batch."""
-    lib = library()
-    what = "ed25519_verify_keyed"
-    if _is_torch(sigs):
-        import torch
-        sigs = _torch_check(sigs, 64, "sigs"); msgs = _torch_check(msgs, 0, "msgs")
-        n = sigs.numel() // 64
-        if not _is_torch(key_idx) or key_idx.dtype != torch.int32 or not key_idx.is_cuda or not key_idx.is_contiguous() or key_idx.numel() != n:
-            raise ValueError(f"{what}: key_idx: expected n contiguous int32 indices on the device")
-        _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, True)
-        _torch_off_check(off, n)
-        out = torch.empty((n,), dtype=torch.uint8, device=sigs.device)
-        _check(lib.ed25519_verify_keyed_dev(_c_ptr(out.data_ptr()), keyset._handle(), _c_ptr(key_idx.data_ptr()), _c_ptr(sigs.data_ptr()),
-                                            _c_ptr(msgs.data_ptr()), _c_ptr(off.data_ptr()) if off is not None else None,
-                                            _c_size(mlen), _c_size(n), _stream()), what + "_dev")
-        return out
-    sigs = _as_np(sigs, 64, "sigs")
-    n = sigs.size // 64
-    idx = np.ascontiguousarray(np.asarray(key_idx))
-    if idx.dtype != np.uint32 or idx.size != n:
-        raise ValueError(f"{what}: key_idx: expected n uint32 indices")
-    msgs, off, mlen = _host_msgs(msgs, msg_off, msg_len, n)
-    out = np.zeros((n,), dtype=np.uint8)
-    _check(lib.ed25519_verify_keyed(_np_ptr(out), keyset._handle(), _np_ptr(idx), _np_ptr(sigs), _np_ptr(msgs),
-                                    _np_ptr(off) if off is not None else None, _c_size(mlen), _c_size(n)), what)
-    return out
+    return _run_items("ed25519_verify_keyed", [(sigs, 64, "sigs")], msgs, (), keyed=(keyset, key_idx), msg_off=msg_off, msg_len=msg_len)
 
 
 def ed25519_verify_keyed_rlc(sigs, keyset, key_idx, msgs, msg_off=None, msg_len=None, return_stats=False):
     """OPT-IN batch verification over a key set (include/eddsa_amd.h): ed25519_verify_batch_rlc with item i's key taken as
     keys[key_idx[i]], for key sets of up to 8192 keys (wider ones run as ed25519_verify_keyed).  Inputs as ed25519_verify_keyed;
     return_stats as ed25519_verify_batch_rlc."""
-    lib = library()
-    what = "ed25519_verify_keyed_rlc"
-    if _is_torch(sigs):
-        import torch
-        sigs = _torch_check(sigs, 64, "sigs"); msgs = _torch_check(msgs, 0, "msgs")
-        n = sigs.numel() // 64
-        if not _is_torch(key_idx) or key_idx.dtype != torch.int32 or not key_idx.is_cuda or not key_idx.is_contiguous() or key_idx.numel() != n:
-            raise ValueError(f"{what}: key_idx: expected n contiguous int32 indices on the device")
-        _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, True)
-        _torch_off_check(off, n)
-        out = torch.empty((n,), dtype=torch.uint8, device=sigs.device)
-        counts = torch.zeros((4,), dtype=torch.int32, device=sigs.device) if return_stats else None
-        _check(lib.ed25519_verify_keyed_rlc_dev(_c_ptr(out.data_ptr()), _c_ptr(counts.data_ptr()) if return_stats else None, keyset._handle(),
-                                                _c_ptr(key_idx.data_ptr()), _c_ptr(sigs.data_ptr()), _c_ptr(msgs.data_ptr()),
-                                                _c_ptr(off.data_ptr()) if off is not None else None, _c_size(mlen), _c_size(n), _stream()),
-               what + "_dev")
-        return (out, tuple(int(x) for x in counts.cpu())) if return_stats else out
-    sigs = _as_np(sigs, 64, "sigs")
-    n = sigs.size // 64
-    idx = np.ascontiguousarray(np.asarray(key_idx))
-    if idx.dtype != np.uint32 or idx.size != n:
-        raise ValueError(f"{what}: key_idx: expected n uint32 indices")
-    msgs, off, mlen = _host_msgs(msgs, msg_off, msg_len, n)
-    out = np.zeros((n,), dtype=np.uint8)
-    counts = (ctypes.c_uint32 * 4)()
-    _check(lib.ed25519_verify_keyed_rlc(_np_ptr(out), counts, keyset._handle(), _np_ptr(idx), _np_ptr(sigs), _np_ptr(msgs),
-                                        _np_ptr(off) if off is not None else None, _c_size(mlen), _c_size(n)), what)
-    return (out, tuple(int(x) for x in counts)) if return_stats else out
+    return _run_items("ed25519_verify_keyed_rlc", [(sigs, 64, "sigs")], msgs, (), keyed=(keyset, key_idx), msg_off=msg_off, msg_len=msg_len,
+                      stats=bool(return_stats))
 
 
 def ed25519_verify_records(records, sig_off, pub_off, msg_off, msg_len):
@@ -772,8 +714,7 @@ def ed25519_verify_records(records, sig_off, pub_off, msg_off, msg_len):
 
 def ed25519_sign_batch(secs, pubs, msgs, msg_off=None, msg_len=None):
     """loop of ed25519_sign (reference lib/eddsa.h:47) -> (n, 64) uint8"""
-    return _run_msgs("ed25519_sign_batch", "ed25519_sign_batch_dev", "ed25519_sign_batch",
-                     secs, 32, "secs", pubs, msgs, msg_off, msg_len, (64,), msgs_first=True)
+    return _run_items("ed25519_sign_batch", [(secs, 32, "secs"), (pubs, 32, "pubs")], msgs, (64,), msg_off=msg_off, msg_len=msg_len)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -794,151 +735,62 @@ def _context(context):
     return context
 
 
-def _run_dom(name, first, first_w, first_name, pubs, msgs, msg_off, msg_len, out_shape, context, prehashed):
-    """common driver of the four calls: `first` (sigs or secs), pubs and msgs (prehashed: 64 bytes per item, no offsets) under
-    `context` -> (n,) + out_shape uint8.  numpy / bytes: the host form `name`; CUDA tensors: `name`_dev on torch's stream."""
-    context = _context(context)
-    ctx_args = [ctypes.c_char_p(context), _c_size(len(context))]
-    on_device = _is_torch(first)
-    if on_device:
-        import torch
-        first = _torch_check(first, first_w, first_name); pubs = _torch_check(pubs, 32, "pubs")
-        msgs = _torch_check(msgs, PREHASH_BYTES if prehashed else 0, "prehashes" if prehashed else "msgs")
-        n = first.numel() // first_w
-        total = msgs.numel()
-    else:
-        first = _as_np(first, first_w, first_name); pubs = _as_np(pubs, 32, "pubs")
-        msgs = _as_np(msgs, PREHASH_BYTES if prehashed else 0, "prehashes" if prehashed else "msgs")
-        n = first.size // first_w
-        total = msgs.size
-    if (pubs.numel() if on_device else pubs.size) // 32 != n:
-        raise ValueError(f"{name}: {first_name} and pubs disagree on the batch size")
-    if prehashed and total != PREHASH_BYTES * n:
-        raise ValueError(f"{name}: prehashes holds {total // PREHASH_BYTES} items of {PREHASH_BYTES} bytes, expected {n}")
-    lib = library()
-    if on_device:
-        off, mlen = None, PREHASH_BYTES
-        if not prehashed:
-            _, off, mlen = _msg_args(msgs, msg_off, msg_len, n, True)
-            _torch_off_check(off, n)
-        out = torch.empty((n,) + out_shape, dtype=torch.uint8, device=first.device)
-        args = [_c_ptr(t.data_ptr()) for t in (out, first, pubs, msgs)]
-        if not prehashed:
-            args += [_c_ptr(off.data_ptr()) if off is not None else None, _c_size(mlen)]
-        _check(getattr(lib, name + "_dev")(*args, _c_size(n), *ctx_args, _stream()), name)
-        return out
-    off, mlen = None, PREHASH_BYTES
-    if not prehashed:
-        msgs, off, mlen = _host_msgs(msgs, msg_off, msg_len, n)
-    out = np.zeros((n,) + out_shape, dtype=np.uint8)
-    args = [_np_ptr(out), _np_ptr(first), _np_ptr(pubs), _np_ptr(msgs)]
-    if not prehashed:
-        args += [_np_ptr(off) if off is not None else None, _c_size(mlen)]
-    _check(getattr(lib, name)(*args, _c_size(n), *ctx_args), name)
-    return out
-
-
 def ed25519ctx_sign_batch(secs, pubs, msgs, context, msg_off=None, msg_len=None):
     """Ed25519ctx signatures (RFC 8032 5.1, dom2 flag 0) of the messages under `context` (bytes, 0..255) -> (n, 64) uint8;
     messages as in ed25519_sign_batch"""
-    return _run_dom("ed25519ctx_sign_batch", secs, 32, "secs", pubs, msgs, msg_off, msg_len, (64,), context, False)
+    return _run_items("ed25519ctx_sign_batch", [(secs, 32, "secs"), (pubs, 32, "pubs")], msgs, (64,), msg_off=msg_off, msg_len=msg_len,
+                      context=_context(context))
 
 
 def ed25519ctx_verify_batch(sigs, pubs, msgs, context, msg_off=None, msg_len=None):
     """Ed25519ctx verdicts -> (n,) uint8, 1 = accept; the off-curve mode and the verify policy apply as in ed25519_verify_batch"""
-    return _run_dom("ed25519ctx_verify_batch", sigs, 64, "sigs", pubs, msgs, msg_off, msg_len, (), context, False)
+    return _run_items("ed25519ctx_verify_batch", [(sigs, 64, "sigs"), (pubs, 32, "pubs")], msgs, (), msg_off=msg_off, msg_len=msg_len,
+                      context=_context(context))
 
 
 def ed25519ph_sign_batch(secs, pubs, prehashes, context=b""):
     """Ed25519ph signatures (dom2 flag 1) over caller-supplied prehashes[i] = SHA-512(M_i), 64 bytes per item as
     hashlib.sha512(M).digest() returns them: the library never sees M -> (n, 64) uint8"""
-    return _run_dom("ed25519ph_sign_batch", secs, 32, "secs", pubs, prehashes, None, None, (64,), context, True)
+    return _run_items("ed25519ph_sign_batch", [(secs, 32, "secs"), (pubs, 32, "pubs")], prehashes, (64,), fixed=PREHASH_BYTES,
+                      data_name="prehashes", context=_context(context))
 
 
 def ed25519ph_verify_batch(sigs, pubs, prehashes, context=b""):
     """Ed25519ph verdicts over caller-supplied prehashes (see ed25519ph_sign_batch) -> (n,) uint8, 1 = accept"""
-    return _run_dom("ed25519ph_verify_batch", sigs, 64, "sigs", pubs, prehashes, None, None, (), context, True)
+    return _run_items("ed25519ph_verify_batch", [(sigs, 64, "sigs"), (pubs, 32, "pubs")], prehashes, (), fixed=PREHASH_BYTES,
+                      data_name="prehashes", context=_context(context))
 
 
 # ---------------------------------------------------------------------------------------------
 # key sets: the digest, Ed25519ctx and Ed25519ph forms (include/eddsa_amd.h)
 # ---------------------------------------------------------------------------------------------
 
-def _run_keyed_forms(name, sigs, keyset, key_idx, data, fixed=None, data_name="msgs", msg_off=None, msg_len=None, context=None,
-                     stats=None):
-    """common driver of the keyed forms that are not plain Ed25519 over messages: sigs, key indices and `data` - digests or
-    prehashes (`fixed` = 64 bytes per item, no offsets) or messages (fixed None) - under `context` (None: the C function takes
-    none) -> (n,) uint8.  numpy / bytes: the host form `name`; CUDA tensors: `name`_dev on torch's stream.  stats: as in
-    _run_msgs.  The checks are those of ed25519_verify_keyed and of _run_digests / _run_dom."""
-    ctx_args = []
-    if context is not None:
-        context = _context(context)
-        ctx_args = [ctypes.c_char_p(context), _c_size(len(context))]
-    handle = keyset._handle()
-    on_device = _is_torch(sigs)
-    if on_device:
-        import torch
-        sigs = _torch_check(sigs, 64, "sigs"); data = _torch_check(data, fixed or 0, data_name)
-        n, total = sigs.numel() // 64, data.numel()
-        if not _is_torch(key_idx) or key_idx.dtype != torch.int32 or not key_idx.is_cuda or not key_idx.is_contiguous() or key_idx.numel() != n:
-            raise ValueError(f"{name}: key_idx: expected n contiguous int32 indices on the device")
-    else:
-        sigs = _as_np(sigs, 64, "sigs"); data = _as_np(data, fixed or 0, data_name)
-        n, total = sigs.size // 64, data.size
-        key_idx = np.ascontiguousarray(np.asarray(key_idx))
-        if key_idx.dtype != np.uint32 or key_idx.size != n:
-            raise ValueError(f"{name}: key_idx: expected n uint32 indices")
-    if fixed and total != fixed * n:
-        raise ValueError(f"{name}: sigs and {data_name} disagree on the batch size ({n}, {total // fixed} items)")
-    lib = library()
-    msg_args = []
-    if on_device:
-        if not fixed:
-            _, off, mlen = _msg_args(data, msg_off, msg_len, n, True)
-            _torch_off_check(off, n)
-            msg_args = [_c_ptr(off.data_ptr()) if off is not None else None, _c_size(mlen)]
-        out = torch.empty((n,), dtype=torch.uint8, device=sigs.device)
-        counts = torch.zeros((4,), dtype=torch.int32, device=sigs.device) if stats else None
-        head = [_c_ptr(out.data_ptr())] + ([_c_ptr(counts.data_ptr()) if stats else None] if stats is not None else [])
-        _check(getattr(lib, name + "_dev")(*head, handle, _c_ptr(key_idx.data_ptr()), _c_ptr(sigs.data_ptr()), _c_ptr(data.data_ptr()),
-                                           *msg_args, _c_size(n), *ctx_args, _stream()), name + "_dev")
-        return (out, tuple(int(x) for x in counts.cpu())) if stats else out
-    if not fixed:
-        data, off, mlen = _host_msgs(data, msg_off, msg_len, n)
-        msg_args = [_np_ptr(off) if off is not None else None, _c_size(mlen)]
-    out = np.zeros((n,), dtype=np.uint8)
-    counts = (ctypes.c_uint32 * 4)()
-    head = [_np_ptr(out)] + ([counts] if stats is not None else [])
-    _check(getattr(lib, name)(*head, handle, _np_ptr(key_idx), _np_ptr(sigs), _np_ptr(data), *msg_args, _c_size(n), *ctx_args), name)
-    return (out, tuple(int(x) for x in counts)) if stats else out
-
-
 def ed25519_verify_keyed_digests(sigs, keyset, key_idx, digests):
     """ed25519_verify_digests with item i's key taken from a key set: the caller vouches that digests[i] =
     SHA-512(R_i || keys[key_idx[i]] || M_i) (64 bytes per item) -> (n,) uint8, 1 = accept; an index outside the key set rejects
     its item.  A comb key set takes the comb route.  Inputs as ed25519_verify_keyed (numpy: host form, CUDA tensors: device form)."""
-    return _run_keyed_forms("ed25519_verify_keyed_digests", sigs, keyset, key_idx, digests, fixed=64, data_name="digests")
+    return _run_items("ed25519_verify_keyed_digests", [(sigs, 64, "sigs")], digests, (), keyed=(keyset, key_idx), fixed=64, data_name="digests")
 
 
 def ed25519_verify_keyed_digests_rlc(sigs, keyset, key_idx, digests, return_stats=False):
     """ed25519_verify_keyed_rlc from caller-supplied digests (see ed25519_verify_keyed_digests): the verdicts and statistics of
     ed25519_verify_digests_rlc over keys[key_idx]; key sets of more than 8192 keys run as ed25519_verify_keyed_digests."""
-    return _run_keyed_forms("ed25519_verify_keyed_digests_rlc", sigs, keyset, key_idx, digests, fixed=64, data_name="digests",
-                            stats=bool(return_stats))
+    return _run_items("ed25519_verify_keyed_digests_rlc", [(sigs, 64, "sigs")], digests, (), keyed=(keyset, key_idx), fixed=64,
+                      data_name="digests", stats=bool(return_stats))
 
 
 def ed25519ctx_verify_keyed(sigs, keyset, key_idx, msgs, context, msg_off=None, msg_len=None):
     """ed25519ctx_verify_batch with item i's key taken from a key set -> (n,) uint8, 1 = accept; `context`: host bytes, 0..255;
     messages as in ed25519_verify_keyed"""
-    return _run_keyed_forms("ed25519ctx_verify_keyed", sigs, keyset, key_idx, msgs, msg_off=msg_off, msg_len=msg_len,
-                            context=context if context is not None else b"")
+    return _run_items("ed25519ctx_verify_keyed", [(sigs, 64, "sigs")], msgs, (), keyed=(keyset, key_idx), msg_off=msg_off, msg_len=msg_len,
+                      context=_context(context))
 
 
 def ed25519ph_verify_keyed(sigs, keyset, key_idx, prehashes, context=b""):
     """ed25519ph_verify_batch with item i's key taken from a key set: prehashes[i] = SHA-512(M_i), 64 bytes per item
     -> (n,) uint8, 1 = accept"""
-    return _run_keyed_forms("ed25519ph_verify_keyed", sigs, keyset, key_idx, prehashes, fixed=PREHASH_BYTES, data_name="prehashes",
-                            context=context if context is not None else b"")
+    return _run_items("ed25519ph_verify_keyed", [(sigs, 64, "sigs")], prehashes, (), keyed=(keyset, key_idx), fixed=PREHASH_BYTES,
+                      data_name="prehashes", context=_context(context))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1003,65 +855,23 @@ def signer_create(secs=None, expanded=None):
     return Signer(h)
 
 
-def _run_sign_keyed(name, signer, key_idx, data, fixed=None, data_name="msgs", msg_off=None, msg_len=None, context=None):
-    """common driver of the three keyed sign calls: key indices and `data` - messages (fixed None) or prehashes (`fixed` = 64 bytes
-    per item, no offsets) - under `context` (None: the C function takes none) -> (n, 64) uint8.  numpy / bytes (key_idx: uint32):
-    the host form `name`; CUDA tensors (key_idx: int32, read as unsigned): `name`_dev on torch's stream."""
-    ctx_args = []
-    if context is not None:
-        context = _context(context)
-        ctx_args = [ctypes.c_char_p(context), _c_size(len(context))]
-    handle = signer._handle()
-    lib = library()
-    msg_args = []
-    if _is_torch(key_idx):
-        import torch
-        if key_idx.dtype != torch.int32 or not key_idx.is_cuda or not key_idx.is_contiguous():
-            raise ValueError(f"{name}: key_idx: expected contiguous int32 indices on the device")
-        n = key_idx.numel()
-        data = _torch_check(data, fixed or 0, data_name)
-        if fixed and data.numel() != fixed * n:
-            raise ValueError(f"{name}: key_idx and {data_name} disagree on the batch size ({n}, {data.numel() // fixed} items)")
-        if not fixed:
-            _, off, mlen = _msg_args(data, msg_off, msg_len, n, True)
-            _torch_off_check(off, n)
-            msg_args = [_c_ptr(off.data_ptr()) if off is not None else None, _c_size(mlen)]
-        out = torch.empty((n, 64), dtype=torch.uint8, device=key_idx.device)
-        _check(getattr(lib, name + "_dev")(_c_ptr(out.data_ptr()), handle, _c_ptr(key_idx.data_ptr()), _c_ptr(data.data_ptr()), *msg_args,
-                                           _c_size(n), *ctx_args, _stream()), name + "_dev")
-        return out
-    key_idx = np.ascontiguousarray(np.asarray(key_idx))
-    if key_idx.dtype != np.uint32:
-        raise ValueError(f"{name}: key_idx: expected uint32 indices")
-    n = key_idx.size
-    data = _as_np(data, fixed or 0, data_name)
-    if fixed and data.size != fixed * n:
-        raise ValueError(f"{name}: key_idx and {data_name} disagree on the batch size ({n}, {data.size // fixed} items)")
-    if not fixed:
-        data, off, mlen = _host_msgs(data, msg_off, msg_len, n)
-        msg_args = [_np_ptr(off) if off is not None else None, _c_size(mlen)]
-    out = np.zeros((n, 64), dtype=np.uint8)
-    _check(getattr(lib, name)(_np_ptr(out), handle, _np_ptr(key_idx), _np_ptr(data), *msg_args, _c_size(n), *ctx_args), name)
-    return out
-
-
 def ed25519_sign_keyed(signer, key_idx, msgs, msg_off=None, msg_len=None):
     """ed25519_sign_batch with item i's key taken from a signer set: the signatures of (key key_idx[i], message i) -> (n, 64) uint8.
     numpy inputs take the host form (an index outside the set: EddsaAmdError, nothing is signed), CUDA tensors the device form
     (such an item gets 64 zero bytes).  msgs / msg_off / msg_len: as in ed25519_sign_batch."""
-    return _run_sign_keyed("ed25519_sign_keyed", signer, key_idx, msgs, msg_off=msg_off, msg_len=msg_len)
+    return _run_items("ed25519_sign_keyed", [], msgs, (64,), keyed=(signer, key_idx), msg_off=msg_off, msg_len=msg_len)
 
 
 def ed25519ctx_sign_keyed(signer, key_idx, msgs, context, msg_off=None, msg_len=None):
     """ed25519ctx_sign_batch with item i's key taken from a signer set -> (n, 64) uint8; `context`: host bytes, 0..255"""
-    return _run_sign_keyed("ed25519ctx_sign_keyed", signer, key_idx, msgs, msg_off=msg_off, msg_len=msg_len,
-                           context=context if context is not None else b"")
+    return _run_items("ed25519ctx_sign_keyed", [], msgs, (64,), keyed=(signer, key_idx), msg_off=msg_off, msg_len=msg_len,
+                      context=_context(context))
 
 
 def ed25519ph_sign_keyed(signer, key_idx, prehashes, context=b""):
     """ed25519ph_sign_batch with item i's key taken from a signer set: prehashes[i] = SHA-512(M_i), 64 bytes per item -> (n, 64) uint8"""
-    return _run_sign_keyed("ed25519ph_sign_keyed", signer, key_idx, prehashes, fixed=PREHASH_BYTES, data_name="prehashes",
-                           context=context if context is not None else b"")
+    return _run_items("ed25519ph_sign_keyed", [], prehashes, (64,), keyed=(signer, key_idx), fixed=PREHASH_BYTES, data_name="prehashes",
+                      context=_context(context))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1070,18 +880,19 @@ def ed25519ph_sign_keyed(signer, key_idx, prehashes, context=b""):
 
 def ed25519_verify_batch_multi(sigs, pubs, msgs, msg_off=None, msg_len=None):
     """ed25519_verify_batch over the device set: contiguous shards, one host thread per device"""
-    return _run_msgs("ed25519_verify_batch_multi", None, "ed25519_verify_batch_multi",
-                     sigs, 64, "sigs", pubs, msgs, msg_off, msg_len, ())
+    return _run_items("ed25519_verify_batch_multi", [(sigs, 64, "sigs"), (pubs, 32, "pubs")], msgs, (), msg_off=msg_off, msg_len=msg_len,
+                      dev=False, sizes_first=True)
 
 
 def ed25519_verify_digests_multi(sigs, pubs, digests):
     """ed25519_verify_digests over the device set (host arrays): contiguous shards, one host thread per device"""
-    return _run_digests("ed25519_verify_digests_multi", None, "ed25519_verify_digests_multi", sigs, pubs, digests)
+    return _run_items("ed25519_verify_digests_multi", [(sigs, 64, "sigs"), (pubs, 32, "pubs")], digests, (), fixed=64, data_name="digests",
+                      dev=False)
 
 
 def ed25519_sign_batch_multi(secs, pubs, msgs, msg_off=None, msg_len=None):
-    return _run_msgs("ed25519_sign_batch_multi", None, "ed25519_sign_batch_multi",
-                     secs, 32, "secs", pubs, msgs, msg_off, msg_len, (64,))
+    return _run_items("ed25519_sign_batch_multi", [(secs, 32, "secs"), (pubs, 32, "pubs")], msgs, (64,), msg_off=msg_off, msg_len=msg_len,
+                      dev=False, sizes_first=True)
 
 
 def x25519_batch_multi(scalars, points):

@@ -550,7 +550,13 @@ out:
     return pass_close(&p, rc);
 }
 
-struct sign_ctx { uint8_t *sigs; const uint8_t *secs, *pubs, *msgs; const uint64_t *msg_off, *msg_end; size_t msg_len; const edk_dom *dom; };
+/* set NULL: `first` holds the secret keys and pubs the public ones; else `first` holds the key indices into the signer set */
+struct sign_ctx { uint8_t *sigs; const edk_signer_set *set; const uint8_t *first, *pubs, *msgs; const uint64_t *msg_off, *msg_end; size_t msg_len;
+                  const edk_dom *dom; };
+
+/* edk_sign_keyed is a WEAK reference (edk_signer.h): without the HIP translation unit no signer set can exist, so no pass gets here */
+extern __typeof__(edk_signer_build) edk_signer_build __attribute__((weak));
+extern __typeof__(edk_sign_keyed) edk_sign_keyed __attribute__((weak));
 
 static hipError_t sign_step(struct engine *e, size_t done, size_t m, const void *vctx, const edk_fixed_ws *fws, hipStream_t st)
 {
@@ -559,26 +565,12 @@ static hipError_t sign_step(struct engine *e, size_t done, size_t m, const void 
     const uint64_t *op = c->msg_off ? c->msg_off + done : NULL;
     edk_fixed_ws with_dom = *fws;                  /* Ed25519ctx / Ed25519ph: the prefix travels in the launcher's copy of the workspace */
     with_dom.dom = c->dom;
-    return edk_sign(c->sigs + 64 * done, c->secs + 32 * done, c->pubs + 32 * done, mp, op, c->msg_end, c->msg_len, m,
-                    e->comb_img, &with_dom, st);
-}
-
-struct sign_keyed_ctx { uint8_t *sigs; const edk_signer_set *set; const uint32_t *key_idx; const uint8_t *msgs; const uint64_t *msg_off, *msg_end;
-                        size_t msg_len; const edk_dom *dom; };
-
-/* edk_sign_keyed is a WEAK reference (edk_signer.h): without the HIP translation unit no signer set can exist, so no pass gets here */
-extern __typeof__(edk_signer_build) edk_signer_build __attribute__((weak));
-extern __typeof__(edk_sign_keyed) edk_sign_keyed __attribute__((weak));
-
-static hipError_t sign_keyed_step(struct engine *e, size_t done, size_t m, const void *vctx, const edk_fixed_ws *fws, hipStream_t st)
-{
-    const struct sign_keyed_ctx *c = (const struct sign_keyed_ctx *)vctx;
-    const uint8_t *mp = c->msg_off ? c->msgs : c->msgs + done * c->msg_len;
-    const uint64_t *op = c->msg_off ? c->msg_off + done : NULL;
-    edk_fixed_ws with_dom = *fws;                  /* as in sign_step */
-    with_dom.dom = c->dom;
+    if (!c->set)
+        return edk_sign(c->sigs + 64 * done, c->first + 32 * done, c->pubs + 32 * done, mp, op, c->msg_end, c->msg_len, m,
+                        e->comb_img, &with_dom, st);
     if (!edk_sign_keyed) return hipErrorNotSupported;
-    return edk_sign_keyed(c->sigs + 64 * done, c->set, c->key_idx + done, mp, op, c->msg_end, c->msg_len, m, e->comb_img, &with_dom, st);
+    return edk_sign_keyed(c->sigs + 64 * done, c->set, (const uint32_t *)c->first + done, mp, op, c->msg_end, c->msg_len, m,
+                          e->comb_img, &with_dom, st);
 }
 
 struct io_ctx { uint8_t *out; const uint8_t *in; };
@@ -603,25 +595,13 @@ static hipError_t xbase_step(struct engine *e, size_t done, size_t m, const void
     return edk_x25519_base(c->out + 32 * done, c->in + 32 * done, m, e->comb_img, fws, st);
 }
 
-/* dom: NULL (Ed25519), or the dom2 prefix both hashes run under (Ed25519ctx, Ed25519ph) */
-int sign_dom_on(struct engine *e, uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
-                const uint64_t *msg_off, size_t msg_len, size_t n, const edk_dom *dom, hipStream_t st)
+/* every sign form (engine.h) */
+int sign_on(struct engine *e, uint8_t *sigs, const eddsa_amd_signer *sg, const uint8_t *first, const uint8_t *pubs, const uint8_t *msgs,
+            const uint64_t *msg_off, size_t msg_len, size_t n, const edk_dom *dom, hipStream_t st)
 {
-    struct sign_ctx c = { sigs, secs, pubs, msgs, msg_off, msg_off ? msg_off + n : NULL, msg_len, dom };   /* spans are clamped into [0, msg_off[n]) */
+    struct sign_ctx c = { .sigs = sigs, .set = sg ? &sg->set : NULL, .first = first, .pubs = pubs, .msgs = msgs, .msg_off = msg_off,
+                          .msg_end = msg_off ? msg_off + n : NULL, .msg_len = msg_len, .dom = dom };   /* spans are clamped into [0, msg_off[n]) */
     return fixed_on(e, n, sign_step, &c, st);
-}
-
-int sign_on(struct engine *e, uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
-                   const uint64_t *msg_off, size_t msg_len, size_t n, hipStream_t st)
-{
-    return sign_dom_on(e, sigs, secs, pubs, msgs, msg_off, msg_len, n, NULL, st);
-}
-
-int sign_keyed_on(struct engine *e, uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs,
-                  const uint64_t *msg_off, size_t msg_len, size_t n, const edk_dom *dom, hipStream_t st)
-{
-    struct sign_keyed_ctx c = { sigs, &s->set, key_idx, msgs, msg_off, msg_off ? msg_off + n : NULL, msg_len, dom };
-    return fixed_on(e, n, sign_keyed_step, &c, st);
 }
 
 /* dom2(flag, context) of RFC 8032 section 2 as the kernels take it (eddsa_kernels.h: edk_dom); a context of more than 255 bytes,
@@ -732,16 +712,6 @@ static int enter_dev(struct call *c, const void *out)
 /* return leave_with(&c, work(c.e, ..)): the work's answer, after leave() */
 static int leave_with(struct call *c, int rc) { leave(c); return rc; }
 
-int ed25519_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs,
-                             const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
-{
-    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL, 0 };
-    struct call c;
-    int rc = 0;
-    if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
-    return leave_with(&c, verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
-}
-
 /* fixed-size records: see include/eddsa_amd.h */
 int records_ok(size_t stride, size_t sig_off, size_t pub_off, size_t msg_off, size_t msg_len)
 {
@@ -749,47 +719,105 @@ int records_ok(size_t stride, size_t sig_off, size_t pub_off, size_t msg_off, si
            msg_off <= stride && msg_len <= stride - msg_off;
 }
 
+/* the checks that every verify and sign form makes before any device is asked (engine.h) */
+int msg_call_open(const struct msg_call *c, edk_dom *dom_buf, const edk_dom **dom)
+{
+    *dom = NULL;
+    if (c->ctx) {                          /* (the prefix is built first: a context of more than 255 bytes ends the call before anything else is looked at) */
+        const int rc = dom2_fill(dom_buf, c->ctx - 1, c->context, c->context_len);
+        if (rc) return rc;
+        *dom = dom_buf;
+    }
+    if (c->records && !records_ok(c->stride, c->rec_sig, c->rec_pub, c->rec_msg, c->msg_len)) return -(int)hipErrorInvalidValue;
+    if (c->keyed && !c->ks && !c->sg) return -(int)hipErrorInvalidValue;
+    if (c->n == 0) return 1;
+    if (c->keyed && (!c->out || !c->first || (c->ks && !c->second) || (!c->msgs && c->msg_len && !c->msg_off)))
+        return -(int)hipErrorInvalidValue;   /* (fixed-length items need their buffer) */
+    return 0;
+}
+
+/* The one body of the device-pointer verify and sign forms: the shared checks, then the device of the output buffer - which for a
+ * keyed form must be the one its key set's tables / its signer set's secrets live on -, then the pass.  The prefix of ctx / ph is
+ * built here, on the host, and goes to the kernels by value. */
+static int msg_call_dev(const struct msg_call *c, int sign, void *stream)
+{
+    edk_dom dom_buf;
+    const edk_dom *dom;
+    struct call e;
+    int dev = -1, rc = msg_call_open(c, &dom_buf, &dom);
+    if (rc) return rc < 0 ? rc : 0;
+    if ((rc = device_of(c->out, &dev))) return rc;
+    if (c->keyed && dev != (c->ks ? c->ks->device : c->sg->device)) return -(int)hipErrorInvalidValue;
+    if ((rc = enter(&e, dev))) return rc;
+    if (sign) {
+        rc = sign_on(e.e, c->out, c->sg, c->first, c->second, c->msgs, c->msg_off, c->msg_len, c->n, dom, (hipStream_t)stream);
+    } else {
+        const struct verify_form f = { .ks = c->ks, .digest = c->digest, .dom = dom, .rlc = c->rlc };
+        const edk_verify_src src = c->records ? verify_src_records(c->first, c->stride, c->rec_sig, c->rec_pub, c->rec_msg, c->msg_len)
+                                              : verify_src(&f, c->first, c->second, c->msgs, c->msg_off, c->msg_len);
+        rc = f.rlc ? rlc_on(e.e, c->out, c->stats, &src, c->n, (hipStream_t)stream)
+                   : verify_on(e.e, c->out, &src, c->n, (hipStream_t)stream, NULL, 0);
+    }
+    leave(&e);
+    return rc;
+}
+
+/* the eleven verify forms: argument adapters */
+int ed25519_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs,
+                             const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
+{
+    const struct msg_call c = { .out = ok, .first = sigs, .second = pubs, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len, .n = n };
+    return msg_call_dev(&c, 0, stream);
+}
+
 int ed25519_verify_records_dev(uint8_t *ok, const uint8_t *records, size_t stride, size_t sig_off, size_t pub_off,
                                size_t msg_off, size_t msg_len, size_t n, void *stream)
 {
-    if (!records_ok(stride, sig_off, pub_off, msg_off, msg_len)) return -(int)hipErrorInvalidValue;
-    const edk_verify_src src = { records + sig_off, records + pub_off, records + msg_off, NULL, msg_len,
-                                 stride, stride, stride, NULL, 0, 0, NULL, 0 };
-    struct call c;
-    int rc = 0;
-    if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
-    return leave_with(&c, verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
+    const struct msg_call c = { .out = ok, .first = records, .msg_len = msg_len, .n = n,
+                                .records = 1, .stride = stride, .rec_sig = sig_off, .rec_pub = pub_off, .rec_msg = msg_off };
+    return msg_call_dev(&c, 0, stream);
 }
 
 int ed25519_verify_batch_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *sigs, const uint8_t *pubs,
                                  const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL, 0 };
-    struct call c;
-    int rc = 0;
-    if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
-    return leave_with(&c, rlc_on(c.e, ok, stats, &src, n, (hipStream_t)stream));
+    const struct msg_call c = { .out = ok, .stats = stats, .first = sigs, .second = pubs, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len,
+                                .n = n, .rlc = 1 };
+    return msg_call_dev(&c, 0, stream);
 }
 
 /* caller-supplied digests (include/eddsa_amd.h): the two calls above with the 64 bytes of SHA-512(R || A || M) per item in the
  * message slot and the flag that selects the kernels that do not hash */
 int ed25519_verify_digests_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1, 0, NULL, 0 };
-    struct call c;
-    int rc = 0;
-    if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
-    return leave_with(&c, verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
+    const struct msg_call c = { .out = ok, .first = sigs, .second = pubs, .msgs = digests, .msg_len = EDDSA_DIGEST_BYTES, .n = n, .digest = 1 };
+    return msg_call_dev(&c, 0, stream);
 }
 
 int ed25519_verify_digests_rlc_dev(uint8_t *ok, uint32_t *stats, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests,
                                    size_t n, void *stream)
 {
-    const edk_verify_src src = { sigs, pubs, digests, NULL, 64, 64, 32, 64, NULL, 1, 0, NULL, 0 };
-    struct call c;
-    int rc = 0;
-    if (n == 0 || (rc = enter_dev(&c, ok))) return rc;
-    return leave_with(&c, rlc_on(c.e, ok, stats, &src, n, (hipStream_t)stream));
+    const struct msg_call c = { .out = ok, .stats = stats, .first = sigs, .second = pubs, .msgs = digests, .msg_len = EDDSA_DIGEST_BYTES, .n = n,
+                                .digest = 1, .rlc = 1 };
+    return msg_call_dev(&c, 0, stream);
+}
+
+/* Ed25519ctx and Ed25519ph (include/eddsa_amd.h): the message forms with dom2(F, context) in front of the hash; ph is ctx with
+ * F = 1 over the caller's 64-byte prehashes */
+int ed25519ctx_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
+                                size_t msg_len, size_t n, const uint8_t *context, size_t context_len, void *stream)
+{
+    const struct msg_call c = { .out = ok, .first = sigs, .second = pubs, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len, .n = n,
+                                .ctx = CTX_ED25519CTX, .context = context, .context_len = context_len };
+    return msg_call_dev(&c, 0, stream);
+}
+
+int ed25519ph_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *prehashes, size_t n,
+                               const uint8_t *context, size_t context_len, void *stream)
+{
+    const struct msg_call c = { .out = ok, .first = sigs, .second = pubs, .msgs = prehashes, .msg_len = EDDSA_PREHASH_BYTES, .n = n,
+                                .ctx = CTX_ED25519PH, .context = context, .context_len = context_len };
+    return msg_call_dev(&c, 0, stream);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -843,37 +871,35 @@ out:
     return rc;
 }
 
+/* the four entry points: *out is NULL after every failure; limit: the most keys a set of this kind may hold (a comb key set: 88 KiB
+ * of HBM per key); on_device: `keys` lies in HBM and the set is built on its device, else on the default one */
+static int keyset_create_checked(eddsa_amd_keyset **out, const uint8_t *keys, size_t count, size_t limit, int on_device, void *stream, int comb)
+{
+    int dev = -1, rc;
+    if (out) *out = NULL;
+    if (!out || !keys || count == 0 || count > limit) return -(int)hipErrorInvalidValue;
+    if (on_device && (rc = device_of(keys, &dev))) return rc;
+    return keyset_create_on(out, keys, count, dev, (hipStream_t)stream, comb);
+}
+
 int eddsa_amd_keyset_create(eddsa_amd_keyset **out, const uint8_t *keys, size_t count)
 {
-    if (out) *out = NULL;
-    if (!out || !keys || count == 0 || count > EDDSA_AMD_KEYSET_MAX_KEYS) return -(int)hipErrorInvalidValue;
-    return keyset_create_on(out, keys, count, -1, NULL, 0);
+    return keyset_create_checked(out, keys, count, EDDSA_AMD_KEYSET_MAX_KEYS, 0, NULL, 0);
 }
 
 int eddsa_amd_keyset_create_dev(eddsa_amd_keyset **out, const uint8_t *keys, size_t count, void *stream)
 {
-    int dev = -1, rc;
-    if (out) *out = NULL;
-    if (!out || !keys || count == 0 || count > EDDSA_AMD_KEYSET_MAX_KEYS) return -(int)hipErrorInvalidValue;
-    if ((rc = device_of(keys, &dev))) return rc;
-    return keyset_create_on(out, keys, count, dev, (hipStream_t)stream, 0);
+    return keyset_create_checked(out, keys, count, EDDSA_AMD_KEYSET_MAX_KEYS, 1, stream, 0);
 }
 
-/* comb key sets: the same checks with the comb's limit (88 KiB of HBM per key) */
 int eddsa_amd_keyset_create_comb(eddsa_amd_keyset **out, const uint8_t *keys, size_t count)
 {
-    if (out) *out = NULL;
-    if (!out || !keys || count == 0 || count > EDDSA_AMD_KEYSET_COMB_MAX_KEYS) return -(int)hipErrorInvalidValue;
-    return keyset_create_on(out, keys, count, -1, NULL, 1);
+    return keyset_create_checked(out, keys, count, EDDSA_AMD_KEYSET_COMB_MAX_KEYS, 0, NULL, 1);
 }
 
 int eddsa_amd_keyset_create_comb_dev(eddsa_amd_keyset **out, const uint8_t *keys, size_t count, void *stream)
 {
-    int dev = -1, rc;
-    if (out) *out = NULL;
-    if (!out || !keys || count == 0 || count > EDDSA_AMD_KEYSET_COMB_MAX_KEYS) return -(int)hipErrorInvalidValue;
-    if ((rc = device_of(keys, &dev))) return rc;
-    return keyset_create_on(out, keys, count, dev, (hipStream_t)stream, 1);
+    return keyset_create_checked(out, keys, count, EDDSA_AMD_KEYSET_COMB_MAX_KEYS, 1, stream, 1);
 }
 
 void eddsa_amd_keyset_destroy(eddsa_amd_keyset *ks)
@@ -892,140 +918,77 @@ int eddsa_amd_keyset_device(const eddsa_amd_keyset *ks) { return ks ? ks->device
 int eddsa_amd_keyset_is_comb(const eddsa_amd_keyset *ks) { return ks && ks->comb ? 1 : 0; }
 size_t eddsa_amd_keyset_bytes(const eddsa_amd_keyset *ks) { return ks ? ks->bytes : 0; }
 
+/* the six verify forms over a key set: the unkeyed form of the same name with the key indices where that has the keys */
 int ed25519_verify_keyed_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
                              const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
-    struct call c;
-    int rc = 0, dev = -1;
-    if (!ks) return -(int)hipErrorInvalidValue;
-    if (n == 0) return 0;
-    if ((rc = device_of(ok, &dev))) return rc;
-    if (dev != ks->device) return -(int)hipErrorInvalidValue;   /* the key set's tables live on its own device */
-    if ((rc = enter(&c, dev))) return rc;
-    const edk_verify_src src = { sigs, NULL, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL, 0,
-                                 ks->keys, ks->flags, ks->table, ks->count, key_idx, ks->comb };
-    return leave_with(&c, verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
+    const struct msg_call c = { .out = ok, .first = sigs, .second = (const uint8_t *)key_idx, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len,
+                                .n = n, .keyed = 1, .ks = ks };
+    return msg_call_dev(&c, 0, stream);
 }
 
-/* the batch verification over a key set: the checks of ed25519_verify_keyed_dev, the pass of ed25519_verify_batch_rlc_dev */
 int ed25519_verify_keyed_rlc_dev(uint8_t *ok, uint32_t *stats, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
                                  const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
-    struct call c;
-    int rc = 0, dev = -1;
-    if (!ks) return -(int)hipErrorInvalidValue;
-    if (n == 0) return 0;
-    if ((rc = device_of(ok, &dev))) return rc;
-    if (dev != ks->device) return -(int)hipErrorInvalidValue;
-    if ((rc = enter(&c, dev))) return rc;
-    const edk_verify_src src = { sigs, NULL, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL, 0,
-                                 ks->keys, ks->flags, ks->table, ks->count, key_idx, ks->comb };
-    return leave_with(&c, rlc_on(c.e, ok, stats, &src, n, (hipStream_t)stream));
-}
-
-/* The digest, Ed25519ctx and Ed25519ph forms over a key set (include/eddsa_amd.h): one body - the checks of
- * ed25519_verify_keyed_dev in its order with the NULL arguments refused before any device is asked, then the edk_verify_src of the
- * unkeyed form of the same name (digests: msg_len 64, no offset table, digest = 1; ctx / ph: the call's dom2 prefix) with the
- * ks_* fields set.  rlc != 0: the combination (the digest form only). */
-static int keyed_forms_dev(uint8_t *ok, uint32_t *stats, int rlc, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
-                           const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, int digest, const edk_dom *dom, void *stream)
-{
-    struct call c;
-    int rc = 0, dev = -1;
-    if (!ks) return -(int)hipErrorInvalidValue;
-    if (n == 0) return 0;
-    if (!ok || !key_idx || !sigs || (!msgs && msg_len && !msg_off)) return -(int)hipErrorInvalidValue;   /* (fixed-length items need their buffer) */
-    if ((rc = device_of(ok, &dev))) return rc;
-    if (dev != ks->device) return -(int)hipErrorInvalidValue;   /* the key set's tables live on its own device */
-    if ((rc = enter(&c, dev))) return rc;
-    const edk_verify_src src = { sigs, NULL, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, digest, 0, dom, 0,
-                                 ks->keys, ks->flags, ks->table, ks->count, key_idx, ks->comb };
-    return leave_with(&c, rlc ? rlc_on(c.e, ok, stats, &src, n, (hipStream_t)stream) : verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
+    const struct msg_call c = { .out = ok, .stats = stats, .first = sigs, .second = (const uint8_t *)key_idx, .msgs = msgs, .msg_off = msg_off,
+                                .msg_len = msg_len, .n = n, .keyed = 1, .ks = ks, .rlc = 1 };
+    return msg_call_dev(&c, 0, stream);
 }
 
 int ed25519_verify_keyed_digests_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
                                      const uint8_t *digests, size_t n, void *stream)
 {
-    return keyed_forms_dev(ok, NULL, 0, ks, key_idx, sigs, digests, NULL, 64, n, 1, NULL, stream);
+    const struct msg_call c = { .out = ok, .first = sigs, .second = (const uint8_t *)key_idx, .msgs = digests, .msg_len = EDDSA_DIGEST_BYTES,
+                                .n = n, .keyed = 1, .ks = ks, .digest = 1 };
+    return msg_call_dev(&c, 0, stream);
 }
 
 int ed25519_verify_keyed_digests_rlc_dev(uint8_t *ok, uint32_t *stats, const eddsa_amd_keyset *ks, const uint32_t *key_idx,
                                          const uint8_t *sigs, const uint8_t *digests, size_t n, void *stream)
 {
-    return keyed_forms_dev(ok, stats, 1, ks, key_idx, sigs, digests, NULL, 64, n, 1, NULL, stream);
+    const struct msg_call c = { .out = ok, .stats = stats, .first = sigs, .second = (const uint8_t *)key_idx, .msgs = digests,
+                                .msg_len = EDDSA_DIGEST_BYTES, .n = n, .keyed = 1, .ks = ks, .digest = 1, .rlc = 1 };
+    return msg_call_dev(&c, 0, stream);
 }
 
-/* (the prefix is built first: a context of more than 255 bytes ends the call before anything else is looked at) */
 int ed25519ctx_verify_keyed_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs, const uint8_t *msgs,
                                 const uint64_t *msg_off, size_t msg_len, size_t n, const uint8_t *context, size_t context_len, void *stream)
 {
-    edk_dom dom;
-    const int rc = dom2_fill(&dom, 0, context, context_len);
-    return rc ? rc : keyed_forms_dev(ok, NULL, 0, ks, key_idx, sigs, msgs, msg_off, msg_len, n, 0, &dom, stream);
+    const struct msg_call c = { .out = ok, .first = sigs, .second = (const uint8_t *)key_idx, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len,
+                                .n = n, .keyed = 1, .ks = ks, .ctx = CTX_ED25519CTX, .context = context, .context_len = context_len };
+    return msg_call_dev(&c, 0, stream);
 }
 
 int ed25519ph_verify_keyed_dev(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
                                const uint8_t *prehashes, size_t n, const uint8_t *context, size_t context_len, void *stream)
 {
-    edk_dom dom;
-    const int rc = dom2_fill(&dom, 1, context, context_len);
-    return rc ? rc : keyed_forms_dev(ok, NULL, 0, ks, key_idx, sigs, prehashes, NULL, EDDSA_PREHASH_BYTES, n, 0, &dom, stream);
+    const struct msg_call c = { .out = ok, .first = sigs, .second = (const uint8_t *)key_idx, .msgs = prehashes, .msg_len = EDDSA_PREHASH_BYTES,
+                                .n = n, .keyed = 1, .ks = ks, .ctx = CTX_ED25519PH, .context = context, .context_len = context_len };
+    return msg_call_dev(&c, 0, stream);
 }
 
+/* the three sign forms over caller-supplied keys; those over a signer set stand behind the signer sets */
 int ed25519_sign_batch_dev(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
                            const uint64_t *msg_off, size_t msg_len, size_t n, void *stream)
 {
-    struct call c;
-    int rc = 0;
-    if (n == 0 || (rc = enter_dev(&c, sigs))) return rc;
-    return leave_with(&c, sign_on(c.e, sigs, secs, pubs, msgs, msg_off, msg_len, n, (hipStream_t)stream));
-}
-
-/* Ed25519ctx and Ed25519ph (include/eddsa_amd.h): the message forms with dom2(F, context) in front of both hashes; ph is ctx with
- * F = 1 over the caller's 64-byte prehashes.  The prefix is built here, on the host, and goes to the kernels by value. */
-static int dom_verify_dev(int flag, uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
-                          size_t msg_len, size_t n, const uint8_t *context, size_t context_len, void *stream)
-{
-    edk_dom dom;
-    struct call c;
-    int rc = dom2_fill(&dom, flag, context, context_len);
-    if (rc || n == 0 || (rc = enter_dev(&c, ok))) return rc;
-    const edk_verify_src src = { sigs, pubs, msgs, msg_off, msg_len, 64, 32, msg_len, NULL, 0, 0, &dom, 0 };
-    return leave_with(&c, verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
-}
-
-static int dom_sign_dev(int flag, uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
-                        size_t msg_len, size_t n, const uint8_t *context, size_t context_len, void *stream)
-{
-    edk_dom dom;
-    struct call c;
-    int rc = dom2_fill(&dom, flag, context, context_len);
-    if (rc || n == 0 || (rc = enter_dev(&c, sigs))) return rc;
-    return leave_with(&c, sign_dom_on(c.e, sigs, secs, pubs, msgs, msg_off, msg_len, n, &dom, (hipStream_t)stream));
-}
-
-int ed25519ctx_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
-                                size_t msg_len, size_t n, const uint8_t *context, size_t context_len, void *stream)
-{
-    return dom_verify_dev(0, ok, sigs, pubs, msgs, msg_off, msg_len, n, context, context_len, stream);
-}
-
-int ed25519ph_verify_batch_dev(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *prehashes, size_t n,
-                               const uint8_t *context, size_t context_len, void *stream)
-{
-    return dom_verify_dev(1, ok, sigs, pubs, prehashes, NULL, EDDSA_PREHASH_BYTES, n, context, context_len, stream);
+    const struct msg_call c = { .out = sigs, .first = secs, .second = pubs, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len, .n = n };
+    return msg_call_dev(&c, 1, stream);
 }
 
 int ed25519ctx_sign_batch_dev(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
                               size_t msg_len, size_t n, const uint8_t *context, size_t context_len, void *stream)
 {
-    return dom_sign_dev(0, sigs, secs, pubs, msgs, msg_off, msg_len, n, context, context_len, stream);
+    const struct msg_call c = { .out = sigs, .first = secs, .second = pubs, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len, .n = n,
+                                .ctx = CTX_ED25519CTX, .context = context, .context_len = context_len };
+    return msg_call_dev(&c, 1, stream);
 }
 
 int ed25519ph_sign_batch_dev(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *prehashes, size_t n,
                              const uint8_t *context, size_t context_len, void *stream)
 {
-    return dom_sign_dev(1, sigs, secs, pubs, prehashes, NULL, EDDSA_PREHASH_BYTES, n, context, context_len, stream);
+    const struct msg_call c = { .out = sigs, .first = secs, .second = pubs, .msgs = prehashes, .msg_len = EDDSA_PREHASH_BYTES, .n = n,
+                                .ctx = CTX_ED25519PH, .context = context, .context_len = context_len };
+    return msg_call_dev(&c, 1, stream);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -1110,42 +1073,29 @@ out:
     return rc;
 }
 
-/* the three device-pointer forms: the NULL arguments are refused before any device is asked, the signer even for an empty batch */
-static int sign_keyed_dev(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
-                          size_t msg_len, size_t n, const edk_dom *dom, void *stream)
-{
-    struct call c;
-    int rc = 0, dev = -1;
-    if (!s) return -(int)hipErrorInvalidValue;
-    if (n == 0) return 0;
-    if (!sigs || !key_idx || (!msgs && msg_len && !msg_off)) return -(int)hipErrorInvalidValue;   /* (fixed-length items need their buffer) */
-    if ((rc = device_of(sigs, &dev))) return rc;
-    if (dev != s->device) return -(int)hipErrorInvalidValue;   /* the set's secrets live on its own device */
-    if ((rc = enter(&c, dev))) return rc;
-    return leave_with(&c, sign_keyed_on(c.e, sigs, s, key_idx, msgs, msg_off, msg_len, n, dom, (hipStream_t)stream));
-}
-
+/* the three device-pointer sign forms over a signer set */
 int ed25519_sign_keyed_dev(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
                            size_t msg_len, size_t n, void *stream)
 {
-    return sign_keyed_dev(sigs, s, key_idx, msgs, msg_off, msg_len, n, NULL, stream);
+    const struct msg_call c = { .out = sigs, .first = (const uint8_t *)key_idx, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len, .n = n,
+                                .keyed = 1, .sg = s };
+    return msg_call_dev(&c, 1, stream);
 }
 
-/* (the prefix is built first: a context of more than 255 bytes ends the call before anything else is looked at) */
 int ed25519ctx_sign_keyed_dev(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
                               size_t msg_len, size_t n, const uint8_t *context, size_t context_len, void *stream)
 {
-    edk_dom dom;
-    const int rc = dom2_fill(&dom, 0, context, context_len);
-    return rc ? rc : sign_keyed_dev(sigs, s, key_idx, msgs, msg_off, msg_len, n, &dom, stream);
+    const struct msg_call c = { .out = sigs, .first = (const uint8_t *)key_idx, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len, .n = n,
+                                .keyed = 1, .sg = s, .ctx = CTX_ED25519CTX, .context = context, .context_len = context_len };
+    return msg_call_dev(&c, 1, stream);
 }
 
 int ed25519ph_sign_keyed_dev(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *prehashes, size_t n,
                              const uint8_t *context, size_t context_len, void *stream)
 {
-    edk_dom dom;
-    const int rc = dom2_fill(&dom, 1, context, context_len);
-    return rc ? rc : sign_keyed_dev(sigs, s, key_idx, prehashes, NULL, EDDSA_PREHASH_BYTES, n, &dom, stream);
+    const struct msg_call c = { .out = sigs, .first = (const uint8_t *)key_idx, .msgs = prehashes, .msg_len = EDDSA_PREHASH_BYTES, .n = n,
+                                .keyed = 1, .sg = s, .ctx = CTX_ED25519PH, .context = context, .context_len = context_len };
+    return msg_call_dev(&c, 1, stream);
 }
 
 int ed25519_genpub_batch_dev(uint8_t *pubs, const uint8_t *secs, size_t n, void *stream)
@@ -1290,7 +1240,8 @@ int ed25519_verify_batch_multi_dev(uint8_t *const ok_full[], const uint8_t *cons
         size_t lo, hi;
         eddsa_amd_shard_bounds(n_total, d, g, &lo, &hi);
         if (hi - lo != n_total / (size_t)g) even = 0;
-        const edk_verify_src src = { sigs[d], pubs[d], msgs[d], NULL, msg_len, 64, 32, msg_len, NULL, 0, 0, NULL, 0 };
+        const struct verify_form plain = { .ks = NULL };
+        const edk_verify_src src = verify_src(&plain, sigs[d], pubs[d], msgs[d], NULL, msg_len);
         TRY(hipSetDevice(g_multi.dev[d]));
         rc = verify_on(g_eng[g_multi.dev[d]], ok_full[d] + lo, &src, hi - lo, (hipStream_t)streams[d], NULL, 0);
     }

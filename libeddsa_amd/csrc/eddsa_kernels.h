@@ -66,7 +66,8 @@ typedef struct edk_verify_ws {
 
 /* where the items of a verify pass live: item i has its signature at sigs + i * sig_stride, its key
  * at pubs + i * pub_stride and its message at msgs + i * msg_stride (msg_len bytes) or, for ragged
- * messages, at msgs + msg_off[i].  Packed arrays: strides 64 / 32 / msg_len; records: one stride. */
+ * messages, at msgs + msg_off[i].  Packed arrays: strides 64 / 32 / msg_len; records: one stride.
+ * The host side writes the fields in one place, by name (engine.h: verify_src, verify_src_records): what a form does not set is 0 / NULL. */
 typedef struct {
   const uint8_t *sigs, *pubs, *msgs;
   const uint64_t* msg_off;
@@ -76,21 +77,21 @@ typedef struct {
   int digest;                /* != 0 (ed25519_verify_digests*): the message slot holds the caller's SHA-512(R || A || M), 64 bytes per
                                 item (msg_len 64, no offset table); the hashing kernels' digest forms take t from it unhashed */
   int policy;                /* the EDDSA_AMD_VERIFY_* bits in force (include/eddsa_amd.h), 0 = none: != 0 adds k_verify_policy behind the
-                                pass's verdicts (kernels.hip).  Filled in by src_at (eddsa_amd.c) for verify_on / rlc_on alike; initialisers
-                                that stop at `digest` leave it 0.  Host side only, like `digest` */
+                                pass's verdicts (kernels.hip).  Filled in by src_at (eddsa_amd.c) for verify_on / rlc_on alike.  Host side
+                                only, like `digest` */
   const edk_dom* dom;        /* != NULL (ed25519ctx_verify_batch*, ed25519ph_verify_batch*): t comes from SHA-512(dom2 || R || A || M') - one
                                 kernel hashes every item under the prefix into ws->domdig and the pass goes on as a digest pass over that
-                                area.  Host side only (the pointer is read while the pass is enqueued); initialisers that stop earlier
-                                leave it NULL; never set together with `digest` */
+                                area.  Host side only (the pointer is read while the pass is enqueued); never set together with
+                                `digest` */
   int equation;              /* EDDSA_AMD_EQUATION_* (include/eddsa_amd.h), 0 = the reference's cofactorless check: != 0 adds the
                                 k_cofactor_* kernels behind the pass's verdicts and S < l to its policy (kernels.hip: edk_verify), and
                                 sends a group with a non-canonical R to the per-item kernels (rlc.hip).  Filled in by src_at like
-                                `policy`, read beside it; initialisers that stop earlier leave it 0.  Host side only */
+                                `policy`, read beside it.  Host side only */
   /* ks_table != NULL (ed25519_verify_keyed*): a KEYED pass - `pubs` is not read; item i's key is entry key_idx[i] of a key set
      (include/eddsa_amd.h: eddsa_amd_keyset), whose HBM these point to: ks_keys 32 bytes, ks_flags one byte (on the curve),
      ks_table VERIFY_ITEM_TABLE_WORDS words per key, ks_count keys.  key_idx lies in HBM like the other arrays of the pass and
      is advanced with them by src_at.  Host side only: the keyed kernels take the pointers as arguments of their own
-     (keyed_kernels.h); initialisers that stop earlier leave them NULL.  With `digest` (ed25519_verify_keyed_digests*) or `dom`
+     (keyed_kernels.h).  With `digest` (ed25519_verify_keyed_digests*) or `dom`
      (ed25519ctx_verify_keyed*, ed25519ph_verify_keyed*) the keyed kernels run in their digest forms; the combination takes
      `digest` and refuses `dom` (rlc.hip: edk_verify_rlc) */
   const uint8_t *ks_keys, *ks_flags;
@@ -99,7 +100,7 @@ typedef struct {
   const uint32_t* key_idx;
   const uint32_t* ks_comb;   /* != NULL: the key set is a COMB key set (eddsa_amd_keyset_create_comb) - KEYSET_COMB_WORDS words per key,
                                 [key][row][m - 1] = m * 2^(2 COMB_W row) * (-A); the pass takes the comb route (kernels.hip: verify_route_of).
-                                NULL for plain sets; initialisers that stop earlier leave it NULL */
+                                NULL for plain sets */
 } edk_verify_src;
 
 /* What the kernels take BY VALUE: the nine fields of edk_verify_src that lanes read, 72 bytes as before the flag existed.  The flag stays

@@ -194,22 +194,76 @@ void wipe_free(void *p, size_t bytes);
  * its place (it is not run), as a sticky HIP error would surface. */
 int take_async_error(struct engine *e);
 
+/* What distinguishes one verify call from another: every verify form of include/eddsa_amd.h is one setting of these four facts.
+ * The buffers of a pass are the other half of an edk_verify_src; verify_src() puts the two together and is, with its sibling
+ * for the records layout, the one place that writes that struct's fields. */
+struct verify_form {
+    const eddsa_amd_keyset *ks;       /* keyed: the pass's second input holds key indices into this set instead of keys; else NULL */
+    int digest;                       /* the message slot holds the caller's SHA-512(R || A || M), 64 bytes per item, no offset table */
+    const edk_dom *dom;               /* Ed25519ctx / Ed25519ph: the call's dom2 prefix; else NULL (never with `digest`) */
+    int rlc;                          /* the combination (rlc_on) instead of the per-item kernels (verify_on) */
+};
+
+/* packed arrays (strides 64 / 32 / msg_len).  second: the pass's keys, 32 bytes per item - of a keyed form its key indices, 4 bytes */
+static inline edk_verify_src verify_src(const struct verify_form *f, const uint8_t *sigs, const uint8_t *second, const uint8_t *msgs,
+                                        const uint64_t *msg_off, size_t msg_len)
+{
+    edk_verify_src src = { .sigs = sigs, .pubs = second, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len,
+                           .sig_stride = 64, .pub_stride = 32, .msg_stride = msg_len, .digest = f->digest, .dom = f->dom };
+    if (f->ks) {
+        src.pubs = NULL;
+        src.ks_keys = f->ks->keys; src.ks_flags = f->ks->flags; src.ks_table = f->ks->table; src.ks_count = f->ks->count;
+        src.key_idx = (const uint32_t *)second;
+        src.ks_comb = f->ks->comb;
+    }
+    return src;
+}
+
+/* fixed-size records (include/eddsa_amd.h): one stride, three offsets; the plain form only */
+static inline edk_verify_src verify_src_records(const uint8_t *records, size_t stride, size_t sig_off, size_t pub_off, size_t msg_off,
+                                                size_t msg_len)
+{
+    const edk_verify_src src = { .sigs = records + sig_off, .pubs = records + pub_off, .msgs = records + msg_off, .msg_len = msg_len,
+                                 .sig_stride = stride, .pub_stride = stride, .msg_stride = stride };
+    return src;
+}
+
+/* A verify or sign call that carries messages, as its entry point received it.  The device-pointer entry points (eddsa_amd.c)
+ * and the host-pointer ones (host_pipe.c) are argument adapters: each fills one of these in and hands it to its layer's one
+ * body, and both bodies begin with msg_call_open, so every form refuses the same arguments in the same order. */
+#define EDDSA_PREHASH_BYTES 64        /* what an Ed25519ph item carries in the message slot */
+#define EDDSA_DIGEST_BYTES 64         /* ... and an item of the digest forms: SHA-512(R || A || M) */
+enum { CTX_NONE = 0, CTX_ED25519CTX = 1, CTX_ED25519PH = 2 };   /* msg_call.ctx: the dom2 flag + 1 */
+struct msg_call {
+    uint8_t *out;                     /* verify: ok; sign: sigs */
+    uint32_t *stats;                  /* rlc: the four counters (device forms: HBM; host forms: the caller's), or NULL */
+    const uint8_t *first, *second;    /* verify: sigs and pubs, keyed: sigs and key_idx; sign: secs and pubs, keyed: key_idx and NULL */
+    const uint8_t *msgs; const uint64_t *msg_off; size_t msg_len, n;
+    int keyed;                        /* the call takes a key set (verify) or a signer set (sign): ks / sg must not be NULL */
+    const eddsa_amd_keyset *ks;
+    const eddsa_amd_signer *sg;
+    int digest, rlc;                  /* verify: as in verify_form */
+    int ctx; const uint8_t *context; size_t context_len;   /* CTX_*; the context is host memory in every form */
+    int records; size_t stride, rec_sig, rec_pub, rec_msg; /* ed25519_verify_records: `first` holds the records, msg_len the messages' */
+};
+/* The checks every form shares, in the order the calls have always made them: the context (more than 255 bytes, or NULL with a
+ * length - even for an empty batch), the records layout, a NULL key set / signer set (even for an empty batch), n == 0, and for
+ * the keyed forms the NULL arrays - all before any device is asked.  < 0: refused; 1: an empty batch, done; 0: go on, *dom is
+ * the call's prefix (dom_buf filled) or NULL. */
+int msg_call_open(const struct msg_call *c, edk_dom *dom_buf, const edk_dom **dom);
+
 /* device-pointer work on one engine (the engine's device is current); all asynchronous on `st` except rlc_on,
  * which waits for the stream once per pass */
 /* bulk_done (or NULL): see edk_verify */
 int verify_on(struct engine *e, uint8_t *ok, const edk_verify_src *all, size_t n, hipStream_t st, hipEvent_t bulk_done, int bulk_early);
 int rlc_on(struct engine *e, uint8_t *ok, uint32_t *stats, const edk_verify_src *all, size_t n, hipStream_t st);
-int sign_on(struct engine *e, uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
-            const uint64_t *msg_off, size_t msg_len, size_t n, hipStream_t st);
-/* Ed25519ctx / Ed25519ph: sign_on under the dom2 prefix (NULL: sign_on itself); dom2_fill builds the prefix and is the one place
- * that refuses a context of more than 255 bytes.  EDDSA_PREHASH_BYTES: what an Ed25519ph item carries in the message slot */
-#define EDDSA_PREHASH_BYTES 64
-int sign_dom_on(struct engine *e, uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
-                const uint64_t *msg_off, size_t msg_len, size_t n, const edk_dom *dom, hipStream_t st);
+/* every sign form.  sg NULL: `first` holds the secret keys, 32 bytes per item, and pubs the public ones; else the secret scalar, the
+ * prefix and the public key of item i come from the signer set by its key index - `first` holds the n indices, 4 bytes each (HBM),
+ * and pubs is not read.  dom: NULL (Ed25519), or the dom2 prefix both hashes run under (Ed25519ctx, Ed25519ph) */
+int sign_on(struct engine *e, uint8_t *sigs, const eddsa_amd_signer *sg, const uint8_t *first, const uint8_t *pubs, const uint8_t *msgs,
+            const uint64_t *msg_off, size_t msg_len, size_t n, const edk_dom *dom, hipStream_t st);
+/* builds the prefix and is the one place that refuses a context of more than 255 bytes */
 int dom2_fill(edk_dom *d, int flag, const uint8_t *context, size_t context_len);
-/* sign_dom_on with the secret scalar, the prefix and the public key of item i taken from a signer set by key_idx[i] (HBM) */
-int sign_keyed_on(struct engine *e, uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs,
-                  const uint64_t *msg_off, size_t msg_len, size_t n, const edk_dom *dom, hipStream_t st);
 int genpub_on(struct engine *e, uint8_t *pubs, const uint8_t *secs, size_t n, hipStream_t st);
 int x25519_on(struct engine *e, uint8_t *out, const uint8_t *scalars, const uint8_t *points, size_t n, hipStream_t st);
 int xbase_on(struct engine *e, uint8_t *out, const uint8_t *scalars, size_t n, hipStream_t st);

@@ -254,7 +254,8 @@ struct hjob {
     size_t stride, rec_sig, rec_pub, rec_msg;  /* records: the width of in[0]'s items and the offsets inside them */
     uint32_t *stats;                           /* rlc: host copy of the pass statistics (4 words) or NULL */
     int src_pinned;                            /* every host array of the job is page-locked: no staging */
-    const edk_dom *dom;                        /* Ed25519ctx / Ed25519ph: the call's dom2 prefix (lives on the entry point's stack); else NULL */
+    const edk_dom *dom;                        /* Ed25519ctx / Ed25519ph: the call's dom2 prefix (lives on msg_call_run's frame); else NULL */
+    int digest;                                /* the digest forms: the message slot holds SHA-512(R || A || M), EDDSA_DIGEST_BYTES per item */
     const eddsa_amd_keyset *ks;                /* ed25519_verify_keyed: the caller's key set (in[1] then holds the key indices); else NULL */
     const eddsa_amd_signer *sg;                /* ed25519_sign_keyed: the caller's signer set (in[0] then holds the key indices); else NULL */
 };
@@ -917,90 +918,22 @@ static int pipe_run(const struct hjob j, size_t n)
 
 /* record the lane's "kernels queued" event (verify does it itself, before its stream waits for the exact path) */
 static int run_done(int rc, const struct chunk *c) { return !rc && hipEventRecord(c->kdone, c->st) != hipSuccess ? -(int)hipErrorUnknown : rc; }
+/* Every verify form: the job says which (engine.h: verify_form - its key set, the digest flag, the dom2 prefix; a job that carries
+ * statistics is the combination), the chunk brings the buffers.  Keyed: the chunk's second input is its slice of the key indices.
+ * Digests and prehashes travel in the message slot, 64 bytes per item, staged like any fixed-length message. */
 static int run_verify(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, NULL, 0 };
+    const struct verify_form f = { .ks = j->ks, .digest = j->digest, .dom = j->dom, .rlc = j->stats != NULL };
+    const edk_verify_src src = j->stride ? verify_src_records(c->d_in[0], j->stride, j->rec_sig, j->rec_pub, j->rec_msg, j->msg_len)
+                                         : verify_src(&f, c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len);
+    if (f.rlc) return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
     return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
 }
-static int run_verify_rlc(struct engine *e, const struct hjob *j, const struct chunk *c)
-{
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, NULL, 0 };
-    return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
-}
-/* caller-supplied digests: the 64 bytes of SHA-512(R || A || M) per item travel in the message slot (EDDSA_DIGEST_BYTES wide, staged
- * like any fixed-length message); the flag selects the kernels that do not hash (eddsa_kernels.h: edk_verify_src) */
-#define EDDSA_DIGEST_BYTES 64
-static int run_verify_digests(struct engine *e, const struct hjob *j, const struct chunk *c)
-{
-    (void)j;
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1, 0, NULL, 0 };
-    return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
-}
-static int run_verify_digests_rlc(struct engine *e, const struct hjob *j, const struct chunk *c)
-{
-    (void)j;
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1, 0, NULL, 0 };
-    return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
-}
-static int run_verify_records(struct engine *e, const struct hjob *j, const struct chunk *c)
-{
-    const edk_verify_src src = { c->d_in[0] + j->rec_sig, c->d_in[0] + j->rec_pub, c->d_in[0] + j->rec_msg, NULL, j->msg_len,
-                                 j->stride, j->stride, j->stride, NULL, 0, 0, NULL, 0 };
-    return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
-}
+/* Every sign form.  Over a signer set (j->sg) the chunk's one input is its slice of the key indices and the secrets come from the
+ * set (the lane's second input buffer is not read); j->dom NULL: Ed25519, else Ed25519ctx / Ed25519ph under the call's prefix */
 static int run_sign(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
-    return run_done(sign_on(e, c->d_out, c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, c->m, c->st), c);
-}
-/* Ed25519ctx / Ed25519ph: verify and sign under the call's dom2 prefix (ph: msg_len 64, never an offset table) */
-static int run_verify_dom(struct engine *e, const struct hjob *j, const struct chunk *c)
-{
-    const edk_verify_src src = { c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, j->dom, 0 };
-    return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
-}
-/* key-set verification: the chunk's second input is its slice of the key indices, the keys come from the job's key set */
-static int run_verify_keyed(struct engine *e, const struct hjob *j, const struct chunk *c)
-{
-    const edk_verify_src src = { c->d_in[0], NULL, c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, NULL, 0,
-                                 j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1], j->ks->comb };
-    return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
-}
-/* the batch verification over a key set: the inputs of run_verify_keyed, the pass and the statistics of run_verify_rlc */
-static int run_verify_keyed_rlc(struct engine *e, const struct hjob *j, const struct chunk *c)
-{
-    const edk_verify_src src = { c->d_in[0], NULL, c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, NULL, 0,
-                                 j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1], j->ks->comb };
-    return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
-}
-/* the digest forms over a key set: run_verify_digests / run_verify_digests_rlc with the second input of run_verify_keyed */
-static int run_verify_keyed_digests(struct engine *e, const struct hjob *j, const struct chunk *c)
-{
-    const edk_verify_src src = { c->d_in[0], NULL, c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1, 0, NULL, 0,
-                                 j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1], j->ks->comb };
-    return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
-}
-static int run_verify_keyed_digests_rlc(struct engine *e, const struct hjob *j, const struct chunk *c)
-{
-    const edk_verify_src src = { c->d_in[0], NULL, c->d_msgs, NULL, EDDSA_DIGEST_BYTES, 64, 32, EDDSA_DIGEST_BYTES, NULL, 1, 0, NULL, 0,
-                                 j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1], j->ks->comb };
-    return run_done(rlc_on(e, c->d_out, c->d_stats, &src, c->m, c->st), c);
-}
-/* Ed25519ctx / Ed25519ph over a key set: run_verify_keyed under the call's dom2 prefix (j->ks and j->dom are both set) */
-static int run_verify_keyed_dom(struct engine *e, const struct hjob *j, const struct chunk *c)
-{
-    const edk_verify_src src = { c->d_in[0], NULL, c->d_msgs, c->d_off, j->msg_len, 64, 32, j->msg_len, NULL, 0, 0, j->dom, 0,
-                                 j->ks->keys, j->ks->flags, j->ks->table, j->ks->count, (const uint32_t *)c->d_in[1], j->ks->comb };
-    return verify_on(e, c->d_out, &src, c->m, c->st, c->kdone, g_pipe_chain == 2);
-}
-static int run_sign_dom(struct engine *e, const struct hjob *j, const struct chunk *c)
-{
-    return run_done(sign_dom_on(e, c->d_out, c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, c->m, j->dom, c->st), c);
-}
-/* signing over a signer set: the chunk's one input is its slice of the key indices, the secrets come from the job's signer set;
- * j->dom NULL: Ed25519, else Ed25519ctx / Ed25519ph under the call's prefix */
-static int run_sign_keyed(struct engine *e, const struct hjob *j, const struct chunk *c)
-{
-    return run_done(sign_keyed_on(e, c->d_out, j->sg, (const uint32_t *)c->d_in[0], c->d_msgs, c->d_off, j->msg_len, c->m, j->dom, c->st), c);
+    return run_done(sign_on(e, c->d_out, j->sg, c->d_in[0], c->d_in[1], c->d_msgs, c->d_off, j->msg_len, c->m, j->dom, c->st), c);
 }
 static int run_x25519(struct engine *e, const struct hjob *j, const struct chunk *c)
 {
@@ -1015,56 +948,46 @@ RUN_1IN(run_xbase, xbase_on)
 RUN_1IN(run_pk_to_x, pk_to_x_on)
 RUN_1IN(run_sk_to_x, sk_to_x_on)
 
-/* The table of operations.  Verify - measured (tools/pipe_sweep.py, 2^20 items from malloc memory): the three kernels of a
- * verify chunk leave ramps and tails that the neighbouring chunks' kernels fill when the lanes run side by side (95.7 M/s;
- * in chunk order 79-86), and the small first chunk gets the chip working 0.2 ms after the call.  The batch verification
- * makes one combination per 2^20 items; it, the records form and the digest forms (their
- * message counterparts with the digests in the message slot, 64 bytes per item) are never merged by the combiner. */
-enum { OP_VERIFY, OP_VERIFY_RLC, OP_VERIFY_RECORDS, OP_VERIFY_DIGESTS, OP_VERIFY_DIGESTS_RLC, OP_SIGN, OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X,
-       OP_VERIFY_DOM, OP_SIGN_DOM, OP_VERIFY_KEYED, OP_VERIFY_KEYED_RLC, OP_VERIFY_KEYED_DIGESTS, OP_VERIFY_KEYED_DIGESTS_RLC,
-       OP_VERIFY_KEYED_DOM, OP_SIGN_KEYED, OP_SIGN_KEYED_DOM };
+/* The table of operations.  A row says what the pipeline and the combiner need to know of a call: whether small calls may be merged
+ * (kind), the widths of its inputs, its chunk sizes, the order of its chunks' kernels and what is wiped - not which form of verify
+ * or sign it is; that is the job's (hjob.ks, .digest, .dom, .stats, .sg).
+ * Verify - measured (tools/pipe_sweep.py, 2^20 items from malloc memory): the three kernels of a verify chunk leave ramps and tails
+ * that the neighbouring chunks' kernels fill when the lanes run side by side (95.7 M/s; in chunk order 79-86), and the small first
+ * chunk gets the chip working 0.2 ms after the call.
+ *   OP_VERIFY            ed25519_verify_batch[_multi] alone: the one verify row the combiner merges
+ *   OP_VERIFY_UNMERGED   the digest forms (their message counterparts with the digests in the message slot) and Ed25519ctx / Ed25519ph
+ *                        (two small calls may carry different contexts)
+ *   OP_VERIFY_RLC        the batch verification from messages or digests: one combination per 2^20 items
+ *   OP_VERIFY_RECORDS    one input of the call's own width
+ *   OP_VERIFY_KEYED      every per-item form over a key set (messages, digests, ctx / ph): signatures and 4-byte key indices; never
+ *                        merged - two small calls may carry different key sets
+ *   OP_VERIFY_KEYED_RLC  the batch verification over a key set: the inputs of OP_VERIFY_KEYED, the chunks of OP_VERIFY_RLC
+ *   OP_SIGN              ed25519_sign_batch[_multi] alone: merged
+ *   OP_SIGN_UNMERGED     Ed25519ctx / Ed25519ph
+ *   OP_SIGN_KEYED        every form over a signer set: 4 bytes of key index per item where the others upload 64 bytes of keys; never
+ *                        merged - two small calls may carry different signer sets.  A signing process keeps nothing of a call in the
+ *                        staging buffers: which key signed what, and the signatures, are zeroed there like the other operations' secrets */
+enum { OP_VERIFY, OP_VERIFY_UNMERGED, OP_VERIFY_RLC, OP_VERIFY_RECORDS, OP_VERIFY_KEYED, OP_VERIFY_KEYED_RLC, OP_SIGN, OP_SIGN_UNMERGED, OP_SIGN_KEYED,
+       OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X };
+#define VERIFY_ROW(kind_, w1_, chunk_, first_) { .n_in = 2, .in_w = { 64, w1_, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify, .wipe = WIPE_NONE, \
+    .chain = 0, .kind = kind_, .chunk = chunk_, .first_chunk = first_, .reports = 1 }
 static const struct op g_ops[] = {
-    [OP_VERIFY] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify, .wipe = WIPE_NONE, .chain = 0,
-                    .kind = KIND_VERIFY, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
-    [OP_VERIFY_RLC] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_rlc, .wipe = WIPE_NONE, .chain = 0,
-                    .kind = KIND_NONE, .chunk = CHUNK_MAX, .first_chunk = CHUNK_MAX, .reports = 1 },
-    [OP_VERIFY_RECORDS] = { .n_in = 1, .in_w = { 0, 0, 0 }, .out_w = 1, .has_msgs = 0, .run = run_verify_records, .wipe = WIPE_NONE, .chain = 0,
+    [OP_VERIFY] = VERIFY_ROW(KIND_VERIFY, 32, PIPE_CHUNK_VERIFY, PIPE_FIRST_CHUNK_VERIFY),
+    [OP_VERIFY_UNMERGED] = VERIFY_ROW(KIND_NONE, 32, PIPE_CHUNK_VERIFY, PIPE_FIRST_CHUNK_VERIFY),
+    [OP_VERIFY_RLC] = VERIFY_ROW(KIND_NONE, 32, CHUNK_MAX, CHUNK_MAX),
+    [OP_VERIFY_RECORDS] = { .n_in = 1, .in_w = { 0, 0, 0 }, .out_w = 1, .has_msgs = 0, .run = run_verify, .wipe = WIPE_NONE, .chain = 0,
                     .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
-    [OP_VERIFY_DIGESTS] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_digests, .wipe = WIPE_NONE, .chain = 0,
-                    .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
-    [OP_VERIFY_DIGESTS_RLC] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_digests_rlc, .wipe = WIPE_NONE, .chain = 0,
-                    .kind = KIND_NONE, .chunk = CHUNK_MAX, .first_chunk = CHUNK_MAX, .reports = 1 },
+    [OP_VERIFY_KEYED] = VERIFY_ROW(KIND_NONE, 4, PIPE_CHUNK_VERIFY, PIPE_FIRST_CHUNK_VERIFY),
+    [OP_VERIFY_KEYED_RLC] = VERIFY_ROW(KIND_NONE, 4, CHUNK_MAX, CHUNK_MAX),
     [OP_SIGN] = { .n_in = 2, .in_w = { 32, 32, 0 }, .out_w = 64, .has_msgs = 1, .run = run_sign, .wipe = WIPE_IN0, .chain = 1, .kind = KIND_SIGN },
+    [OP_SIGN_UNMERGED] = { .n_in = 2, .in_w = { 32, 32, 0 }, .out_w = 64, .has_msgs = 1, .run = run_sign, .wipe = WIPE_IN0, .chain = 1, .kind = KIND_NONE },
+    [OP_SIGN_KEYED] = { .n_in = 1, .in_w = { 4, 0, 0 }, .out_w = 64, .has_msgs = 1, .run = run_sign, .wipe = WIPE_IN0 | WIPE_OUT, .chain = 1,
+                    .kind = KIND_NONE },
     [OP_X25519] = { .n_in = 2, .in_w = { 32, 32, 0 }, .out_w = 32, .run = run_x25519, .wipe = WIPE_IN0 | WIPE_OUT, .chain = 1, .kind = KIND_X25519 },
     [OP_GENPUB] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_genpub, .wipe = WIPE_IN0, .chain = 1, .kind = KIND_GENPUB },
     [OP_XBASE] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_xbase, .wipe = WIPE_IN0, .chain = 1, .kind = KIND_XBASE },
     [OP_PK_TO_X] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_pk_to_x, .wipe = WIPE_NONE, .chain = 1, .kind = KIND_PK_TO_X },
     [OP_SK_TO_X] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_sk_to_x, .wipe = WIPE_IN0 | WIPE_OUT, .chain = 1, .kind = KIND_SK_TO_X },
-    /* Ed25519ctx / Ed25519ph: the rows of verify and sign; never merged - two small calls may carry different contexts */
-    [OP_VERIFY_DOM] = { .n_in = 2, .in_w = { 64, 32, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_dom, .wipe = WIPE_NONE, .chain = 0,
-                    .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
-    [OP_SIGN_DOM] = { .n_in = 2, .in_w = { 32, 32, 0 }, .out_w = 64, .has_msgs = 1, .run = run_sign_dom, .wipe = WIPE_IN0, .chain = 1, .kind = KIND_NONE },
-    /* key-set verification: signatures and 4-byte key indices; never merged - two small calls may carry different key sets */
-    [OP_VERIFY_KEYED] = { .n_in = 2, .in_w = { 64, 4, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_keyed, .wipe = WIPE_NONE, .chain = 0,
-                    .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
-    /* its batch verification: the inputs of OP_VERIFY_KEYED, one combination per chunk like OP_VERIFY_RLC */
-    [OP_VERIFY_KEYED_RLC] = { .n_in = 2, .in_w = { 64, 4, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_keyed_rlc, .wipe = WIPE_NONE, .chain = 0,
-                    .kind = KIND_NONE, .chunk = CHUNK_MAX, .first_chunk = CHUNK_MAX, .reports = 1 },
-    /* the digest and ctx / ph forms over a key set: the rows of OP_VERIFY_KEYED and OP_VERIFY_KEYED_RLC - the digests or prehashes
-     * travel in the message slot, EDDSA_DIGEST_BYTES wide; never merged (key sets and contexts differ from call to call) */
-    [OP_VERIFY_KEYED_DIGESTS] = { .n_in = 2, .in_w = { 64, 4, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_keyed_digests, .wipe = WIPE_NONE, .chain = 0,
-                    .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
-    [OP_VERIFY_KEYED_DIGESTS_RLC] = { .n_in = 2, .in_w = { 64, 4, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_keyed_digests_rlc, .wipe = WIPE_NONE, .chain = 0,
-                    .kind = KIND_NONE, .chunk = CHUNK_MAX, .first_chunk = CHUNK_MAX, .reports = 1 },
-    [OP_VERIFY_KEYED_DOM] = { .n_in = 2, .in_w = { 64, 4, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify_keyed_dom, .wipe = WIPE_NONE, .chain = 0,
-                    .kind = KIND_NONE, .chunk = PIPE_CHUNK_VERIFY, .first_chunk = PIPE_FIRST_CHUNK_VERIFY, .reports = 1 },
-    /* signing over a signer set: the rows of OP_SIGN and OP_SIGN_DOM with 4 bytes of key index per item where those upload 64 bytes
-     * of keys; never merged - two small calls may carry different signer sets.  A signing process keeps nothing of a call in the
-     * staging buffers: which key signed what, and the signatures, are zeroed there like the other operations' secrets */
-    [OP_SIGN_KEYED] = { .n_in = 1, .in_w = { 4, 0, 0 }, .out_w = 64, .has_msgs = 1, .run = run_sign_keyed, .wipe = WIPE_IN0 | WIPE_OUT, .chain = 1,
-                    .kind = KIND_NONE },
-    [OP_SIGN_KEYED_DOM] = { .n_in = 1, .in_w = { 4, 0, 0 }, .out_w = 64, .has_msgs = 1, .run = run_sign_keyed, .wipe = WIPE_IN0 | WIPE_OUT, .chain = 1,
-                    .kind = KIND_NONE },
 };
 
 /* a call of operation `id` (in1, msgs, msg_off: NULL where the operation has none) */
@@ -1079,21 +1002,85 @@ static struct hjob job(int id, uint8_t *out, const uint8_t *in0, const uint8_t *
  * host-pointer entry points (include/eddsa_amd.h)
  * ---------------------------------------------------------------------------------------- */
 
+/* The one body of the host-pointer verify and sign forms: the checks every form shares (engine.h: msg_call_open; the ctx / ph
+ * prefix it builds lives on this frame for the length of the call), the row the call's form selects, the job.  A call over a
+ * signer set has its WHOLE index array checked first - an index outside the set ends the call before anything is touched (the
+ * device-pointer forms, which cannot look, write 64 zero bytes for such an item).  The combination's statistics go through a
+ * local array, so that the caller's words change only when the call got as far as its batch size. */
+static int msg_call_run(const struct msg_call *c, int sign)
+{
+    edk_dom dom_buf;
+    uint32_t local[4] = { 0, 0, 0, 0 };
+    struct hjob j = { .in = { c->first, c->second, NULL }, .out = c->out, .msgs = c->msgs, .msg_off = c->msg_off, .msg_len = c->msg_len,
+                      .ks = c->ks, .sg = c->sg, .digest = c->digest, .stats = c->rlc ? local : NULL };
+    int rc = msg_call_open(c, &dom_buf, &j.dom);
+    if (rc < 0) return rc;
+    if (rc == 0 && c->sg) {
+        const uint32_t *key_idx = (const uint32_t *)c->first;
+        uint32_t bad = 0;
+        for (size_t i = 0; i < c->n; i++) bad |= (uint32_t)(key_idx[i] >= c->sg->count);
+        if (bad) return -(int)hipErrorInvalidValue;
+    }
+    if (c->records) { j.stride = c->stride; j.rec_sig = c->rec_sig; j.rec_pub = c->rec_pub; j.rec_msg = c->rec_msg; }
+    j.op = &g_ops[sign ? (c->sg ? OP_SIGN_KEYED : c->ctx ? OP_SIGN_UNMERGED : OP_SIGN)
+                  : c->records ? OP_VERIFY_RECORDS
+                  : c->ks ? (c->rlc ? OP_VERIFY_KEYED_RLC : OP_VERIFY_KEYED)
+                  : c->rlc ? OP_VERIFY_RLC : c->digest || c->ctx ? OP_VERIFY_UNMERGED : OP_VERIFY];
+    rc = rc ? 0 : pipe_run(j, c->n);
+    if (c->stats) memcpy(c->stats, local, sizeof(local));
+    return rc;
+}
+
 int ed25519_verify_batch(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs,
                          const uint64_t *msg_off, size_t msg_len, size_t n)
 {
-    return pipe_run(job(OP_VERIFY, ok, sigs, pubs, msgs, msg_off, msg_len), n);
+    const struct msg_call c = { .out = ok, .first = sigs, .second = pubs, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len, .n = n };
+    return msg_call_run(&c, 0);
 }
 
 int ed25519_verify_batch_rlc(uint8_t *ok, uint32_t stats[4], const uint8_t *sigs, const uint8_t *pubs,
                              const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n)
 {
-    uint32_t local[4] = { 0, 0, 0, 0 };
-    struct hjob j = job(OP_VERIFY_RLC, ok, sigs, pubs, msgs, msg_off, msg_len);
-    j.stats = local;
-    int rc = pipe_run(j, n);
-    if (stats) memcpy(stats, local, sizeof(local));
-    return rc;
+    const struct msg_call c = { .out = ok, .stats = stats, .first = sigs, .second = pubs, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len,
+                                .n = n, .rlc = 1 };
+    return msg_call_run(&c, 0);
+}
+
+int ed25519_verify_digests(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n)
+{
+    const struct msg_call c = { .out = ok, .first = sigs, .second = pubs, .msgs = digests, .msg_len = EDDSA_DIGEST_BYTES, .n = n, .digest = 1 };
+    return msg_call_run(&c, 0);
+}
+
+int ed25519_verify_digests_rlc(uint8_t *ok, uint32_t stats[4], const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n)
+{
+    const struct msg_call c = { .out = ok, .stats = stats, .first = sigs, .second = pubs, .msgs = digests, .msg_len = EDDSA_DIGEST_BYTES, .n = n,
+                                .digest = 1, .rlc = 1 };
+    return msg_call_run(&c, 0);
+}
+
+int ed25519_verify_records(uint8_t *ok, const uint8_t *records, size_t stride, size_t sig_off, size_t pub_off,
+                           size_t msg_off, size_t msg_len, size_t n)
+{
+    const struct msg_call c = { .out = ok, .first = records, .msg_len = msg_len, .n = n,
+                                .records = 1, .stride = stride, .rec_sig = sig_off, .rec_pub = pub_off, .rec_msg = msg_off };
+    return msg_call_run(&c, 0);
+}
+
+int ed25519ctx_verify_batch(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
+                            size_t msg_len, size_t n, const uint8_t *context, size_t context_len)
+{
+    const struct msg_call c = { .out = ok, .first = sigs, .second = pubs, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len, .n = n,
+                                .ctx = CTX_ED25519CTX, .context = context, .context_len = context_len };
+    return msg_call_run(&c, 0);
+}
+
+int ed25519ph_verify_batch(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *prehashes, size_t n,
+                           const uint8_t *context, size_t context_len)
+{
+    const struct msg_call c = { .out = ok, .first = sigs, .second = pubs, .msgs = prehashes, .msg_len = EDDSA_PREHASH_BYTES, .n = n,
+                                .ctx = CTX_ED25519PH, .context = context, .context_len = context_len };
+    return msg_call_run(&c, 0);
 }
 
 /* key-set verification (include/eddsa_amd.h): 4 bytes of index per item travel where the other forms upload 32 bytes of key; the
@@ -1101,177 +1088,97 @@ int ed25519_verify_batch_rlc(uint8_t *ok, uint32_t stats[4], const uint8_t *sigs
 int ed25519_verify_keyed(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
                          const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n)
 {
-    if (!ks) return -(int)hipErrorInvalidValue;
-    struct hjob j = job(OP_VERIFY_KEYED, ok, sigs, (const uint8_t *)key_idx, msgs, msg_off, msg_len);
-    j.ks = ks;
-    return pipe_run(j, n);
+    const struct msg_call c = { .out = ok, .first = sigs, .second = (const uint8_t *)key_idx, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len,
+                                .n = n, .keyed = 1, .ks = ks };
+    return msg_call_run(&c, 0);
 }
 
 int ed25519_verify_keyed_rlc(uint8_t *ok, uint32_t stats[4], const eddsa_amd_keyset *ks, const uint32_t *key_idx,
                              const uint8_t *sigs, const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n)
 {
-    uint32_t local[4] = { 0, 0, 0, 0 };
-    if (!ks) return -(int)hipErrorInvalidValue;
-    struct hjob j = job(OP_VERIFY_KEYED_RLC, ok, sigs, (const uint8_t *)key_idx, msgs, msg_off, msg_len);
-    j.ks = ks;
-    j.stats = local;
-    int rc = pipe_run(j, n);
-    if (stats) memcpy(stats, local, sizeof(local));
-    return rc;
-}
-
-/* the digest, Ed25519ctx and Ed25519ph forms over a key set (include/eddsa_amd.h): NULL arguments end the call before any device
- * is asked; the ctx / ph prefix is built before that (a context of more than 255 bytes ends the call there) and lives on the entry
- * point's frame for the length of the call */
-static int keyed_forms_run(int op, uint8_t *ok, uint32_t *stats, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
-                           const uint8_t *msgs, const uint64_t *msg_off, size_t msg_len, size_t n, const edk_dom *dom)
-{
-    uint32_t local[4] = { 0, 0, 0, 0 };
-    if (!ks) return -(int)hipErrorInvalidValue;
-    if (n == 0) return 0;
-    if (!ok || !key_idx || !sigs || (!msgs && msg_len && !msg_off)) return -(int)hipErrorInvalidValue;   /* (fixed-length items need their buffer) */
-    struct hjob j = job(op, ok, sigs, (const uint8_t *)key_idx, msgs, msg_off, msg_len);
-    j.ks = ks;
-    j.dom = dom;
-    if (op == OP_VERIFY_KEYED_DIGESTS_RLC) j.stats = local;
-    int rc = pipe_run(j, n);
-    if (stats) memcpy(stats, local, sizeof(local));
-    return rc;
+    const struct msg_call c = { .out = ok, .stats = stats, .first = sigs, .second = (const uint8_t *)key_idx, .msgs = msgs, .msg_off = msg_off,
+                                .msg_len = msg_len, .n = n, .keyed = 1, .ks = ks, .rlc = 1 };
+    return msg_call_run(&c, 0);
 }
 
 int ed25519_verify_keyed_digests(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs,
                                  const uint8_t *digests, size_t n)
 {
-    return keyed_forms_run(OP_VERIFY_KEYED_DIGESTS, ok, NULL, ks, key_idx, sigs, digests, NULL, EDDSA_DIGEST_BYTES, n, NULL);
+    const struct msg_call c = { .out = ok, .first = sigs, .second = (const uint8_t *)key_idx, .msgs = digests, .msg_len = EDDSA_DIGEST_BYTES,
+                                .n = n, .keyed = 1, .ks = ks, .digest = 1 };
+    return msg_call_run(&c, 0);
 }
 
 int ed25519_verify_keyed_digests_rlc(uint8_t *ok, uint32_t stats[4], const eddsa_amd_keyset *ks, const uint32_t *key_idx,
                                      const uint8_t *sigs, const uint8_t *digests, size_t n)
 {
-    return keyed_forms_run(OP_VERIFY_KEYED_DIGESTS_RLC, ok, stats, ks, key_idx, sigs, digests, NULL, EDDSA_DIGEST_BYTES, n, NULL);
+    const struct msg_call c = { .out = ok, .stats = stats, .first = sigs, .second = (const uint8_t *)key_idx, .msgs = digests,
+                                .msg_len = EDDSA_DIGEST_BYTES, .n = n, .keyed = 1, .ks = ks, .digest = 1, .rlc = 1 };
+    return msg_call_run(&c, 0);
 }
 
 int ed25519ctx_verify_keyed(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs, const uint8_t *msgs,
                             const uint64_t *msg_off, size_t msg_len, size_t n, const uint8_t *context, size_t context_len)
 {
-    edk_dom dom;
-    const int rc = dom2_fill(&dom, 0, context, context_len);
-    return rc ? rc : keyed_forms_run(OP_VERIFY_KEYED_DOM, ok, NULL, ks, key_idx, sigs, msgs, msg_off, msg_len, n, &dom);
+    const struct msg_call c = { .out = ok, .first = sigs, .second = (const uint8_t *)key_idx, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len,
+                                .n = n, .keyed = 1, .ks = ks, .ctx = CTX_ED25519CTX, .context = context, .context_len = context_len };
+    return msg_call_run(&c, 0);
 }
 
 int ed25519ph_verify_keyed(uint8_t *ok, const eddsa_amd_keyset *ks, const uint32_t *key_idx, const uint8_t *sigs, const uint8_t *prehashes,
                            size_t n, const uint8_t *context, size_t context_len)
 {
-    edk_dom dom;
-    const int rc = dom2_fill(&dom, 1, context, context_len);
-    return rc ? rc : keyed_forms_run(OP_VERIFY_KEYED_DOM, ok, NULL, ks, key_idx, sigs, prehashes, NULL, EDDSA_PREHASH_BYTES, n, &dom);
-}
-
-int ed25519_verify_digests(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n)
-{
-    return pipe_run(job(OP_VERIFY_DIGESTS, ok, sigs, pubs, digests, NULL, EDDSA_DIGEST_BYTES), n);
-}
-
-int ed25519_verify_digests_rlc(uint8_t *ok, uint32_t stats[4], const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n)
-{
-    uint32_t local[4] = { 0, 0, 0, 0 };
-    struct hjob j = job(OP_VERIFY_DIGESTS_RLC, ok, sigs, pubs, digests, NULL, EDDSA_DIGEST_BYTES);
-    j.stats = local;
-    int rc = pipe_run(j, n);
-    if (stats) memcpy(stats, local, sizeof(local));
-    return rc;
-}
-
-int ed25519_verify_records(uint8_t *ok, const uint8_t *records, size_t stride, size_t sig_off, size_t pub_off,
-                           size_t msg_off, size_t msg_len, size_t n)
-{
-    if (!records_ok(stride, sig_off, pub_off, msg_off, msg_len)) return -(int)hipErrorInvalidValue;
-    struct hjob j = job(OP_VERIFY_RECORDS, ok, records, NULL, NULL, NULL, msg_len);
-    j.stride = stride; j.rec_sig = sig_off; j.rec_pub = pub_off; j.rec_msg = msg_off;
-    return pipe_run(j, n);
+    const struct msg_call c = { .out = ok, .first = sigs, .second = (const uint8_t *)key_idx, .msgs = prehashes, .msg_len = EDDSA_PREHASH_BYTES,
+                                .n = n, .keyed = 1, .ks = ks, .ctx = CTX_ED25519PH, .context = context, .context_len = context_len };
+    return msg_call_run(&c, 0);
 }
 
 int ed25519_sign_batch(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,
                        const uint64_t *msg_off, size_t msg_len, size_t n)
 {
-    return pipe_run(job(OP_SIGN, sigs, secs, pubs, msgs, msg_off, msg_len), n);
-}
-
-/* signing over a signer set (include/eddsa_amd.h): NULL arguments end the call before any device is asked, the signer even for an
- * empty batch; then the WHOLE index array is checked - an index outside the set ends the call before anything is touched (the
- * device-pointer forms, which cannot look, write 64 zero bytes for such an item) */
-static int sign_keyed_run(int op, uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
-                          size_t msg_len, size_t n, const edk_dom *dom)
-{
-    uint32_t bad = 0;
-    if (!s) return -(int)hipErrorInvalidValue;
-    if (n == 0) return 0;
-    if (!sigs || !key_idx || (!msgs && msg_len && !msg_off)) return -(int)hipErrorInvalidValue;   /* (fixed-length items need their buffer) */
-    for (size_t i = 0; i < n; i++) bad |= (uint32_t)(key_idx[i] >= s->count);
-    if (bad) return -(int)hipErrorInvalidValue;
-    struct hjob j = job(op, sigs, (const uint8_t *)key_idx, NULL, msgs, msg_off, msg_len);
-    j.sg = s;
-    j.dom = dom;
-    return pipe_run(j, n);
-}
-
-int ed25519_sign_keyed(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
-                       size_t msg_len, size_t n)
-{
-    return sign_keyed_run(OP_SIGN_KEYED, sigs, s, key_idx, msgs, msg_off, msg_len, n, NULL);
-}
-
-int ed25519ctx_sign_keyed(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
-                          size_t msg_len, size_t n, const uint8_t *context, size_t context_len)
-{
-    edk_dom dom;
-    const int rc = dom2_fill(&dom, 0, context, context_len);
-    return rc ? rc : sign_keyed_run(OP_SIGN_KEYED_DOM, sigs, s, key_idx, msgs, msg_off, msg_len, n, &dom);
-}
-
-int ed25519ph_sign_keyed(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *prehashes, size_t n,
-                         const uint8_t *context, size_t context_len)
-{
-    edk_dom dom;
-    const int rc = dom2_fill(&dom, 1, context, context_len);
-    return rc ? rc : sign_keyed_run(OP_SIGN_KEYED_DOM, sigs, s, key_idx, prehashes, NULL, EDDSA_PREHASH_BYTES, n, &dom);
-}
-
-/* Ed25519ctx / Ed25519ph (include/eddsa_amd.h): the prefix is built before anything is touched - a context of more than 255
- * bytes ends the call there - and lives on this frame for the length of the call */
-static int dom_run(int op, int flag, uint8_t *out, const uint8_t *in0, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
-                   size_t msg_len, size_t n, const uint8_t *context, size_t context_len)
-{
-    edk_dom dom;
-    const int rc = dom2_fill(&dom, flag, context, context_len);
-    if (rc) return rc;
-    struct hjob j = job(op, out, in0, pubs, msgs, msg_off, msg_len);
-    j.dom = &dom;
-    return pipe_run(j, n);
+    const struct msg_call c = { .out = sigs, .first = secs, .second = pubs, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len, .n = n };
+    return msg_call_run(&c, 1);
 }
 
 int ed25519ctx_sign_batch(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
                           size_t msg_len, size_t n, const uint8_t *context, size_t context_len)
 {
-    return dom_run(OP_SIGN_DOM, 0, sigs, secs, pubs, msgs, msg_off, msg_len, n, context, context_len);
-}
-
-int ed25519ctx_verify_batch(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *msgs, const uint64_t *msg_off,
-                            size_t msg_len, size_t n, const uint8_t *context, size_t context_len)
-{
-    return dom_run(OP_VERIFY_DOM, 0, ok, sigs, pubs, msgs, msg_off, msg_len, n, context, context_len);
+    const struct msg_call c = { .out = sigs, .first = secs, .second = pubs, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len, .n = n,
+                                .ctx = CTX_ED25519CTX, .context = context, .context_len = context_len };
+    return msg_call_run(&c, 1);
 }
 
 int ed25519ph_sign_batch(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *prehashes, size_t n,
                          const uint8_t *context, size_t context_len)
 {
-    return dom_run(OP_SIGN_DOM, 1, sigs, secs, pubs, prehashes, NULL, EDDSA_PREHASH_BYTES, n, context, context_len);
+    const struct msg_call c = { .out = sigs, .first = secs, .second = pubs, .msgs = prehashes, .msg_len = EDDSA_PREHASH_BYTES, .n = n,
+                                .ctx = CTX_ED25519PH, .context = context, .context_len = context_len };
+    return msg_call_run(&c, 1);
 }
 
-int ed25519ph_verify_batch(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *prehashes, size_t n,
-                           const uint8_t *context, size_t context_len)
+/* signing over a signer set (include/eddsa_amd.h) */
+int ed25519_sign_keyed(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
+                       size_t msg_len, size_t n)
 {
-    return dom_run(OP_VERIFY_DOM, 1, ok, sigs, pubs, prehashes, NULL, EDDSA_PREHASH_BYTES, n, context, context_len);
+    const struct msg_call c = { .out = sigs, .first = (const uint8_t *)key_idx, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len, .n = n,
+                                .keyed = 1, .sg = s };
+    return msg_call_run(&c, 1);
+}
+
+int ed25519ctx_sign_keyed(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
+                          size_t msg_len, size_t n, const uint8_t *context, size_t context_len)
+{
+    const struct msg_call c = { .out = sigs, .first = (const uint8_t *)key_idx, .msgs = msgs, .msg_off = msg_off, .msg_len = msg_len, .n = n,
+                                .keyed = 1, .sg = s, .ctx = CTX_ED25519CTX, .context = context, .context_len = context_len };
+    return msg_call_run(&c, 1);
+}
+
+int ed25519ph_sign_keyed(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *prehashes, size_t n,
+                         const uint8_t *context, size_t context_len)
+{
+    const struct msg_call c = { .out = sigs, .first = (const uint8_t *)key_idx, .msgs = prehashes, .msg_len = EDDSA_PREHASH_BYTES, .n = n,
+                                .keyed = 1, .sg = s, .ctx = CTX_ED25519PH, .context = context, .context_len = context_len };
+    return msg_call_run(&c, 1);
 }
 
 int x25519_batch(uint8_t *out, const uint8_t *scalars, const uint8_t *points, size_t n) { return pipe_run(job(OP_X25519, out, scalars, points, NULL, NULL, 0), n); }
@@ -1352,7 +1259,9 @@ int ed25519_verify_batch_multi(uint8_t *ok, const uint8_t *sigs, const uint8_t *
 
 int ed25519_verify_digests_multi(uint8_t *ok, const uint8_t *sigs, const uint8_t *pubs, const uint8_t *digests, size_t n)
 {
-    return multi_run(job(OP_VERIFY_DIGESTS, ok, sigs, pubs, digests, NULL, EDDSA_DIGEST_BYTES), n);
+    struct hjob j = job(OP_VERIFY_UNMERGED, ok, sigs, pubs, digests, NULL, EDDSA_DIGEST_BYTES);
+    j.digest = 1;
+    return multi_run(j, n);
 }
 
 int ed25519_sign_batch_multi(uint8_t *sigs, const uint8_t *secs, const uint8_t *pubs, const uint8_t *msgs,

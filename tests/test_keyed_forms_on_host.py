@@ -87,6 +87,10 @@ def test_the_calls_check_their_arguments_before_any_device_is_touched():
     ctx = ctypes.c_char_p(b"abc")
     n = SZ(4)
     calls = {                                        # name -> (arguments in front of n, arguments behind n)
+        "ed25519_verify_keyed": ([ok, ks, idx, sig, dig, None, SZ(64)], []),
+        "ed25519_verify_keyed_dev": ([ok, ks, idx, sig, dig, None, SZ(64)], [None]),
+        "ed25519_verify_keyed_rlc": ([ok, st, ks, idx, sig, dig, None, SZ(64)], []),
+        "ed25519_verify_keyed_rlc_dev": ([ok, None, ks, idx, sig, dig, None, SZ(64)], [None]),
         "ed25519_verify_keyed_digests": ([ok, ks, idx, sig, dig], []),
         "ed25519_verify_keyed_digests_dev": ([ok, ks, idx, sig, dig], [None]),
         "ed25519_verify_keyed_digests_rlc": ([ok, st, ks, idx, sig, dig], []),
