@@ -1,116 +1,30 @@
 """The opt-in cofactored equation of verification (include/eddsa_amd.h: eddsa_amd_set_verify_equation, the rules of ZIP-215)
 in Python integers, and the vectors the cofactored tests share (tests/test_cofactor_lane_on_host.py on the CPU,
-tests/test_gpu_cofactored.py on the GPU).  Nothing here comes from the engine or from its source: the curve helpers are those
-of tests/policy_model.py, the group law is the textbook extended-coordinates one (checked against that file's affine law by the
-CPU test), SHA-512 is hashlib's.
+tests/test_gpu_cofactored.py on the GPU).  The curve, the decoder and the hashes are those of tests/ed_model.py.
 
 An item (R | S, A, M) is accepted exactly when S < l, A and R decode - y = the low 255 bits mod p, (y^2 - 1) / (d y^2 + 1) a
 square, x takes the sign bit, x = 0 takes either - and [8]([S]B - [t]A - R) is the neutral element with
 t = SHA-512(prefix | R | A | M) mod l (prefix: empty, or dom2 of Ed25519ctx / Ed25519ph)."""
-import hashlib
 import random
 
 import numpy as np
 
-import policy_model as pm
-from policy_model import D, L, P
-
-D2 = 2 * D % P
-NEUTRAL = (0, 1, 1, 0)
-DOM2_TAG = b"SigEd25519 no Ed25519 collisions"
-
-
-# ---------------------------------------------------------------- the group in extended coordinates (X : Y : Z : T), a = -1
-
-def padd(p, q):
-    x1, y1, z1, t1 = p
-    x2, y2, z2, t2 = q
-    a, b = (y1 - x1) * (y2 - x2) % P, (y1 + x1) * (y2 + x2) % P
-    c, d = t1 * D2 % P * t2 % P, 2 * z1 * z2 % P
-    e, f, g, h = b - a, d - c, d + c, b + a
-    return (e * f % P, g * h % P, f * g % P, e * h % P)
-
-
-def pdbl(p):
-    x1, y1, z1, _ = p
-    a, b, c = x1 * x1 % P, y1 * y1 % P, 2 * z1 * z1 % P
-    e, g, h = ((x1 + y1) ** 2 - a - b) % P, (b - a) % P, (-a - b) % P
-    f = (g - c) % P
-    return (e * f % P, g * h % P, f * g % P, e * h % P)
-
-
-def pneg(p):
-    return (-p[0] % P, p[1], p[2], -p[3] % P)
-
-
-def ext(pt):
-    return (pt[0], pt[1], 1, pt[0] * pt[1] % P)
-
-
-def affine(p):
-    zi = pow(p[2], -1, P)
-    return (p[0] * zi % P, p[1] * zi % P)
-
-
-def is_neutral(p):
-    return p[0] % P == 0 and (p[1] - p[2]) % P == 0
-
-
-def pmul(k, p):
-    acc = NEUTRAL
-    for bit in bin(k)[2:] if k else "":
-        acc = pdbl(acc)
-        if bit == "1":
-            acc = padd(acc, p)
-    return acc
-
-
-def pmul2(k1, p1, k2, p2):
-    """k1 p1 + k2 p2 in one pass over the bits"""
-    both = padd(p1, p2)
-    acc = NEUTRAL
-    for i in range(max(k1.bit_length(), k2.bit_length()) - 1, -1, -1):
-        acc = pdbl(acc)
-        pick = (k1 >> i & 1) | (k2 >> i & 1) << 1
-        if pick:
-            acc = padd(acc, (p1, p2, both)[pick - 1])
-    return acc
-
-
-BY = 4 * pow(5, -1, P) % P
-BX = pm.sqrt(pm.x_squared(BY))
-BX = BX if BX % 2 == 0 else P - BX
-B = ext((BX, BY))
-
-
-def encode(p):
-    x, y = affine(p)
-    return (y | (x & 1) << 255).to_bytes(32, "little")
+import ed_model as em
+from ed_model import B, L, P, affine, arr, challenge, dom2, encode, ext, is_neutral, le, num, padd, pdbl, pmul, pmul2, pneg  # noqa: F401
 
 
 def decode(enc):
-    """the point of these 32 bytes under the permissive rule, or None when y is on no curve point"""
-    v = int.from_bytes(enc, "little")
-    y, sign = (v & (2**255 - 1)) % P, v >> 255
-    xx = pm.x_squared(y)
-    if not pm.is_square(xx):
-        return None
-    x = pm.sqrt(xx)
-    if x & 1 != sign:
-        x = -x % P                                  # (x = 0 stays 0 under either sign bit)
-    return ext((x, y))
+    """the point of these 32 bytes under the permissive rule (x = 0 takes either sign bit), or None when y is on no curve point"""
+    pt = em.decode_reference(enc)
+    return None if pt is None else ext(pt)
 
 
 # ---------------------------------------------------------------- the rule
 
-def challenge(sig, pub, msg, prefix=b""):
-    return int.from_bytes(hashlib.sha512(prefix + bytes(sig[:32]) + bytes(pub) + bytes(msg)).digest(), "little") % L
-
-
 def accepts_t(sig, pub, t):
     """the cofactored verdict of (sig, pub) with the challenge scalar t given"""
     sig, pub = bytes(sig), bytes(pub)
-    s = int.from_bytes(sig[32:], "little")
+    s = num(sig[32:])
     if s >= L:
         return False
     a, r = decode(pub), decode(sig[:32])
@@ -122,10 +36,6 @@ def accepts_t(sig, pub, t):
 
 def accepts(sig, pub, msg, prefix=b""):
     return accepts_t(sig, pub, challenge(sig, pub, msg, prefix))
-
-
-def dom2(flag, context):
-    return DOM2_TAG + bytes([flag, len(context)]) + bytes(context)
 
 
 # ---------------------------------------------------------------- the vectors
@@ -161,9 +71,9 @@ def vectors(prefix=b"", mlen=32, honest=16, seed=20261019):
     def sign(a, pub_pt, r, r_pt, msg):
         pub, renc = encode(pub_pt), encode(r_pt)
         t = challenge(renc, pub, msg, prefix)
-        return renc + ((r + t * a) % L).to_bytes(32, "little"), pub
+        return renc + le((r + t * a) % L), pub
 
-    tors = pm.torsion_encodings()
+    tors = em.torsion_encodings()
     for a_enc in tors:
         for r_enc in tors:
             put(CLASSES[0], r_enc + bytes(32), a_enc, rng.randbytes(mlen))
@@ -173,7 +83,7 @@ def vectors(prefix=b"", mlen=32, honest=16, seed=20261019):
         sig, pub = sign(a, pmul(a, B), r, pmul(r, B), msg)
         honest_items.append((sig, pub, msg))
         put(CLASSES[1], sig, pub, msg)
-    small = [ext(pt) for pt in sorted(pm.torsion_points()) if pt != (0, 1)]
+    small = [ext(pt) for pt in sorted(em.torsion_points()) if pt != (0, 1)]
     mixed_items = []
     for t_a in small:
         for t_r in small:
@@ -182,10 +92,10 @@ def vectors(prefix=b"", mlen=32, honest=16, seed=20261019):
             mixed_items.append((sig, pub, msg))
             put(CLASSES[2], sig, pub, msg)
     for k, (sig, pub, msg) in enumerate(honest_items):
-        s = int.from_bytes(sig[32:], "little") + (k % 14 + 1) * L
+        s = num(sig[32:]) + (k % 14 + 1) * L
         if s >= 2**256:
-            s = int.from_bytes(sig[32:], "little") + L
-        put(CLASSES[3], sig[:32] + s.to_bytes(32, "little"), pub, msg)
+            s = num(sig[32:]) + L
+        put(CLASSES[3], sig[:32] + le(s), pub, msg)
     for sig, pub, msg in honest_items:
         bit = rng.randrange(512)
         flipped = bytearray(sig)
@@ -197,8 +107,8 @@ def vectors(prefix=b"", mlen=32, honest=16, seed=20261019):
         else:
             put(CLASSES[5], sig, _off_curve(rng), msg)
     for sig, pub, msg in mixed_items:
-        s = int.from_bytes(sig[32:], "little") + L
-        put(CLASSES[6], sig[:32] + s.to_bytes(32, "little"), pub, msg)
+        s = num(sig[32:]) + L
+        put(CLASSES[6], sig[:32] + le(s), pub, msg)
     return out
 
 
@@ -214,7 +124,7 @@ def from_json(rows):
 
 def arrays(vecs):
     """-> sig (n, 64), pub (n, 32), msg (n, mlen), accept (n,) as uint8, read-only"""
-    out = (pm.arr([v["sig"] for v in vecs]), pm.arr([v["pub"] for v in vecs]), pm.arr([v["msg"] for v in vecs]),
+    out = (arr([v["sig"] for v in vecs]), arr([v["pub"] for v in vecs]), arr([v["msg"] for v in vecs]),
            np.array([v["accept"] for v in vecs], np.uint8))
     for a in out:
         a.setflags(write=False)

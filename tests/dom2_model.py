@@ -3,39 +3,21 @@
 mod l and the oracle's two curve operations (orc_ed_scale_base, orc_ed_dual_scale).  Nothing here comes from the engine or from
 its source.  `orc` is the ctypes handle of oracle/liboracle.so (the `oracle` fixture's .lib).  Honestly generated keys only."""
 import ctypes
-import hashlib
 import json
 import os
 
 import numpy as np
 
-L = 2**252 + 27742317777372353535851937790883648493
-TAG = b"SigEd25519 no Ed25519 collisions"
+import ed_model as em
+from ed_model import DOM2_TAG as TAG, L, clamped, dom2, le, num, sha  # noqa: F401  (for this model's users)
+
 CTX, PH = 0, 1
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rfc8032_dom2.json")
 
 
-def dom2(flag, context):
-    assert flag in (CTX, PH) and len(context) <= 255
-    return TAG + bytes([flag, len(context)]) + bytes(context)
-
-
-def sha(*parts):
-    return hashlib.sha512(b"".join(parts)).digest()
-
-
-def le(x, n=32):
-    return int(x).to_bytes(n, "little")
-
-
-def num(b):
-    return int.from_bytes(b, "little")
-
-
 def secret_scalar(sk):
     """(a, prefix) of ed25519_key_setup: h = SHA-512(sk), a = h[0..32) clamped, prefix = h[32..64)"""
-    h = sha(sk)
-    return (num(h[:32]) & ((1 << 254) - 8)) | (1 << 254), h[32:]
+    return clamped(sk), sha(sk)[32:]
 
 
 def scale_base(orc, k):
@@ -53,7 +35,7 @@ def nonce(sk, mprime, flag, context):
 
 
 def challenge(r_bytes, pk, mprime, flag, context):
-    return num(sha(dom2(flag, context), r_bytes, pk, mprime)) % L
+    return em.challenge(r_bytes, pk, mprime, dom2(flag, context))
 
 
 def sign(orc, sk, pk, mprime, flag, context):

@@ -1,31 +1,20 @@
 """Plain-integer models for the tests of key-set verification (include/eddsa_amd.h: ed25519_verify_keyed): the pair search of the
 half-length route (libeddsa_amd/csrc/halve.h: halve_scalar_lane), the decoding rule that the out-of-range key must fail, and
 the construction of mixed keyed batches.  Test infrastructure only: Python integers, hashlib and numpy."""
-import hashlib
-
 import numpy as np
 
-P = 2**255 - 19
-L = 2**252 + 27742317777372353535851937790883648493
-D = (-121665 * pow(121666, P - 2, P)) % P
+from ed_model import L, P, challenge, decode_reference, le  # noqa: F401  (P, challenge: for this model's users)
+
 N8L = 8 * L
 
 # the key bytes an item whose index names no key of the set is given (libeddsa_amd/csrc/keyed_lanes.h: keyed_no_key): y = 2
-NO_KEY = (2).to_bytes(32, "little")
+NO_KEY = le(2)
 
 
 def decodes(enc):
     """whether 32 bytes decode to a curve point under the most permissive rule in use (the cofactored equation's, which is the
-    reference import's test for "a root exists"): y = the low 255 bits mod p, (y^2 - 1) / (d y^2 + 1) a square (0 included)"""
-    y = (int.from_bytes(enc, "little") & (2**255 - 1)) % P
-    u, v = (y * y - 1) % P, (D * y * y + 1) % P
-    x2 = u * pow(v, P - 2, P) % P
-    return x2 == 0 or pow(x2, (P - 1) // 2, P) == 1
-
-
-def challenge(sig, pub, msg):
-    """t = SHA-512(R || A || M) mod l"""
-    return int.from_bytes(hashlib.sha512(bytes(sig[:32]) + bytes(pub) + bytes(msg)).digest(), "little") % L
+    reference import's test for "a root exists")"""
+    return decode_reference(enc) is not None
 
 
 def short_pair(t, bits=134):

@@ -10,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from hostlib import ROOT, declared_names, exported_names, header_text
 
 
 def _lib_path(name="libeddsa_amd.so"):
@@ -20,15 +20,8 @@ def _lib_path(name="libeddsa_amd.so"):
     return path
 
 
-def _exported(path):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-    return {l.split()[-1] for l in out.splitlines() if " T " in l}       # (kernel handles and __hip_cuid_* are data symbols)
-
-
 def _declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return set(re.findall(r"EDDSA(?:_AMD)?_DECL\s+[\w\s\*]+?\b(\w+)\s*\(", text))
+    return declared_names(header_text(strip_comments=True, name=header), r"EDDSA(?:_AMD)?_DECL")
 
 
 def test_library_exports_every_declared_symbol():
@@ -45,9 +38,9 @@ def test_library_exports_every_declared_symbol():
     assert len(product) >= 13 + 14 + 5 and len(debug) >= 10 and not (product & debug)
     for n in product:
         assert hasattr(lib, n), n
-    assert _exported(_lib_path()) == product, _exported(_lib_path()) ^ product                     # nothing else leaks out
+    assert exported_names(_lib_path()) == product, exported_names(_lib_path()) ^ product                     # nothing else leaks out
     dbg = _lib_path("libeddsa_amd_debug.so")
-    assert _exported(dbg) == product | debug, _exported(dbg) ^ (product | debug)
+    assert exported_names(dbg) == product | debug, exported_names(dbg) ^ (product | debug)
     # the debug build is the product's objects plus the hooks: the same kernels (one compilation of each .hip file serves both)
     mk = open(os.path.join(ROOT, "Makefile")).read()
     assert "$(DEBUGLIB): $(BUILD)/kernels.o $(BUILD)/rlc.o $(BUILD)/eddsa_amd.dbg.o $(BUILD)/host_pipe.dbg.o" in mk
@@ -122,11 +115,9 @@ def test_the_layer_probes_are_a_library_of_their_own():
     probe = os.path.join(ROOT, "libeddsa_amd", "libeddsa_amd_probe.so")
     if not os.path.exists(probe):
         subprocess.check_call(["make", "-C", ROOT, "probe"])
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "eddsa_amd_probe.h")).read(), flags=re.S)
-    declared = set(re.findall(r"EDDSA_PROBE_DECL\s+[\w\s\*]+?\b(\w+)\s*\(", text))
+    declared = declared_names(header_text(strip_comments=True, name="eddsa_amd_probe.h"), r"EDDSA_PROBE_DECL")
     assert declared == {"eddsa_amd_probe_layer", "eddsa_amd_probe_halve"}
-    out = subprocess.check_output(["nm", "-D", "--defined-only", probe], text=True)
-    assert {l.split()[-1] for l in out.splitlines() if " T " in l} == declared
+    assert exported_names(probe) == declared
     out = subprocess.check_output(["nm", "-D", "--defined-only", _lib_path()], text=True)
     assert not [l for l in out.splitlines() if "probe" in l or "debug_layer" in l or "debug_halve" in l]
     ldd = subprocess.check_output(["ldd", probe], text=True)

@@ -4,21 +4,19 @@ model that generates them, the lane steps of k_cofactor_points / k_cofactor_eval
 for the host with every bound asserted (tests/host_check/cofactor_check.cpp) against the model, the setters and the header."""
 import collections
 import ctypes
-import hashlib
 import json
 import os
 import random
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import cofactored_model as cm
 import policy_model as pm
-from policy_model import L, P
+from ed_model import L, P, arr, le, num, sha
+from hostlib import ROOT, build_check, exported_names, header_text
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = "verify_cofactored.json"
 COUNTS = {"a_torsion": 196, "b_honest": 16, "c_mixed": 49, "d_s_plus_kl": 16, "e_bit_flip": 16, "f_off_curve": 8, "g_mixed_s_plus_l": 49}
 ACCEPTED = ("a_torsion", "b_honest", "c_mixed")
@@ -32,11 +30,7 @@ def vecs():
 @pytest.fixture(scope="module")
 def cofactorcheck(tmp_path_factory):
     """tests/host_check/cofactor_check.cpp built with the flags of the hostcheck fixture (conftest.py), outside the tree"""
-    lib = str(tmp_path_factory.mktemp("cofactor_check") / "libcofactorcheck.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-DED_HOST_CHECK", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(ROOT, "libeddsa_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_check", "cofactor_check.cpp"), "-o", lib])
-    h = ctypes.CDLL(lib)
+    h = build_check(tmp_path_factory, "cofactor")
     h.cc_violations.restype = ctypes.c_long
     return h
 
@@ -50,28 +44,10 @@ def lane(h, sig, pk, dig):
 
 
 def digests(sig, pk, msg, prefix=b""):
-    return pm.arr([hashlib.sha512(prefix + sig[i, :32].tobytes() + pk[i].tobytes() + msg[i].tobytes()).digest() for i in range(len(sig))])
+    return arr([sha(prefix, sig[i, :32].tobytes(), pk[i].tobytes(), msg[i].tobytes()) for i in range(len(sig))])
 
 
 # ---------------------------------------------------------------- the model
-
-def test_the_model_group_law_against_the_affine_one():
-    rng = random.Random(5)
-    base = (cm.BX, cm.BY)
-    assert (-cm.BX * cm.BX + cm.BY * cm.BY - 1 - pm.D * cm.BX * cm.BX * cm.BY * cm.BY) % P == 0 and cm.BX % 2 == 0
-    assert cm.is_neutral(cm.pmul(L, cm.B)) and not cm.is_neutral(cm.pmul(L - 1, cm.B))
-    for _ in range(20):
-        k1, k2 = rng.randrange(L), rng.randrange(1 << 64)
-        q = pm.mul(k2, base)
-        assert cm.affine(cm.pmul(k1, cm.B)) == pm.mul(k1, base)
-        assert cm.affine(cm.pmul2(k1, cm.B, k2, cm.ext(q))) == pm.mul(k1 + k2 * k2, base)
-        assert cm.affine(cm.pdbl(cm.ext(q))) == pm.add(q, q) and cm.affine(cm.padd(cm.ext(q), cm.pneg(cm.ext(q)))) == (0, 1)
-        assert cm.affine(cm.decode(cm.encode(cm.ext(q)))) == q
-    for enc in pm.torsion_encodings():                   # every encoding of the eight points decodes, to a point 8 kills
-        assert cm.is_neutral(cm.pmul(8, cm.decode(enc)))
-    # x = 0 takes either sign bit; a non-canonical y counts
-    assert cm.affine(cm.decode((1 | 1 << 255).to_bytes(32, "little"))) == (0, 1) == cm.affine(cm.decode((P + 1).to_bytes(32, "little")))
-
 
 def test_the_vectors_have_their_classes_and_verdicts(vecs):
     assert collections.Counter(v["class"] for v in vecs) == COUNTS
@@ -79,7 +55,7 @@ def test_the_vectors_have_their_classes_and_verdicts(vecs):
         assert v["accept"] == (v["class"] in ACCEPTED), v["class"]
         assert len(v["sig"]) == 64 and len(v["pub"]) == 32 and len(v["msg"]) == 32
     for v in vecs:                                       # the classes are what they say
-        s = int.from_bytes(v["sig"][32:], "little")
+        s = num(v["sig"][32:])
         if v["class"] in ("d_s_plus_kl", "g_mixed_s_plus_l"):
             assert L <= s < 2**256
         if v["class"] in ("a_torsion",):
@@ -129,7 +105,7 @@ def test_the_lane_under_a_dom2_prefix_and_with_other_digests(cofactorcheck, vecs
     sig, pk, msg, accept = cm.arrays(dvecs)
     assert np.array_equal(lane(cofactorcheck, sig, pk, digests(sig, pk, msg, prefix)), accept)
     plain = digests(sig, pk, msg)
-    want = np.array([cm.accepts_t(sig[i], pk[i], int.from_bytes(plain[i].tobytes(), "little") % L) for i in range(len(sig))], np.uint8)
+    want = np.array([cm.accepts_t(sig[i], pk[i], num(plain[i].tobytes()) % L) for i in range(len(sig))], np.uint8)
     assert np.array_equal(lane(cofactorcheck, sig, pk, plain), want)
     cls = np.array([v["class"] for v in dvecs])
     assert want[cls == "a_torsion"].all() and not want[cls == "b_honest"].any()
@@ -141,14 +117,13 @@ def test_the_lane_on_edges_and_random_strings(cofactorcheck, vecs):
     R, and 300 seeded random triples (about a quarter have both encodings on the curve)"""
     rng = random.Random(20261019)
     honest = [v for v in vecs if v["class"] == "b_honest"][0]
-    enc = lambda v: v.to_bytes(32, "little")
-    items = [(honest["sig"][:32] + enc(s), honest["pub"]) for s in (0, 1, L - 1, L, L + 1, 1 << 252, (1 << 253) - 1, (1 << 256) - 1)]
-    y_edges = [enc(y | sign << 255) for y in (0, 1, 2, P - 1, P, P + 1, P + 18, (1 << 255) - 1) for sign in (0, 1)]
+    items = [(honest["sig"][:32] + le(s), honest["pub"]) for s in (0, 1, L - 1, L, L + 1, 1 << 252, (1 << 253) - 1, (1 << 256) - 1)]
+    y_edges = [le(y | sign << 255) for y in (0, 1, 2, P - 1, P, P + 1, P + 18, (1 << 255) - 1) for sign in (0, 1)]
     items += [(r + bytes(32), a) for a in y_edges for r in y_edges]
     items += [(rng.randbytes(64), rng.randbytes(32)) for _ in range(300)]
-    sig, pk = pm.arr([s for s, _ in items]), pm.arr([a for _, a in items])
-    dig = pm.arr([rng.randbytes(64) for _ in items])
-    want = np.array([cm.accepts_t(s, a, int.from_bytes(dig[i].tobytes(), "little") % L) for i, (s, a) in enumerate(items)], np.uint8)
+    sig, pk = arr([s for s, _ in items]), arr([a for _, a in items])
+    dig = arr([rng.randbytes(64) for _ in items])
+    want = np.array([cm.accepts_t(s, a, num(dig[i].tobytes()) % L) for i, (s, a) in enumerate(items)], np.uint8)
     got = lane(cofactorcheck, sig, pk, dig)
     bad = np.nonzero(got != want)[0]
     assert not len(bad), [(items[i][0].hex(), items[i][1].hex(), int(got[i])) for i in bad[:3]]
@@ -209,14 +184,12 @@ def test_the_c_setter_returns_0_or_invalid_value():
 
 
 def test_the_header_declares_the_setter_and_its_two_values():
-    text = open(os.path.join(ROOT, "include", "eddsa_amd.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text, code = header_text(), header_text(strip_comments=True)
     defined = {name: int(value, 0) for name, value in re.findall(r"#define\s+(EDDSA_AMD_EQUATION_\w+)\s+(\w+)", code)}
     assert defined == {"EDDSA_AMD_EQUATION_COFACTORLESS": 0, "EDDSA_AMD_EQUATION_COFACTORED": 1}
     assert re.search(r"#define\s+EDDSA_AMD_VERIFY_POLICY_MASK\s+0xF00\b", code)       # not a bit of the off-curve word
     assert re.findall(r"(\w+_DECL)\s+int\s+eddsa_amd_set_verify_equation\s*\(\s*int\s+equation\s*\)", code) == ["RFC8032_EDDSA_DECL"]
-    out = subprocess.check_output(["nm", "-D", "--defined-only", os.path.join(ROOT, "libeddsa_amd", "libeddsa_amd.so")], text=True)
-    assert " T eddsa_amd_set_verify_equation" in out
+    assert "eddsa_amd_set_verify_equation" in exported_names("libeddsa_amd.so")
     flat = " ".join(text.split())
     for words in ("[8]([S]B - [t]A - R)", "x = 0 with the sign bit set is accepted", "for EVERY input", "nothing is queued",
                   "that caveat does not exist"):

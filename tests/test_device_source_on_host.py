@@ -9,11 +9,9 @@ import hashlib
 
 import numpy as np
 
+from ed_model import D, H, L, P, decode_reference, inv, le, small_order_ys
 from gen_golden import golden_msg
 
-H = bytes.fromhex
-P = 2**255 - 19
-L = 2**252 + 27742317777372353535851937790883648493
 SZ = ctypes.c_size_t
 
 
@@ -25,10 +23,6 @@ def call(h, name, out_len, *args):
 
 def no_violations(h):
     assert h.hc_violations() == 0, h.hc_first_violation()
-
-
-def le(x, n=32):
-    return int(x).to_bytes(n, "little")
 
 
 EXTREME = [0, 1, 2, 9, 19, P - 1, P, P + 1, 2**255 - 19 - 1, 2**255 - 1, 2**255, 2**255 + 18, 2**256 - 1,
@@ -117,7 +111,7 @@ def test_batch_inverse_is_the_inverse(hostcheck):
         out = ctypes.create_string_buffer(32 * k)
         hostcheck.hc_batch_inverse(out, b"".join(le(z) for z in zs), k)
         for j, z in enumerate(zs):
-            assert int.from_bytes(out.raw[32 * j:32 * j + 32], "little") == pow(z % P, P - 2, P), (k, j)
+            assert int.from_bytes(out.raw[32 * j:32 * j + 32], "little") == inv(z % P), (k, j)
     no_violations(hostcheck)
 
 
@@ -205,8 +199,7 @@ def test_tables_match_the_reference_points(hostcheck, oracle, golden):
     hostcheck.hc_tables(base16.ctypes.data_as(ctypes.c_void_p), comb.ctypes.data_as(ctypes.c_void_p))
     pos = [0, 26, 51, 77, 102, 128, 153, 179, 204, 230]
     val = lambda limbs: sum(int(v) << s for v, s in zip(limbs, pos))  # noqa: E731
-    inv2 = pow(2, P - 2, P)
-    ell = 2**252 + 27742317777372353535851937790883648493
+    inv2 = inv(2)
 
     def enc(entry):
         ymx, ypx = val(entry[0:10]), val(entry[10:20])
@@ -218,7 +211,7 @@ def test_tables_match_the_reference_points(hostcheck, oracle, golden):
         assert enc(comb[k]) == pts[32 * k:32 * k + 32], k
     out = ctypes.create_string_buffer(32)
     for e in range(704):
-        oracle.lib.orc_ed_scale_base(out, int((e % 32 + 1) * 4096 ** (e // 32) % ell).to_bytes(32, "little"))
+        oracle.lib.orc_ed_scale_base(out, int((e % 32 + 1) * 4096 ** (e // 32) % L).to_bytes(32, "little"))
         assert enc(comb[e]) == out.raw, e
     for k in list(range(1, 32769, 331)) + [32767, 32768]:
         oracle.lib.orc_ed_scale_base(out, int(k).to_bytes(32, "little"))
@@ -249,7 +242,7 @@ def test_fuzz_field_and_scalars_with_hypothesis(hostcheck, oracle):
         assert call(hostcheck, "hc_fe_mul", 32, a, b) == le(x * y % P)
         assert call(hostcheck, "hc_fe_mul_loose", 32, a, ka, b, kb) == le(ka * x * kb * y % P)
         assert call(hostcheck, "hc_fe_sq", 32, a) == le(x * x % P)
-        assert call(hostcheck, "hc_fe_inv", 32, a) == le(pow(x % P, P - 2, P))
+        assert call(hostcheck, "hc_fe_inv", 32, a) == le(inv(x % P))
 
     @settings(max_examples=300, deadline=None)
     @given(st.binary(min_size=64, max_size=64), b32, b32, b32)
@@ -267,33 +260,21 @@ def test_fuzz_field_and_scalars_with_hypothesis(hostcheck, oracle):
 # ---------------------------------------------------------------------------------------------------------
 # batch verification (libeddsa_amd/csrc/rlc_lanes.h): the per-lane steps of rlc.hip on the host, bounds asserted
 # ---------------------------------------------------------------------------------------------------------
-P = 2**255 - 19
-L = 2**252 + 27742317777372353535851937790883648493
-D = (-121665 * pow(121666, P - 2, P)) % P
+# an anchor that does not come from the model: the y of the five points of small order, as literals
 SMALL_ORDER_Y = {1, P - 1, 0,
                  int.from_bytes(bytes.fromhex("26e8958fc2b227b045c3f489f2ef98f0d5dfac05d3c63339b13802886d53fc05"), "little"),
                  int.from_bytes(bytes.fromhex("c7176a703d4dd84fba3c0b760d10670f2a2053fa2c39ccc64ec7fd7792ac037a"), "little")}
 
 
 def _decode(enc):
-    """(on_curve, x, y) of ed_import's result (lib/ed.c:100-149), big-integer arithmetic"""
-    v = int.from_bytes(enc, "little")
-    sign, y = v >> 255, (v & (2**255 - 1)) % P
-    u, w = (y * y - 1) % P, (D * y * y + 1) % P
-    x2 = u * pow(w, P - 2, P) % P
-    x = pow(x2, (P + 3) // 8, P)
-    if (x * x - x2) % P:
-        x = x * pow(2, (P - 1) // 4, P) % P
-    on = (x * x - x2) % P == 0
-    if on and (x & 1) != sign:
-        x = (P - x) % P
-    return on, x, y
+    """(on_curve, x, y) of ed_import's result (lib/ed.c:100-149); x and y are None off the curve"""
+    return (True,) + decode_reference(enc) if decode_reference(enc) else (False, None, None)
 
 
 def test_rlc_decoding_and_routing_flags(hostcheck, oracle):
     import ctypes
     rng = np.random.default_rng(21)
-    le = lambda x: int(x).to_bytes(32, "little")  # noqa: E731
+    assert SMALL_ORDER_Y == small_order_ys()
     encs = [le(1), le(P - 1), le(0), le(1 << 255), le(1 | 1 << 255), le(P), le(P + 1), le(P + 3), le((P - 1) | 1 << 255),
             bytes.fromhex("26e8958fc2b227b045c3f489f2ef98f0d5dfac05d3c63339b13802886d53fc05"),
             bytes.fromhex("c7176a703d4dd84fba3c0b760d10670f2a2053fa2c39ccc64ec7fd7792ac03fa")]

@@ -6,13 +6,13 @@ import hashlib
 import os
 import random
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-L = (1 << 252) + 27742317777372353535851937790883648493
+from ed_model import L
+from hostlib import ROOT, build_check, declared_names
+
 PATTERN = int("88" * 32, 16)                       # what the prepare kernels add: nibble - 8 is the signed digit
 NAMES = ("ed25519_verify_digests", "ed25519_verify_digests_dev", "ed25519_verify_digests_rlc", "ed25519_verify_digests_rlc_dev",
          "ed25519_verify_digests_multi")
@@ -21,11 +21,7 @@ NAMES = ("ed25519_verify_digests", "ed25519_verify_digests_dev", "ed25519_verify
 @pytest.fixture(scope="module")
 def digestcheck(tmp_path_factory):
     """tests/host_check/digest_check.cpp built with the flags of the hostcheck fixture (conftest.py), outside the tree"""
-    lib = str(tmp_path_factory.mktemp("digest_check") / "libdigestcheck.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-DED_HOST_CHECK", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(ROOT, "libeddsa_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_check", "digest_check.cpp"), "-o", lib])
-    h = ctypes.CDLL(lib)
+    h = build_check(tmp_path_factory, "digest")
     h.dc_violations.restype = ctypes.c_long
     return h
 
@@ -106,14 +102,14 @@ def test_wrappers_validate_before_the_c_call():
 def test_the_header_declares_the_five_names():
     text = open(os.path.join(ROOT, "include", "eddsa_amd.h")).read()
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = set(re.findall(r"EDDSA_AMD_DECL\s+[\w\s\*]+?\b(\w+)\s*\(", code))
+    declared = declared_names(code, r"EDDSA_AMD_DECL")
     assert set(NAMES) <= declared
     for name in NAMES:
         (args,) = re.findall(r"\b" + name + r"\s*\(([^)]*)\)", code)
         assert "const uint8_t *digests" in args and "msg" not in args, name
         assert ("void *stream" in args) == name.endswith("_dev"), name
     ref = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "eddsa.h")).read(), flags=re.S)
-    single = set(re.findall(r"EDDSA_DECL\s+[\w\s\*]+?\b(\w+)\s*\(", ref))
+    single = declared_names(ref, r"EDDSA_DECL")
     assert len(single) == 13 and len(declared | single) == 52              # the reference's 13 stay 13; 47 exported names become 52
     # the vouching rule and the combiner rule are stated where the caller reads them
     flat = " ".join(text.split())

@@ -7,14 +7,13 @@ import hashlib
 import os
 import random
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import dom2_model as dm
+from hostlib import ROOT, build_check, declared_names
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 L = dm.L
 PATTERN = int("88" * 32, 16)
 NAMES = ("ed25519ctx_sign_batch", "ed25519ctx_verify_batch", "ed25519ph_sign_batch", "ed25519ph_verify_batch",
@@ -27,11 +26,7 @@ TOTALS_MOD_128 = (110, 111, 112, 113, 127, 128, 129)      # the edges of one- an
 @pytest.fixture(scope="module")
 def domcheck(tmp_path_factory):
     """tests/host_check/dom2_check.cpp built with the flags of the hostcheck fixture (conftest.py), outside the tree"""
-    lib = str(tmp_path_factory.mktemp("dom2_check") / "libdom2check.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-DED_HOST_CHECK", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(ROOT, "libeddsa_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_check", "dom2_check.cpp"), "-o", lib])
-    h = ctypes.CDLL(lib)
+    h = build_check(tmp_path_factory, "dom2")
     h.d2_violations.restype = ctypes.c_long
     return h
 
@@ -175,7 +170,7 @@ def test_wrappers_validate_before_the_c_call():
 def test_the_header_declares_the_eight_names():
     text = open(os.path.join(ROOT, "include", "eddsa_amd.h")).read()
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = set(re.findall(r"EDDSA(?:_AMD)?_DECL\s+[\w\s\*]+?\b(\w+)\s*\(", code))
+    declared = declared_names(code, r"EDDSA(?:_AMD)?_DECL")
     assert set(NAMES) <= declared
     for name in NAMES:
         (args,) = re.findall(r"\b" + name + r"\s*\(([^)]*)\)", code)

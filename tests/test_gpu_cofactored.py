@@ -3,7 +3,6 @@ k_cofactor_list / k_cofactor_points / k_cofactor_eval; rlc.hip: k_rlc_points): u
 and R decode and [8](S B - t A - R) = 0.  Expected verdicts are the Python model's (tests/cofactored_model.py, the committed
 vectors of tests/golden/verify_cofactored.json and their siblings under a dom2 prefix) - never the engine's.  Every test puts the
 equation, the policy and the mode word back."""
-import contextlib
 import hashlib
 
 import numpy as np
@@ -11,38 +10,12 @@ import pytest
 
 import cofactored_model as cm
 import policy_model as pm
+from gpu_kit import bad, dev, host, settings
 from policy_model import BITS, STRICT
 
 pytestmark = pytest.mark.gpu
 G = 8192                                            # items per group of the batch verification
 MLEN = 32
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(x):
-    return x if isinstance(x, np.ndarray) else x.cpu().numpy()
-
-
-@contextlib.contextmanager
-def settings(engine, cofactored=True, policy=0, algo=0, offcurve=True, rlc_min=None):
-    try:
-        engine.set_verify_algo(algo)
-        engine.set_offcurve_mode(offcurve)
-        engine.set_verify_policy(policy)
-        engine.set_verify_equation(cofactored)
-        if rlc_min is not None:
-            engine.set_rlc_min_items(rlc_min)
-        yield
-    finally:
-        engine.set_verify_equation(False)
-        engine.set_verify_policy(0)
-        engine.set_offcurve_mode(True)
-        engine.set_verify_algo(0)
-        engine.set_rlc_min_items(engine.RLC_MIN_ITEMS_DEFAULT)
 
 
 @pytest.fixture(scope="module")
@@ -68,10 +41,6 @@ def digests(sig, pk, msg, prefix=b""):
     return pm.arr([hashlib.sha512(prefix + sig[i, :32].tobytes() + pk[i].tobytes() + msg[i].tobytes()).digest() for i in range(len(sig))])
 
 
-def bad(got, want):
-    return np.nonzero(np.asarray(host(got)) != want)[0][:10]
-
-
 # ---------------------------------------------------------------- 1: parity with the model, every size, route and form
 
 @pytest.mark.parametrize("algo,offcurve,n", [(0, True, 257), (0, True, 600), (1, True, 600), (2, True, 600), (3, True, 600),
@@ -82,7 +51,7 @@ def test_device_form_at_every_size_route_and_mode(engine, arrs, cofactorless, al
     the self-check mode 2, where the reference-order chain decides every item first and the algo chooses its companions"""
     sig, pk, msg, want, pick = cm.tiled(arrs, n)
     assert (cofactorless[pick] != want).sum() > 64 and 0 < want.sum() < n
-    with settings(engine, algo=algo, offcurve=offcurve):
+    with settings(engine, cofactored=True, algo=algo, offcurve=offcurve):
         got = host(engine.ed25519_verify_batch(dev(sig), dev(pk), dev(msg), msg_len=MLEN))
     assert got.dtype == np.uint8 and np.array_equal(got, want), bad(got, want)
 
@@ -96,7 +65,7 @@ def test_single_items_and_the_single_item_call(engine, vecs, arrs, cofactorless)
         if v["class"] != "c_mixed" or not cofactorless[i]:           # (a mixed-order item the pass itself rejects)
             first.setdefault(v["class"], i)
     assert len(first) == len(cm.CLASSES)
-    with settings(engine):
+    with settings(engine, cofactored=True):
         for cls, i in first.items():
             got = host(engine.ed25519_verify_batch(dev(sig[i:i + 1]), dev(pk[i:i + 1]), dev(msg[i:i + 1]), msg_len=MLEN))
             assert got.tolist() == [want[i]], cls
@@ -108,7 +77,7 @@ def test_host_records_and_digest_forms(engine, arrs, cofactorless):
     sig, pk, msg, want, pick = cm.tiled(arrs, 600, seed=2)
     dig = digests(sig, pk, msg)
     rec = np.ascontiguousarray(np.concatenate([sig, pk, msg], axis=1))
-    with settings(engine):
+    with settings(engine, cofactored=True):
         assert not len(bad(engine.ed25519_verify_batch(sig, pk, msg, msg_len=MLEN), want)), "host"
         assert not len(bad(engine.ed25519_verify_records(rec, 0, 64, 96, MLEN), want)), "records, host"
         assert not len(bad(engine.ed25519_verify_records(dev(rec), 0, 64, 96, MLEN), want)), "records, device"
@@ -134,7 +103,7 @@ def test_ctx_and_ph_forms(engine, flag):
             return engine.ed25519ph_verify_batch(s, p, m, c)
         return engine.ed25519ctx_verify_batch(s, p, m, c, msg_len=mlen)
 
-    with settings(engine):
+    with settings(engine, cofactored=True):
         assert not len(bad(run(sig, pk, msg, context), want)), "host"
         assert not len(bad(run(dev(sig), dev(pk), dev(msg), context), want)), "device"
         assert not len(bad(run(dev(sig), dev(pk), dev(msg), b"another"), other)), "another context"
@@ -159,7 +128,7 @@ def test_batch_verification_equals_the_per_item_rule(engine, vecs, arrs):
     want = np.concatenate([want1, arrs[3][pick2]])
     assert want[G:].all() and 0 < want[:G].sum() < G
     dig = digests(sig, pk, msg)
-    with settings(engine, rlc_min=0):
+    with settings(engine, cofactored=True, rlc_min=0):
         per_item = host(engine.ed25519_verify_batch(dev(sig), dev(pk), dev(msg), msg_len=MLEN))
         assert np.array_equal(per_item, want), bad(per_item, want)
         for form, (ok, st) in rlc_forms(engine, sig, pk, msg, dig):
@@ -184,7 +153,7 @@ def test_a_non_canonical_r_sends_its_group_to_the_per_item_kernels(engine, vecs,
         sig = pm.arr([odd if i == at else honest[i % len(honest)]["sig"] for i in range(n)])
         pk = pm.arr([pub if i == at else honest[i % len(honest)]["pub"] for i in range(n)])
         msg = pm.arr([m if i == at else honest[i % len(honest)]["msg"] for i in range(n)])
-        with settings(engine, rlc_min=0):
+        with settings(engine, cofactored=True, rlc_min=0):
             ok, st = engine.ed25519_verify_batch_rlc(dev(sig), dev(pk), dev(msg), msg_len=MLEN, return_stats=True)
         assert host(ok).all() and tuple(st) == (0, n, 1, 0), st
         with settings(engine, cofactored=False, rlc_min=0):
@@ -199,7 +168,7 @@ def test_the_strict_rules_compose_with_the_equation(engine, arrs):
     sig, pk, msg, want, pick = cm.tiled(arrs, 600, seed=5)
     for policy in BITS + (STRICT,):
         both = want & pm.holds_batch(policy, sig, pk)
-        with settings(engine, policy=policy):
+        with settings(engine, cofactored=True, policy=policy):
             got_d = host(engine.ed25519_verify_batch(dev(sig), dev(pk), dev(msg), msg_len=MLEN))
             got_h = engine.ed25519_verify_batch(sig, pk, msg, msg_len=MLEN)
         assert np.array_equal(got_d, both) and np.array_equal(got_h, both), (hex(policy), bad(got_d, both))
@@ -245,6 +214,6 @@ def test_multi_device_form(engine, arrs):
     assert engine.init_devices([0]) == 1
     sig, pk, msg, want, pick = cm.tiled(arrs, 5000, seed=7)
     dig = digests(sig, pk, msg)
-    with settings(engine):
+    with settings(engine, cofactored=True):
         assert not len(bad(engine.ed25519_verify_batch_multi(sig, pk, msg, msg_len=MLEN), want))
         assert not len(bad(engine.ed25519_verify_digests_multi(sig, pk, dig), want))

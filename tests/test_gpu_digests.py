@@ -3,28 +3,18 @@ device-pointer forms): item i is accepted exactly when the reference's ed25519_v
 with SHA-512(R_i || A_i || M) = digests[i].  Digests come from hashlib, expected verdicts from the oracle or from the committed
 vectors' accept fields - never from the engine's own message form."""
 import hashlib
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from ed_model import H, L, arr
 from gen_golden import golden_msg  # tools/ is on sys.path (conftest)
+from gpu_kit import dev
+from hostlib import build_c_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-H = bytes.fromhex
-L = 2**252 + 27742317777372353535851937790883648493
 G = 8192                                            # items per group of the batch verification
-
-
-def arr(rows):
-    return np.frombuffer(b"".join(rows), np.uint8).reshape(len(rows), -1).copy()
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def digests_of(sig, pk, msgs):
@@ -257,10 +247,7 @@ def test_c_program_against_the_shipped_library(engine, oracle, signed, tmp_path)
     """tests/c/verify_digests.c: plain C against eddsa_amd.h, linked against libeddsa_amd.so (which exports no hook), on the
     (0, 300) batch of the kernel test: ed25519_verify_digests and ed25519_verify_digests_rlc return the oracle's verdicts"""
     sig, pk, dig, want = corrupted(oracle, signed, 300)
-    exe = tmp_path / "verify_digests"
-    subprocess.check_call(["gcc", "-std=c11", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "c", "verify_digests.c"), "-L" + os.path.join(ROOT, "libeddsa_amd"),
-                           "-leddsa_amd", "-Wl,-rpath," + os.path.join(ROOT, "libeddsa_amd"), "-o", str(exe)])
+    exe = build_c_program(tmp_path, "verify_digests.c", libs=("eddsa_amd",), wall=True)
     files = []
     for name, a in (("sigs", sig), ("pubs", pk), ("digests", dig), ("want", want)):
         files.append(str(tmp_path / (name + ".bin")))

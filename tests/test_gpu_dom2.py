@@ -8,26 +8,13 @@ import numpy as np
 import pytest
 
 import dom2_model as dm
+from ed_model import arr
+from gpu_kit import dev, host
 
 pytestmark = pytest.mark.gpu
 L = dm.L
 CTX, PH = dm.CTX, dm.PH
 INVALID_VALUE = -1                                  # -hipErrorInvalidValue
-
-
-def arr(rows, width=None):
-    rows = [bytes(r) for r in rows]
-    width = len(rows[0]) if width is None else width
-    return np.frombuffer(b"".join(rows), np.uint8).reshape(len(rows), width).copy()
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.array(a)).cuda()     # (a copy: the shared keys are read-only arrays)
-
-
-def host(x):
-    return x if isinstance(x, np.ndarray) else x.cpu().numpy()
 
 
 def run(engine, what, flag, device, first, pk, rows, context, ragged=False):

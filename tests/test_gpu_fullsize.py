@@ -6,13 +6,10 @@ import hashlib
 import numpy as np
 import pytest
 
+from gpu_kit import dev
+
 pytestmark = pytest.mark.gpu
 N = 1 << 20
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def test_x25519_2_20_digest_and_commutativity(engine, golden):

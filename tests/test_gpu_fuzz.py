@@ -4,12 +4,10 @@ the oracle, host-pointer and device-pointer paths.  Bit-exact."""
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from ed_model import L
+from gpu_kit import always_combine, dev  # noqa: F401  (always_combine: a fixture)
 
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("always_combine")]
 
 
 SIZES = [1, 2, 3, 63, 64, 65, 255, 256, 257, 511, 777, 1024, 2047, 2048, 2049, 4099, 24576, 24577, 16383, 16384, 16385, 20011, 32768, 32769, 33000]
@@ -18,14 +16,6 @@ SIZES = [1, 2, 3, 63, 64, 65, 255, 256, 257, 511, 777, 1024, 2047, 2048, 2049, 4
 @pytest.fixture(scope="module")
 def device_set(engine):
     return engine.init_devices()
-
-
-@pytest.fixture(autouse=True)
-def always_combine(engine):
-    """small batches through the combination itself (by default calls below 5 x 2^15 items use the per-item kernels)"""
-    engine.set_rlc_min_items(0)
-    yield
-    engine.set_rlc_min_items(engine.RLC_MIN_ITEMS_DEFAULT)
 
 
 # EDDSA_FUZZ_EXTRA=k adds k more random cases (a longer soak after kernel changes)
@@ -62,9 +52,8 @@ def test_fuzz_against_the_oracle(engine, oracle, device_set, case):
     for i in np.nonzero(kind == 3)[0]: pk[i, bit[i] // 8 % 32] ^= 1 << (bit[i] % 8)
     g = np.nonzero(kind == 4)[0]
     pk[g] = rng.integers(0, 256, (len(g), 32), dtype=np.uint8)
-    ell = 2**252 + 27742317777372353535851937790883648493
     for i in np.nonzero(kind == 5)[0]:
-        s = int.from_bytes(sig[i, 32:].tobytes(), "little") + ell
+        s = int.from_bytes(sig[i, 32:].tobytes(), "little") + L
         if s < 2**256: sig[i, 32:] = np.frombuffer(s.to_bytes(32, "little"), np.uint8)
     if ragged:
         want = np.array([oracle.verify(sig[i].tobytes(), pk[i].tobytes(), one(i)) for i in range(n)], np.uint8)

@@ -7,18 +7,10 @@ import numpy as np
 import pytest
 
 import workload  # tools/ is on sys.path (conftest)
+from ed_model import H, L, P, arr, challenge, le
+from gpu_kit import dev
 
 pytestmark = pytest.mark.gpu
-H = bytes.fromhex
-
-
-def arr(rows):
-    return np.frombuffer(b"".join(rows), np.uint8).reshape(len(rows), -1).copy()
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @pytest.fixture(autouse=True)
@@ -109,8 +101,6 @@ def test_commitments_that_only_decode_permissively(engine, oracle):
     """R strings that ed_import would accept but ed_export never produces - x = 0 with the sign bit set, y >= p -
     next to their canonical spellings, under keys and S for which the canonical one is accepted: the byte comparison
     of the reference rejects the former, and so must the point comparison of the half-length route"""
-    P = 2**255 - 19
-    le = lambda x: int(x).to_bytes(32, "little")   # noqa: E731
     ident, minus1 = le(1), le(P - 1)
     rs = [ident, le(1 | 1 << 255), le(P + 1), le((P + 1) | 1 << 255), minus1, le((P - 1) | 1 << 255), le(P), le(2**255 - 1)]
     keys = [ident, minus1, le(1 | 1 << 255)]
@@ -131,7 +121,6 @@ def test_device_pair_search_against_integers(engine):
     """the pair search as the DEVICE runs it (reciprocal by Newton steps instead of the host build's division) against
     Euclid on Python integers: random t, tiny t, t = (8l)/k with giant quotients at the start, in the middle and
     right at the threshold, quotients just below and above the 2^31 limit"""
-    L = 2**252 + 27742317777372353535851937790883648493
     N = 8 * L
 
     def model(t, th=134, retry_min=122):
@@ -188,8 +177,6 @@ def test_small_passes_with_items_that_have_no_short_pair(engine, oracle):
     """a pass of 2^15 signatures (the four-lane route) contains two or three items whose t has no short pair: their
     waves run 64 windows and the other items of those waves add neutral elements; same bytes as the oracle, also
     with corrupted items next to them"""
-    import hashlib
-    L = 2**252 + 27742317777372353535851937790883648493
     N = 8 * L
 
     def has_pair(t):
@@ -208,8 +195,7 @@ def test_small_passes_with_items_that_have_no_short_pair(engine, oracle):
     sk, msg = workload.sign_inputs(n, seed=21, config=2)
     pk = engine.ed25519_genpub_batch(sk)
     sig = engine.ed25519_sign_batch(sk, pk, msg)
-    long_items = [i for i in range(n) if not has_pair(
-        int.from_bytes(hashlib.sha512(sig[i, :32].tobytes() + pk[i].tobytes() + msg[i].tobytes()).digest(), "little") % L)]
+    long_items = [i for i in range(n) if not has_pair(challenge(sig[i].tobytes(), pk[i].tobytes(), msg[i].tobytes()))]
     assert 1 <= len(long_items) <= 12, long_items
     want = np.ones(n, np.uint8)
     assert np.array_equal(engine.ed25519_verify_batch(sig, pk, msg, msg_len=32), want)

@@ -2,9 +2,7 @@
 what the reference's ed25519_verify returns for (sigs[i], keys[key_idx[i]], message i), an index outside the key set rejects its
 item.  Expected verdicts are the oracle's on (sig, keys[idx], msg) - under a policy or the cofactored equation those of
 tests/policy_model.py and tests/cofactored_model.py - never the engine's own unkeyed call.  Every test puts the settings back."""
-import contextlib
 import ctypes
-import os
 import subprocess
 
 import numpy as np
@@ -14,43 +12,13 @@ import cofactored_model as cm
 import keyed_model as km
 import policy_model as pm
 import workload  # tools/ is on sys.path (conftest)
+from gpu_kit import bad, dev, dev_idx, host, settings
+from hostlib import build_c_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = (1, 2, 63, 64, 65, 255, 257, 4099)
 KEYSETS = (1, 3, 300)
 MAXLEN = 150
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def dev_idx(idx):
-    """uint32 indices as the int32 tensor the device form takes (0xFFFFFFFF travels as -1)"""
-    return dev(np.ascontiguousarray(idx, dtype=np.uint32).view(np.int32))
-
-
-def host(x):
-    return x if isinstance(x, np.ndarray) else x.cpu().numpy()
-
-
-def bad(got, want):
-    return np.nonzero(np.asarray(host(got)) != want)[0][:10]
-
-
-@contextlib.contextmanager
-def settings(engine, offcurve=True, policy=0, cofactored=False):
-    try:
-        engine.set_offcurve_mode(offcurve)
-        engine.set_verify_policy(policy)
-        engine.set_verify_equation(cofactored)
-        yield
-    finally:
-        engine.set_verify_equation(False)
-        engine.set_verify_policy(0)
-        engine.set_offcurve_mode(True)
 
 
 def keyed(engine, form, ks, idx, sig, msgs, off=None, mlen=None):
@@ -451,10 +419,7 @@ def test_c_program_against_the_shipped_library(engine, oracle, honest, tmp_path)
     want = want.copy()
     idx[0], idx[256] = len(keys), 0xFFFFFFFF
     want[0] = want[256] = 0
-    exe = tmp_path / "verify_keyed"
-    subprocess.check_call(["gcc", "-std=c11", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "c", "verify_keyed.c"), "-L" + os.path.join(ROOT, "libeddsa_amd"),
-                           "-leddsa_amd", "-Wl,-rpath," + os.path.join(ROOT, "libeddsa_amd"), "-o", str(exe)])
+    exe = build_c_program(tmp_path, "verify_keyed.c", libs=("eddsa_amd",), wall=True)
     files = []
     for name, a in (("keys", keys), ("idx", idx.astype(np.uint32)), ("sigs", sig), ("msgs", msgs), ("want", want)):
         files.append(str(tmp_path / (name + ".bin")))

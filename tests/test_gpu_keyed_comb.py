@@ -13,7 +13,8 @@ import keyed_comb_model as cm
 import keyed_model as km
 import policy_model as pm
 import workload  # tools/ is on sys.path (conftest)
-from test_gpu_keyed import bad, dev, dev_idx, honest, host, keyed, mixed, settings, valid257, _off_curve_keys  # noqa: F401 (fixtures)
+from gpu_kit import bad, dev, dev_idx, host, settings
+from test_gpu_keyed import honest, keyed, mixed, valid257, _off_curve_keys  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 SIZES = (1, 63, 64, 65, 255, 256, 257, 1000)

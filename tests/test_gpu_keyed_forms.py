@@ -13,7 +13,9 @@ import pytest
 import dom2_model as dm
 import keyed_model as km
 import policy_model as pm
-from test_gpu_keyed import bad, dev, dev_idx, honest, host, keyed, mixed, settings  # noqa: F401 (fixtures)
+from ed_model import arr
+from gpu_kit import always_combine, bad, dev, dev_idx, host, settings  # noqa: F401  (always_combine: a fixture)
+from test_gpu_keyed import honest, keyed, mixed  # noqa: F401 (fixtures)
 from test_gpu_keyed_comb import comb_set
 from test_gpu_keyed_rlc import expected_stats
 
@@ -23,10 +25,6 @@ SIZES = (1, 63, 64, 65, 255, 256, 257, 1000, 4099)
 KEYSETS = (1, 3, 300)
 CONTEXTS = (b"", b"ctx", bytes(range(255)))
 NO_IDX = 0xFFFFFFFF
-
-
-def arr(rows):
-    return np.frombuffer(b"".join(rows), np.uint8).reshape(len(rows), -1).copy()
 
 
 def u32(idx):
@@ -285,13 +283,6 @@ def test_a_digest_over_another_key_is_rejected(engine, honest, oracle):
 
 
 # ---------------------------------------------------------------- 4: the combination over digests
-
-@pytest.fixture()
-def always_combine(engine):
-    engine.set_rlc_min_items(0)
-    yield
-    engine.set_rlc_min_items(engine.RLC_MIN_ITEMS_DEFAULT)
-
 
 NMAX = 2 * G + 5
 

@@ -4,9 +4,7 @@ and nothing else.  Expected verdicts are the oracle's on (sig, keys[idx], msg) -
 of tests/policy_model.py and tests/cofactored_model.py; the digit rows, window points and group verdicts of a pass are held
 against the integer model of tests/test_gpu_rlc_stages.py with the key terms collected per key.  Every test puts the settings
 back."""
-import contextlib
 import ctypes
-import os
 import subprocess
 
 import numpy as np
@@ -16,53 +14,17 @@ import cofactored_model as cm
 import keyed_model as km
 import policy_model as pm
 import test_gpu_rlc_stages as st
+from gpu_kit import always_combine, bad, dev, dev_idx, host, settings  # noqa: F401  (always_combine: a fixture)
+from hostlib import build_c_program
 
-pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("always_combine")]
 G = st.G
 L = st.L
 NMAX = 2 * G + 300
 SIZES = (1, 2, 255, 257, 8191, 8192, 8193, NMAX)
 KEYSETS = (1, 3, 300, 8191, 8192)
-OFF_CURVE = (2).to_bytes(32, "little")                                       # y = 2: no curve point (keyed_model.NO_KEY)
+OFF_CURVE = km.NO_KEY                                       # y = 2: no curve point (keyed_model.NO_KEY)
 ORDER_2 = (st.P - 1).to_bytes(32, "little")                                  # (0, -1)
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def dev_idx(idx):
-    return dev(np.ascontiguousarray(idx, dtype=np.uint32).view(np.int32))
-
-
-def host(x):
-    return x if isinstance(x, np.ndarray) else x.cpu().numpy()
-
-
-def bad(got, want):
-    return np.nonzero(np.asarray(host(got)) != want)[0][:10]
-
-
-@pytest.fixture(autouse=True)
-def always_combine(engine):
-    engine.set_rlc_min_items(0)
-    yield
-    engine.set_rlc_min_items(engine.RLC_MIN_ITEMS_DEFAULT)
-
-
-@contextlib.contextmanager
-def settings(engine, offcurve=True, policy=0, cofactored=False):
-    try:
-        engine.set_offcurve_mode(offcurve)
-        engine.set_verify_policy(policy)
-        engine.set_verify_equation(cofactored)
-        yield
-    finally:
-        engine.set_verify_equation(False)
-        engine.set_verify_policy(0)
-        engine.set_offcurve_mode(True)
 
 
 def krlc(engine, form, ks, idx, sig, msgs, off=None, mlen=None):
@@ -226,7 +188,7 @@ def check_keyed_stages(engine, m, key_bytes, idx, which_r):
     for kb in key_bytes:
         on, x, y = st.decode(kb)
         assert on
-        key_pts.append(st.neg(st.ext(x, y)))
+        key_pts.append(st.neg(st.ext((x, y))))
     seg = engine.debug_rlc_snapshot("seg")
     gok = engine.debug_rlc_snapshot("gok")
     assert seg.shape == (m.groups, 48, 4, 32)
@@ -496,10 +458,7 @@ def test_c_program_against_the_shipped_library(engine, oracle, keys, tmp_path):
     sig[G + 9, 32 + 4] ^= 1
     want = np.ones(n, np.uint8)
     want[[0, 256, G + 9]] = 0
-    exe = tmp_path / "verify_keyed_rlc"
-    subprocess.check_call(["gcc", "-std=c11", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "c", "verify_keyed_rlc.c"), "-L" + os.path.join(ROOT, "libeddsa_amd"),
-                           "-leddsa_amd", "-Wl,-rpath," + os.path.join(ROOT, "libeddsa_amd"), "-o", str(exe)])
+    exe = build_c_program(tmp_path, "verify_keyed_rlc.c", libs=("eddsa_amd",), wall=True)
     files = []
     for name, a in (("keys", pk[:300]), ("idx", idx.astype(np.uint32)), ("sigs", sig), ("msgs", msgs), ("want", want)):
         files.append(str(tmp_path / (name + ".bin")))

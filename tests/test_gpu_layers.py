@@ -11,16 +11,9 @@ import hashlib
 import numpy as np
 import pytest
 
+from ed_model import H, L, P, inv, le
+
 pytestmark = pytest.mark.gpu
-
-H = bytes.fromhex
-P = 2**255 - 19
-L = 2**252 + 27742317777372353535851937790883648493
-
-
-def le(x, n=32):
-    return int(x).to_bytes(n, "little")
-
 
 def golden_msg(i):
     out, c = b"", 0
@@ -80,7 +73,7 @@ def test_field_layer_random_and_extreme_operands_on_the_device(probe):
             assert got == [le(ka * val(a) * kb * val(b) % P) for a, b in pairs[-300:]], (ka, kb)
     sample = pairs[:256] + pairs[-4:]
     got = probe.debug_layer("fe_inv", [a for a, _ in sample], 32)
-    assert got == [le(pow(val(a) % P, P - 2, P)) for a, _ in sample]
+    assert got == [le(inv(val(a) % P)) for a, _ in sample]
     got = probe.debug_layer("fe_pow2523", [a for a, _ in sample], 32)
     assert got == [le(pow(val(a) % P, (P - 5) // 8, P)) for a, _ in sample]
 

@@ -11,24 +11,16 @@ import hashlib
 import numpy as np
 import pytest
 
+from ed_model import L, challenge
+from gpu_kit import dev
+
 pytestmark = pytest.mark.gpu
-L = 2**252 + 27742317777372353535851937790883648493
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def ragged(msgs):
     off = np.zeros(len(msgs) + 1, np.uint64)
     off[1:] = np.cumsum([len(m) for m in msgs])
     return np.frombuffer(b"".join(msgs), np.uint8).copy(), off
-
-
-def challenge(sig, pk, msg):
-    """t = SHA-512(R || A || M) mod l by hashlib: what ed25519-sha512.c:166-171 feeds the scalar multiplication"""
-    return int.from_bytes(hashlib.sha512(sig[:32] + pk + msg).digest(), "little") % L
 
 
 @pytest.mark.parametrize("mlen,n", [(4096, 96), (16384, 80), (65536, 70), (1 << 20, 6)])

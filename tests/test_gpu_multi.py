@@ -9,13 +9,10 @@ import sys
 import numpy as np
 import pytest
 
+from gpu_kit import dev
+from hostlib import ROOT, build_c_program
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def golden_msg(i):
@@ -196,13 +193,10 @@ def test_c_program_on_the_multi_device_entry_points(engine, golden, tmp_path):
     """tests/c/multi_device.c: a plain C caller (HIP runtime API for its own buffers) of
     eddsa_amd_init_devices / *_multi / ed25519_verify_batch_multi_dev, linked against the library through
     its SONAME link libeddsa.so.0"""
-    exe = tmp_path / "multi_device"
     lib = os.path.join(ROOT, "libeddsa_amd")
     if not os.path.exists(os.path.join(lib, "libeddsa.so.0")):
         os.symlink("libeddsa_amd.so", os.path.join(lib, "libeddsa.so.0"))
-    subprocess.check_call(["gcc", "-std=c11", "-O1", "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "c", "multi_device.c"), "-L" + lib, "-leddsa_amd",
-                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-o", str(exe)])
+    exe = build_c_program(tmp_path, "multi_device.c", libs=("eddsa_amd",), rocm=True)
     msgs = tmp_path / "msgs.bin"
     msgs.write_bytes(b"".join(golden_msg(i) for i in range(1024)))
     r = subprocess.run([str(exe), os.path.join(ROOT, "tests", "golden", "ed25519_table.bin"), str(msgs)],

@@ -6,16 +6,12 @@ import os
 import numpy as np
 import pytest
 
+from ed_model import D, H, L, P, arr, inv, le
 from gen_golden import golden_msg  # tools/ is on sys.path (conftest)
+from gpu_kit import dev
+from hostlib import ROOT, build_c_program
 
 pytestmark = pytest.mark.gpu
-H = bytes.fromhex
-L = 2**252 + 27742317777372353535851937790883648493
-P = 2**255 - 19
-
-
-def arr(rows):
-    return np.frombuffer(b"".join(rows), np.uint8).reshape(len(rows), -1).copy()
 
 
 def ragged(msgs):
@@ -23,11 +19,6 @@ def ragged(msgs):
     off[1:] = np.cumsum([len(m) for m in msgs])
     blob = np.frombuffer(b"".join(msgs), np.uint8).copy() if off[-1] else np.zeros(0, np.uint8)
     return blob, off
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 # ---------------------------------------------------------------- golden vectors
@@ -102,17 +93,14 @@ def test_device_tables_equal_the_reference_table(engine, oracle, golden):
 
     def enc(entry):
         ymx, ypx = val(entry[0:10]), val(entry[10:20])
-        inv2 = pow(2, P - 2, P)
-        y, x = (ypx + ymx) * inv2 % P, (ypx - ymx) * inv2 % P
-        d = (-121665 * pow(121666, P - 2, P)) % P
-        assert val(entry[20:30]) == 2 * d * x * y % P
-        return (y | (x & 1) << 255).to_bytes(32, "little")
+        y, x = (ypx + ymx) * inv(2) % P, (ypx - ymx) * inv(2) % P
+        assert val(entry[20:30]) == 2 * D * x * y % P
+        return le(y | (x & 1) << 255)
 
     pts = golden("comb_points.bin")
-    ell = 2**252 + 27742317777372353535851937790883648493
     out = ctypes.create_string_buffer(32)
     for e in range(704):
-        oracle.lib.orc_ed_scale_base(out, int((e % 32 + 1) * 4096 ** (e // 32) % ell).to_bytes(32, "little"))
+        oracle.lib.orc_ed_scale_base(out, int((e % 32 + 1) * 4096 ** (e // 32) % L).to_bytes(32, "little"))
         assert enc(comb[e]) == out.raw, e
     for k in range(1, 9):                                  # base16[k] = k*B = comb row 0 = the reference's row 0
         assert enc(comb[k - 1]) == pts[32 * (k - 1):32 * k]
@@ -569,15 +557,11 @@ def test_c_program_against_eddsa_h(engine, golden, tmp_path):
     exports no hook (the two programs below use the measurement surface and link libeddsa_amd_debug.so)"""
     import os
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "selftest_dropin"
-    subprocess.check_call(["gcc", "-std=c11", "-O1", "-I" + os.path.join(root, "include"),
-                           os.path.join(root, "tests", "c", "selftest_dropin.c"), "-L" + os.path.join(root, "libeddsa_amd"),
-                           "-leddsa_amd", "-Wl,-rpath," + os.path.join(root, "libeddsa_amd"), "-o", str(exe)])
+    exe = build_c_program(tmp_path, "selftest_dropin.c", libs=("eddsa_amd",))
     msgs = tmp_path / "msgs.bin"
     msgs.write_bytes(b"".join(golden_msg(i) for i in range(1024)))
-    r = subprocess.run([str(exe), os.path.join(root, "tests", "golden", "x25519_table.bin"),
-                        os.path.join(root, "tests", "golden", "ed25519_table.bin"), str(msgs)],
+    r = subprocess.run([str(exe), os.path.join(ROOT, "tests", "golden", "x25519_table.bin"),
+                        os.path.join(ROOT, "tests", "golden", "ed25519_table.bin"), str(msgs)],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "selftest_dropin: ok" in r.stdout
@@ -591,15 +575,11 @@ def test_host_side_stress_program_on_the_real_runtime(engine, golden, tmp_path):
     fake runtime under the sanitizers)"""
     import os
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "host_side_stress"
-    subprocess.check_call(["gcc", "-std=c11", "-O1", "-pthread", "-I" + os.path.join(root, "include"),
-                           os.path.join(root, "tests", "c", "host_side_stress.c"), "-L" + os.path.join(root, "libeddsa_amd"),
-                           "-leddsa_amd_debug", "-Wl,-rpath," + os.path.join(root, "libeddsa_amd"), "-ldl", "-o", str(exe)])
+    exe = build_c_program(tmp_path, "host_side_stress.c", libs=("eddsa_amd_debug", "dl"), threads=True)
     msgs = tmp_path / "msgs.bin"
     msgs.write_bytes(b"".join(golden_msg(i) for i in range(1024)))
-    r = subprocess.run([str(exe), os.path.join(root, "tests", "golden", "ed25519_table.bin"), str(msgs),
-                        os.path.join(root, "tests", "golden", "x25519_table.bin"), "16", "12"],
+    r = subprocess.run([str(exe), os.path.join(ROOT, "tests", "golden", "ed25519_table.bin"), str(msgs),
+                        os.path.join(ROOT, "tests", "golden", "x25519_table.bin"), "16", "12"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "host_side_stress: ok (16 threads" in r.stdout
@@ -613,15 +593,11 @@ def test_threaded_c_application_on_the_single_item_functions(engine, golden, tmp
     import os
     import re
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "threaded_callers"
-    subprocess.check_call(["gcc", "-std=c11", "-O1", "-pthread", "-I" + os.path.join(root, "include"),
-                           os.path.join(root, "tests", "c", "threaded_callers.c"), "-L" + os.path.join(root, "libeddsa_amd"),
-                           "-leddsa_amd_debug", "-Wl,-rpath," + os.path.join(root, "libeddsa_amd"), "-o", str(exe)])
+    exe = build_c_program(tmp_path, "threaded_callers.c", libs=("eddsa_amd_debug",), threads=True)
     msgs = tmp_path / "msgs.bin"
     msgs.write_bytes(b"".join(golden_msg(i) for i in range(1024)))
-    r = subprocess.run([str(exe), os.path.join(root, "tests", "golden", "ed25519_table.bin"), str(msgs),
-                        os.path.join(root, "tests", "golden", "x25519_table.bin"), "64", "100"],
+    r = subprocess.run([str(exe), os.path.join(ROOT, "tests", "golden", "ed25519_table.bin"), str(msgs),
+                        os.path.join(ROOT, "tests", "golden", "x25519_table.bin"), "64", "100"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "threaded_callers: ok" in r.stdout
@@ -821,7 +797,6 @@ def test_concurrent_host_threads(engine, oracle):
 
 def _bench_line(args, env_extra=None, launcher=None):
     import json, socket, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, **(env_extra or {}))
     cmd = [sys.executable]
     if launcher:
@@ -830,7 +805,7 @@ def _bench_line(args, env_extra=None, launcher=None):
             port = s.getsockname()[1]
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(launcher),
                 "--master-addr", "127.0.0.1", "--master-port", str(port)]
-    out = subprocess.run(cmd + [os.path.join(root, "bench.py")] + args, env=env, cwd=root, capture_output=True,
+    out = subprocess.run(cmd + [os.path.join(ROOT, "bench.py")] + args, env=env, cwd=ROOT, capture_output=True,
                          text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -2,43 +2,18 @@
 under policy P item i is accepted exactly when the reference accepts it AND every predicate of P holds for its bytes.  Expected
 verdicts are (the oracle's, or the committed vectors' accept fields) AND the Python model of tests/policy_model.py - never the
 engine's.  Every test puts the mode word back."""
-import contextlib
 import hashlib
 
 import numpy as np
 import pytest
 
 import policy_model as pm
+from gpu_kit import dev, host, settings
 from policy_model import BITS, MLEN, POLICIES, STRICT
 
 pytestmark = pytest.mark.gpu
 G = 8192                                            # items per group of the batch verification
 BLOCK = 256                                         # lanes per block of k_verify_policy (kernels.hip)
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(x):
-    return x if isinstance(x, np.ndarray) else x.cpu().numpy()
-
-
-@contextlib.contextmanager
-def settings(engine, policy, algo=0, offcurve=True, rlc_min=None):
-    try:
-        engine.set_verify_algo(algo)
-        engine.set_offcurve_mode(offcurve)
-        engine.set_verify_policy(policy)
-        if rlc_min is not None:
-            engine.set_rlc_min_items(rlc_min)
-        yield
-    finally:
-        engine.set_verify_policy(0)
-        engine.set_offcurve_mode(True)
-        engine.set_verify_algo(0)
-        engine.set_rlc_min_items(engine.RLC_MIN_ITEMS_DEFAULT)
 
 
 @pytest.fixture(scope="module")
@@ -74,7 +49,7 @@ def test_vector_files_through_every_form(engine, golden):
 
     for policy in POLICIES:
         want = accept & pm.holds_batch(policy, sig, pk)
-        with settings(engine, policy):
+        with settings(engine, policy=policy):
             assert not names(engine.ed25519_verify_batch(sig, pk, flat, msg_off=off), want), (hex(policy), "host")
             got = engine.ed25519_verify_batch(dev(sig), dev(pk), dev(flat), msg_off=dev(off.astype(np.int64)))
             assert not names(host(got), want), (hex(policy), "device")
@@ -106,7 +81,7 @@ def test_policy_batch_at_the_smallest_pass_that_reaches_each_writer_of_ok(engine
     sig, pk, msg, oracle_ok = (a[:n] for a in batch)
     for policy in (STRICT, BITS[case % 4]):
         want = oracle_ok & pm.holds_batch(policy, sig, pk)
-        with settings(engine, policy, algo=algo):
+        with settings(engine, policy=policy, algo=algo):
             got_h = engine.ed25519_verify_batch(sig, pk, msg, msg_len=MLEN)
             got_d = host(engine.ed25519_verify_batch(dev(sig), dev(pk), dev(msg), msg_len=MLEN))
         assert np.array_equal(got_h, want), (hex(policy), "host", np.nonzero(got_h != want)[0][:10])
@@ -156,12 +131,12 @@ def test_batch_verification_applies_the_policy_and_routes_as_before(engine, orac
     oracle_ok = oracle.verify_batch(sig, pk, msg, MLEN)
     assert oracle_ok.all()
     for put in (lambda a: a, dev):
-        with settings(engine, 0, rlc_min=0):
+        with settings(engine, policy=0, rlc_min=0):
             ok, base = engine.ed25519_verify_batch_rlc(put(sig), put(pk), put(msg), msg_len=MLEN, return_stats=True)
         assert host(ok).all() and sum(base[:2]) == n
         for policy in (STRICT, BITS[0]):
             want = pm.holds_batch(policy, sig, pk)
-            with settings(engine, policy, rlc_min=0):
+            with settings(engine, policy=policy, rlc_min=0):
                 ok, st = engine.ed25519_verify_batch_rlc(put(sig), put(pk), put(msg), msg_len=MLEN, return_stats=True)
             assert np.array_equal(host(ok), want), (hex(policy), np.nonzero(host(ok) != want)[0])
             assert st == base, (hex(policy), st, base)
@@ -185,7 +160,7 @@ def test_host_chunks_from_ordinary_memory(engine, oracle, batch):
     assert oracle_ok.all()
     want = pm.holds_batch(STRICT, bsig, bpk)[pick]
     assert np.array_equal(np.nonzero(want == 0)[0], hit)
-    with settings(engine, STRICT):
+    with settings(engine, policy=STRICT):
         got = engine.ed25519_verify_batch(sig, pk, msg, msg_len=MLEN)
     assert np.array_equal(got, want), np.nonzero(got != want)[0][:10]
 
@@ -199,7 +174,7 @@ def test_multi_device_form_and_empty_batches(engine, batch):
     sig, pk, msg, oracle_ok = (a[pick] for a in batch)
     want = oracle_ok & pm.holds_batch(STRICT, batch[0], batch[1])[pick]
     assert 0 < want.sum() < oracle_ok.sum()
-    with settings(engine, STRICT, rlc_min=0):
+    with settings(engine, policy=STRICT, rlc_min=0):
         assert np.array_equal(engine.ed25519_verify_batch_multi(sig, pk, msg, msg_len=MLEN), want)
         for fn in (engine.ed25519_verify_batch, engine.ed25519_verify_batch_rlc, engine.ed25519_verify_batch_multi):
             got = fn(sig[:0], pk[:0], msg[:0], msg_len=MLEN)

@@ -3,31 +3,17 @@ whatever route an item takes - accepted with its group by the random linear comb
 a non-canonical R, or decided by the per-item kernels after its group failed or was flagged - the verdict
 bytes must be those of the reference's per-item loop."""
 import hashlib
-import json
 import os
 
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from ed_model import L, P
+from gpu_kit import always_combine, dev  # noqa: F401  (always_combine: a fixture)
+from hostlib import ROOT
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("always_combine")]
 G = 8192
-P = 2**255 - 19
-L = 2**252 + 27742317777372353535851937790883648493
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-@pytest.fixture(autouse=True)
-def always_combine(engine):
-    """these tests drive the combination itself with small batches: switch off the routing of calls below 5 x 2^15
-    items to the per-item kernels (test_small_calls_go_to_the_per_item_kernels checks the default)"""
-    engine.set_rlc_min_items(0)
-    yield
-    engine.set_rlc_min_items(engine.RLC_MIN_ITEMS_DEFAULT)
 
 
 def _signed(engine, n, seed, mlen=32):

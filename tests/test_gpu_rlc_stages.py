@@ -2,8 +2,8 @@
 statistics counters cannot tell a seed that ignores part of the batch from one that does not, nor a window point that is wrong in
 a group that fails anyway.  So every device stage of a pass is read back (debug_rlc_snapshot: leaves, seed, t and S, flags, digit
 rows, base-point digits, window points, group verdicts) and held against a model in plain Python integers and hashlib, written
-below from the description of the combination and from nothing of the device source.  Every comparison is exact: bytes, integers
-or affine points.
+below (the curve is that of tests/ed_model.py) from the description of the combination and from nothing of the device source.
+Every comparison is exact: bytes, integers or affine points.
 
 The conventions are the ones tests/test_device_source_on_host.py pins for the per-lane code on the host:
   leaf_i = SHA-512(SHA-512(R | A | M) | S)[:32]; a tree node = SHA-512(up to 16 children)[:32]; the seed is the root;
@@ -11,72 +11,23 @@ The conventions are the ones tests/test_device_source_on_host.py pins for the pe
   the key's scalar is z t mod 8 l, centred; digits are signed bytes in [-128, 127]; the points are -A, -R and B.
 """
 import functools
-import hashlib
 
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+import ed_model as em
+from ed_model import B as BASE, D, D2, L, NEUTRAL, P, affine, ext, inv, is_neutral, padd as add, pneg as neg
+from gpu_kit import always_combine, dev  # noqa: F401  (always_combine: a fixture)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("always_combine")]
 G = 8192
-P = 2**255 - 19
-L = 2**252 + 27742317777372353535851937790883648493
-D = (-121665 * pow(121666, P - 2, P)) % P
-D2 = 2 * D % P
-SQRT_M1 = pow(2, (P - 1) // 4, P)
-SMALL_ORDER_Y = {1, P - 1, 0,
-                 int.from_bytes(bytes.fromhex("26e8958fc2b227b045c3f489f2ef98f0d5dfac05d3c63339b13802886d53fc05"), "little"),
-                 int.from_bytes(bytes.fromhex("c7176a703d4dd84fba3c0b760d10670f2a2053fa2c39ccc64ec7fd7792ac037a"), "little")}
-H = lambda b: hashlib.sha512(b).digest()  # noqa: E731
-LE = lambda b: int.from_bytes(b, "little")  # noqa: E731
-
-
-# ---------------------------------------------------------------------------------------------------------
-# the curve on Python integers: extended coordinates (X, Y, Z, T), x = X / Z, y = Y / Z, x y = T / Z
-# ---------------------------------------------------------------------------------------------------------
-NEUTRAL = (0, 1, 1, 0)
+H, LE = em.sha, em.num
 
 
 def decode(enc):
-    """(on the curve, x, y) of a 32-byte encoding, read permissively: y is taken mod p, any sign bit"""
-    v = LE(enc)
-    sign, y = v >> 255, (v & (2**255 - 1)) % P
-    u, w = (y * y - 1) % P, (D * y * y + 1) % P
-    x = u * pow(w, 3, P) * pow(u * pow(w, 7, P) % P, (P - 5) // 8, P) % P
-    if (w * x * x - u) % P:
-        x = x * SQRT_M1 % P
-    on = (w * x * x - u) % P == 0
-    if on and (x & 1) != sign:
-        x = (P - x) % P
-    return on, x, y
-
-
-def ext(x, y):
-    return (x, y, 1, x * y % P)
-
-
-def add(p, q):
-    """the unified addition of a = -1 twisted Edwards curves: complete on this curve, so p = q and p = -q need no case"""
-    x1, y1, z1, t1 = p
-    x2, y2, z2, t2 = q
-    a, b, c, d = (y1 - x1) * (y2 - x2) % P, (y1 + x1) * (y2 + x2) % P, t1 * D2 * t2 % P, 2 * z1 * z2 % P
-    e, f, g, h = b - a, d - c, d + c, b + a
-    return (e * f % P, g * h % P, f * g % P, e * h % P)
-
-
-def neg(p):
-    return ((P - p[0]) % P, p[1], p[2], (P - p[3]) % P)
-
-
-def affine(p):
-    zi = pow(p[2], P - 2, P)
-    return (p[0] * zi % P, p[1] * zi % P)
-
-
-def is_neutral(p):
-    return p[0] % P == 0 and (p[1] - p[2]) % P == 0 and p[2] % P != 0
-
-
-BASE = ext(decode((4 * pow(5, P - 2, P) % P).to_bytes(32, "little"))[1], 4 * pow(5, P - 2, P) % P)
+    """(on the curve, x, y) of a 32-byte encoding, read permissively: y is taken mod p, any sign bit; x and y None off the curve"""
+    pt = em.decode_reference(enc)
+    return (False, None, None) if pt is None else (True,) + pt
 
 
 def weighted_sum(digits, points):
@@ -144,7 +95,7 @@ class Model:
             (a_on, _, ay), (r_on, rx, ry) = self.decoded[0][i], self.decoded[1][i]
             v = LE(self.r[i])
             valid = r_on and (v & (2**255 - 1)) < P and not (rx == 0 and v >> 255)
-            per_item = (not a_on or ay in SMALL_ORDER_Y) or (valid and ry in SMALL_ORDER_Y)
+            per_item = (not a_on or ay in em.small_order_ys()) or (valid and ry in em.small_order_ys())
             out.append((1 if valid else 0) | (2 if per_item else 0))
         return out
 
@@ -179,7 +130,7 @@ class Model:
     @functools.cached_property
     def neg_points(self):
         """(-A_i, -R_i) in extended coordinates (of encodings that decode: nothing else carries a non-zero digit here)"""
-        return [[neg(ext(x, y)) if on else None for on, x, y in side] for side in self.decoded]
+        return [[neg(ext((x, y))) if on else None for on, x, y in side] for side in self.decoded]
 
     def window_point(self, g, seg):
         """window point `seg` of group g: entries 0..31 are windows 31..0 of the keys and the base point, 32..47 windows 15..0
@@ -196,8 +147,8 @@ def entry_point(entry):
     """a packed window point (Y-X | Y+X | 2dT | 2Z, 32 little-endian bytes each) as (X, Y, Z, T); it must be a curve point
     with Z != 0 and X Y = Z T"""
     ymx, ypx, t2d, z2 = (LE(entry[k].tobytes()) % P for k in range(4))
-    half = pow(2, P - 2, P)
-    x, y, z, t = (ypx - ymx) * half % P, (ypx + ymx) * half % P, z2 * half % P, t2d * pow(D2, P - 2, P) % P
+    half = inv(2)
+    x, y, z, t = (ypx - ymx) * half % P, (ypx + ymx) * half % P, z2 * half % P, t2d * inv(D2) % P
     assert z != 0 and (x * y - z * t) % P == 0
     assert (-x * x * z * z + y * y * z * z - z**4 - D * x * x * y * y) % P == 0      # -x^2 + y^2 = 1 + d x^2 y^2, projectively
     return (x, y, z, t)
@@ -219,18 +170,6 @@ def horner(points):
 # ---------------------------------------------------------------------------------------------------------
 # plumbing
 # ---------------------------------------------------------------------------------------------------------
-def dev(a):
-    import torch
-    return torch.from_numpy(np.array(a)).cuda()         # (a copy: the shared fixtures are read-only)
-
-
-@pytest.fixture(autouse=True)
-def always_combine(engine):
-    engine.set_rlc_min_items(0)
-    yield
-    engine.set_rlc_min_items(engine.RLC_MIN_ITEMS_DEFAULT)
-
-
 def sign(engine, sk, msg):
     pk = engine.ed25519_genpub_batch(dev(sk))
     return engine.ed25519_sign_batch(dev(sk), pk, dev(msg)).cpu().numpy(), pk.cpu().numpy()

@@ -11,6 +11,7 @@ import pytest
 import dom2_model as dm
 import sign_keyed_model as sm
 from gen_golden import golden_msg  # tools/ is on sys.path (conftest)
+from gpu_kit import dev
 
 pytestmark = pytest.mark.gpu
 L = sm.L
@@ -23,17 +24,8 @@ SIZES = (1, 63, 64, 65, 255, 256, 257, 1 << 14, (1 << 14) + 1, (1 << 15) + 1, (1
          131072 + 256 + 77, 262144 + 2 * 256 + 77, 131072 + 512 + 77)
 
 
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def idx_dev(idx):
     return dev(np.asarray(idx, np.uint32).view(np.int32))
-
-
-def host(x):
-    return x if isinstance(x, np.ndarray) else x.cpu().numpy()
 
 
 def ragged(rng, n, longest=300):

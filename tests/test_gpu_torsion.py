@@ -10,14 +10,10 @@ import numpy as np
 import pytest
 
 import workload
+from gpu_kit import dev
 
 pytestmark = pytest.mark.gpu
 G = 8192
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @pytest.fixture(scope="module")

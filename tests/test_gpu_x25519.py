@@ -14,16 +14,12 @@ import pytest
 
 import x25519_cases as xc
 from x25519_cases import DEGENERATE, DEGENERATE_MODEL, ORDINARY, ORDINARY_MODEL, P
+from gpu_kit import dev
 
 pytestmark = pytest.mark.gpu
 
 POOL = DEGENERATE + ORDINARY
 POOL_MODEL = DEGENERATE_MODEL + ORDINARY_MODEL
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.array(a)).cuda()                      # (a copy: the shared arrays are read-only)
 
 
 @functools.lru_cache(maxsize=None)

@@ -7,22 +7,17 @@ import ctypes
 import os
 import random
 import re
-import subprocess
 
 import pytest
 
 import keyed_comb_model as cm
 import keyed_model as km
+from ed_model import H
+from hostlib import ROOT, build_check, declared_names, exported_names, header_text
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-H = bytes.fromhex
 SZ = ctypes.c_size_t
 NAMES = ("eddsa_amd_keyset_create_comb", "eddsa_amd_keyset_create_comb_dev", "eddsa_amd_keyset_is_comb", "eddsa_amd_keyset_bytes")
 INVALID_VALUE = 1                                    # hipErrorInvalidValue
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "eddsa_amd.h")).read()
 
 
 def _cases(golden):
@@ -32,11 +27,7 @@ def _cases(golden):
 @pytest.fixture(scope="module")
 def combcheck(tmp_path_factory):
     """tests/host_check/keyed_comb_check.cpp built with the flags of the hostcheck fixture (conftest.py), outside the tree"""
-    lib = str(tmp_path_factory.mktemp("keyed_comb_check") / "libkeyedcombcheck.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-DED_HOST_CHECK", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(ROOT, "libeddsa_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_check", "keyed_comb_check.cpp"), "-o", lib])
-    h = ctypes.CDLL(lib)
+    h = build_check(tmp_path_factory, "keyed_comb")
     h.kcc_violations.restype = ctypes.c_long
     h.kcc_build.restype = ctypes.c_long
     return h
@@ -56,12 +47,11 @@ def built(combcheck, golden):
 # ---------------------------------------------------------------- the interface
 
 def test_the_header_declares_the_names_and_the_library_exports_them():
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    text = header_text(strip_comments=True)
     assert re.search(r"#define\s+EDDSA_AMD_KEYSET_COMB_MAX_KEYS\s+\(\(size_t\)1\s*<<\s*14\)", text)
-    declared = set(re.findall(r"RFC8032_EDDSA_DECL\s+[\w\s\*]+?\b(\w+)\s*\(", text))
+    declared = declared_names(text, r"RFC8032_EDDSA_DECL")
     assert set(NAMES) <= declared
-    out = subprocess.check_output(["nm", "-D", "--defined-only", os.path.join(ROOT, "libeddsa_amd", "libeddsa_amd.so")], text=True)
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
+    exported = exported_names("libeddsa_amd.so")
     assert set(NAMES) <= exported
     assert "eddsa_amd_debug_keyset_comb_read" not in exported        # the read-back hook is the debug library's alone
     debug_h = open(os.path.join(ROOT, "include", "eddsa_amd_debug.h")).read()
@@ -69,7 +59,7 @@ def test_the_header_declares_the_names_and_the_library_exports_them():
 
 
 def test_the_header_states_the_contract():
-    text = " ".join(re.sub(r"\n \*", " ", _header()).split())        # (a phrase may run over the comment's line break)
+    text = " ".join(re.sub(r"\n \*", " ", header_text()).split())        # (a phrase may run over the comment's line break)
     for phrase in ("88 KiB of HBM per key", "EDDSA_AMD_KEYSET_COMB_MAX_KEYS = 2^14 keys", "1.375 GiB", "in every mode",
                    "at every size", "S mod l", "there is no new verify entry point", "under both equations",
                    "profiles/verify_keyed_comb.txt"):

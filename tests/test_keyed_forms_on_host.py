@@ -8,16 +8,15 @@ import ctypes
 import hashlib
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import dom2_model as dm
 import keyed_model as km
+from ed_model import H
+from hostlib import ROOT, build_check, declared_names, exported_names, header_text
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-H = bytes.fromhex
 SZ = ctypes.c_size_t
 L = km.L
 NAMES = ("ed25519_verify_keyed_digests", "ed25519_verify_keyed_digests_dev", "ed25519_verify_keyed_digests_rlc",
@@ -27,31 +26,22 @@ INVALID_VALUE = 1                                    # hipErrorInvalidValue
 WINDOWED = 1                                         # kernel_io.h: VERIFY_WINDOWED
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "eddsa_amd.h")).read()
-
-
-def _exports(lib):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", os.path.join(ROOT, "libeddsa_amd", lib)], text=True)
-    return {l.split()[-1] for l in out.splitlines() if " T " in l}
-
-
 # ---------------------------------------------------------------- the interface
 
 def test_the_header_declares_the_eight_names_and_the_library_exports_them():
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    declared = set(re.findall(r"RFC8032_EDDSA_DECL\s+[\w\s\*]+?\b(\w+)\s*\(", text))
+    text = header_text(strip_comments=True)
+    declared = declared_names(text, r"RFC8032_EDDSA_DECL")
     assert set(NAMES) <= declared
-    assert set(NAMES) <= _exports("libeddsa_amd.so")
+    assert set(NAMES) <= exported_names("libeddsa_amd.so")
     # no new debug name: what the debug library exports on top of the shipped one is what its header declares
     debug_h = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "eddsa_amd_debug.h")).read(), flags=re.S)
-    extra = _exports("libeddsa_amd_debug.so") - _exports("libeddsa_amd.so")
+    extra = exported_names("libeddsa_amd_debug.so") - exported_names("libeddsa_amd.so")
     assert extra <= set(re.findall(r"\b(eddsa_amd_\w+)\s*\(", debug_h)), extra
     assert not [n for n in extra if "keyed_digests" in n or "ctx" in n or "ph_" in n]
 
 
 def test_the_header_states_the_contract():
-    text = " ".join(re.sub(r"\n \*", " ", _header()).split())
+    text = " ".join(re.sub(r"\n \*", " ", header_text()).split())
     for phrase in ("ok[i] is byte for byte what the unkeyed form of the same name returns",
                    "ed25519_verify_digests, ed25519_verify_digests_rlc, ed25519ctx_verify_batch, ed25519ph_verify_batch",
                    "over plain key sets and over comb key sets", "A comb set takes the comb route in the per-item forms",
@@ -68,7 +58,7 @@ def test_the_header_states_the_contract():
 
 
 def test_the_old_out_of_scope_sentences_stand_with_a_note_of_what_was_added():
-    text = " ".join(re.sub(r"\n \*", " ", _header()).split())
+    text = " ".join(re.sub(r"\n \*", " ", header_text()).split())
     for sentence in ("Out of scope: _rlc, _multi, records, digest, Ed25519ctx / Ed25519ph and single-item forms; tables wider than nine entries.",
                      "Still out of scope: the digest, records, _multi, Ed25519ctx / Ed25519ph and single-item forms of keyed verification.",
                      "Out of scope: four-lane forms of the comb route, combs wider than 6 bits, the digest, records, _multi and ctx / ph keyed forms."):
@@ -148,11 +138,7 @@ class Prepared(ctypes.Structure):
 @pytest.fixture(scope="module")
 def check(tmp_path_factory):
     """tests/host_check/keyed_forms_check.cpp built with the flags of the hostcheck fixture (conftest.py), outside the tree"""
-    lib = str(tmp_path_factory.mktemp("keyed_forms_check") / "libkeyedformscheck.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-DED_HOST_CHECK", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(ROOT, "libeddsa_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_check", "keyed_forms_check.cpp"), "-o", lib])
-    h = ctypes.CDLL(lib)
+    h = build_check(tmp_path_factory, "keyed_forms")
     h.kfc_violations.restype = ctypes.c_long
     return h
 

@@ -7,33 +7,25 @@ import ctypes
 import os
 import random
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import keyed_model as km
+import ed_model as em
+from ed_model import D, H, P, le
+from hostlib import ROOT, build_check, declared_names, exported_names, header_text
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-H = bytes.fromhex
 SZ = ctypes.c_size_t
 NAMES = ("eddsa_amd_keyset_create", "eddsa_amd_keyset_create_dev", "eddsa_amd_keyset_destroy", "eddsa_amd_keyset_count",
          "eddsa_amd_keyset_device", "ed25519_verify_keyed", "ed25519_verify_keyed_dev")
 INVALID_VALUE = 1                                    # hipErrorInvalidValue
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "eddsa_amd.h")).read()
-
-
 @pytest.fixture(scope="module")
 def keyedcheck(tmp_path_factory):
     """tests/host_check/keyed_check.cpp built with the flags of the hostcheck fixture (conftest.py), outside the tree"""
-    lib = str(tmp_path_factory.mktemp("keyed_check") / "libkeyedcheck.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-DED_HOST_CHECK", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(ROOT, "libeddsa_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_check", "keyed_check.cpp"), "-o", lib])
-    h = ctypes.CDLL(lib)
+    h = build_check(tmp_path_factory, "keyed")
     h.kc_violations.restype = ctypes.c_long
     h.kc_build.restype = ctypes.c_long
     return h
@@ -44,19 +36,18 @@ def keyedcheck(tmp_path_factory):
 def test_the_header_declares_the_names_and_the_library_exports_them():
     """the opaque type and the seven functions, each with RFC8032_EDDSA_DECL (the EDDSA_AMD_DECL names are counted by the tests of
     earlier additions); the shipped library exports every one of them"""
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    text = header_text(strip_comments=True)
     assert re.search(r"typedef\s+struct\s+eddsa_amd_keyset\s+eddsa_amd_keyset\s*;", text)
     assert re.search(r"#define\s+EDDSA_AMD_KEYSET_MAX_KEYS\s+\(\(size_t\)1\s*<<\s*20\)", text)
-    declared = set(re.findall(r"RFC8032_EDDSA_DECL\s+[\w\s\*]+?\b(\w+)\s*\(", text))
+    declared = declared_names(text, r"RFC8032_EDDSA_DECL")
     assert set(NAMES) <= declared
-    assert not set(NAMES) & set(re.findall(r"(?<![0-9A-Z_])EDDSA_AMD_DECL\s+[\w\s\*]+?\b(\w+)\s*\(", text))
-    out = subprocess.check_output(["nm", "-D", "--defined-only", os.path.join(ROOT, "libeddsa_amd", "libeddsa_amd.so")], text=True)
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
+    assert not set(NAMES) & declared_names(text, r"(?<![0-9A-Z_])EDDSA_AMD_DECL")
+    exported = exported_names("libeddsa_amd.so")
     assert set(NAMES) <= exported
 
 
 def test_the_header_states_the_contract():
-    text = " ".join(_header().split())
+    text = " ".join(header_text().split())
     for phrase in ("key_idx[i] >= count is rejected", "SURVIVES eddsa_amd_shutdown", "never merged by the small-call combiner",
                    "Out of scope: _rlc, _multi, records, digest", "one-lane", "profiles/verify_keyed.txt"):
         assert phrase in text, phrase
@@ -96,15 +87,13 @@ def test_the_out_of_range_key_does_not_decode(keyedcheck):
     choice, is the point (sqrt(-1), 0) of order 4, for which R = [S]B verifies under the cofactored equation"""
     out = ctypes.create_string_buffer(32)
     keyedcheck.kc_no_key(out)
-    assert out.raw == km.NO_KEY == (2).to_bytes(32, "little")
-    y = 2
-    x2 = (y * y - 1) * pow(km.D * y * y + 1, km.P - 2, km.P) % km.P
-    assert x2 == 3 * pow(4 * km.D + 1, km.P - 2, km.P) % km.P
-    assert pow(x2, (km.P - 1) // 2, km.P) == km.P - 1                  # Euler: a non-residue
+    assert out.raw == km.NO_KEY == le(2)
+    x2 = em.x_squared(2)
+    assert x2 == 3 * em.inv(4 * D + 1) % P
+    assert pow(x2, (P - 1) // 2, P) == P - 1                         # Euler: a non-residue
     assert not km.decodes(km.NO_KEY)
     assert km.decodes(bytes(32))                                     # y = 0: x^2 = -1, a point of order 4
-    x = pow(2, (km.P - 1) // 4, km.P)
-    assert (x * x + 1) % km.P == 0
+    assert (em.SQRT_M1 * em.SQRT_M1 + 1) % P == 0
 
 
 # ---------------------------------------------------------------- the lanes, from a shared table

@@ -7,32 +7,23 @@ import ctypes
 import hashlib
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-H = bytes.fromhex
+from ed_model import H, L
+from hostlib import ROOT, build_check, declared_names, exported_names, header_text
+
 SZ = ctypes.c_size_t
-L = 2**252 + 27742317777372353535851937790883648493
 N8L = 8 * L
 NAMES = ("ed25519_verify_keyed_rlc", "ed25519_verify_keyed_rlc_dev")
 INVALID_VALUE = 1                                    # hipErrorInvalidValue
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "eddsa_amd.h")).read()
-
-
 @pytest.fixture(scope="module")
 def check(tmp_path_factory):
     """tests/host_check/keyed_rlc_check.cpp built with the flags of the hostcheck fixture (conftest.py), outside the tree"""
-    lib = str(tmp_path_factory.mktemp("keyed_rlc_check") / "libkeyedrlccheck.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-DED_HOST_CHECK", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(ROOT, "libeddsa_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_check", "keyed_rlc_check.cpp"), "-o", lib])
-    h = ctypes.CDLL(lib)
+    h = build_check(tmp_path_factory, "keyed_rlc")
     h.krc_violations.restype = ctypes.c_long
     return h
 
@@ -40,15 +31,14 @@ def check(tmp_path_factory):
 # ---------------------------------------------------------------- the interface
 
 def test_the_header_declares_the_two_names_and_the_library_exports_them():
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    declared = set(re.findall(r"RFC8032_EDDSA_DECL\s+[\w\s\*]+?\b(\w+)\s*\(", text))
+    text = header_text(strip_comments=True)
+    declared = declared_names(text, r"RFC8032_EDDSA_DECL")
     assert set(NAMES) <= declared
-    out = subprocess.check_output(["nm", "-D", "--defined-only", os.path.join(ROOT, "libeddsa_amd", "libeddsa_amd.so")], text=True)
-    assert set(NAMES) <= {l.split()[-1] for l in out.splitlines() if " T " in l}
+    assert set(NAMES) <= exported_names("libeddsa_amd.so")
 
 
 def test_the_header_states_the_contract():
-    text = " ".join(_header().split())
+    text = " ".join(header_text().split())
     for phrase in ("key_idx[i] >= count gets ok[i] = 0 under every setting", "it contributes to no sum",
                    "does not send its group to the per-item kernels", "more than 8192 keys is not combined",
                    "eddsa_amd_set_rlc_min_items", "64 bytes per item of workspace capacity", "profiles/verify_keyed_rlc.txt",

@@ -6,9 +6,8 @@ import hashlib
 
 import numpy as np
 
+from ed_model import H, P, inv, le, num
 from gen_golden import golden_msg  # tools/ is on sys.path (conftest)
-
-H = bytes.fromhex
 
 
 def _call(oracle, name, out_len, *ins):
@@ -75,14 +74,11 @@ def test_comb_table_points(oracle, golden):
     pts = golden("comb_points.bin")
     tab = ctypes.create_string_buffer(32 * 8 * 96)
     oracle.lib.orc_ed_lookup_bytes(tab)
-    p = 2**255 - 19
-    inv2 = pow(2, p - 2, p)
+    inv2 = inv(2)
     for e in range(256):
-        ymx = int.from_bytes(tab.raw[96 * e:96 * e + 32], "little")
-        ypx = int.from_bytes(tab.raw[96 * e + 32:96 * e + 64], "little")
-        y, x = (ypx + ymx) * inv2 % p, (ypx - ymx) * inv2 % p
-        enc = (y | (x & 1) << 255).to_bytes(32, "little")
-        assert enc == pts[32 * e:32 * e + 32], e
+        ymx, ypx = num(tab.raw[96 * e:96 * e + 32]), num(tab.raw[96 * e + 32:96 * e + 64])
+        y, x = (ypx + ymx) * inv2 % P, (ypx - ymx) * inv2 % P
+        assert le(y | (x & 1) << 255) == pts[32 * e:32 * e + 32], e
 
 
 def test_batch_digest_small(oracle, golden):

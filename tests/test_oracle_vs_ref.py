@@ -5,8 +5,7 @@ import ctypes
 
 import numpy as np
 
-L = 2**252 + 27742317777372353535851937790883648493
-P = 2**255 - 19
+from ed_model import L, P
 
 
 class Ed(ctypes.Structure):

@@ -7,15 +7,14 @@ import itertools
 import os
 import random
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import policy_model as pm
+from hostlib import ROOT, build_check, declared_names, header_text
 from policy_model import BITS, L, P, POLICIES, STRICT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MACROS = {"EDDSA_AMD_VERIFY_S_BELOW_L": 0x100, "EDDSA_AMD_VERIFY_A_CANONICAL": 0x200, "EDDSA_AMD_VERIFY_A_NOT_SMALL": 0x400,
           "EDDSA_AMD_VERIFY_R_NOT_SMALL": 0x800, "EDDSA_AMD_VERIFY_STRICT": 0xF00, "EDDSA_AMD_VERIFY_POLICY_MASK": 0xF00}
 
@@ -23,11 +22,7 @@ MACROS = {"EDDSA_AMD_VERIFY_S_BELOW_L": 0x100, "EDDSA_AMD_VERIFY_A_CANONICAL": 0
 @pytest.fixture(scope="module")
 def policycheck(tmp_path_factory):
     """tests/host_check/policy_check.cpp built with the flags of the hostcheck fixture (conftest.py), outside the tree"""
-    lib = str(tmp_path_factory.mktemp("policy_check") / "libpolicycheck.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-DED_HOST_CHECK", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(ROOT, "libeddsa_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_check", "policy_check.cpp"), "-o", lib])
-    h = ctypes.CDLL(lib)
+    h = build_check(tmp_path_factory, "policy")
     h.pc_violations.restype = ctypes.c_long
     return h
 
@@ -156,12 +151,11 @@ def test_the_two_setters_compose(stub):
 
 
 def test_the_header_defines_the_six_macros_and_declares_no_new_function():
-    text = open(os.path.join(ROOT, "include", "eddsa_amd.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text, code = header_text(), header_text(strip_comments=True)
     defined = {name: int(value, 0) for name, value in re.findall(r"#define\s+(EDDSA_AMD_VERIFY_\w+)\s+(\w+)", code)}
     assert defined == MACROS
     assert STRICT == sum(BITS) == MACROS["EDDSA_AMD_VERIFY_POLICY_MASK"]
-    declared = set(re.findall(r"EDDSA_AMD_DECL\s+[\w\s\*]+?\b(\w+)\s*\(", code))
+    declared = declared_names(code, r"EDDSA_AMD_DECL")
     assert len(declared) == 39 and not [name for name in declared if "policy" in name.lower() or "strict" in name.lower()]
     kernels = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "libeddsa_amd", "csrc", "eddsa_kernels.h")).read(), flags=re.S)
     edk = set(re.findall(r"\b(edk_\w+)\s*\(", kernels))

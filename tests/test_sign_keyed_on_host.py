@@ -13,8 +13,8 @@ import pytest
 
 import dom2_model as dm
 import sign_keyed_model as sm
+from hostlib import ROOT, build_check, declared_names, exported_names, header_text
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SZ = ctypes.c_size_t
 L = sm.L
 NAMES = ("eddsa_amd_signer_create", "eddsa_amd_signer_create_expanded", "eddsa_amd_signer_destroy", "eddsa_amd_signer_count",
@@ -23,33 +23,24 @@ NAMES = ("eddsa_amd_signer_create", "eddsa_amd_signer_create_expanded", "eddsa_a
 INVALID_VALUE = 1                                    # hipErrorInvalidValue
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "eddsa_amd.h")).read()
-
-
-def _exports(lib):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", os.path.join(ROOT, "libeddsa_amd", lib)], text=True)
-    return {l.split()[-1] for l in out.splitlines() if " T " in l}
-
-
 # ---------------------------------------------------------------- the interface
 
 def test_the_header_declares_the_twelve_names_and_the_library_exports_them():
     assert len(set(NAMES)) == 12
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    declared = set(re.findall(r"RFC8032_EDDSA_DECL\s+[\w\s\*]+?\b(\w+)\s*\(", text))
+    text = header_text(strip_comments=True)
+    declared = declared_names(text, r"RFC8032_EDDSA_DECL")
     assert set(NAMES) <= declared
-    assert set(NAMES) <= _exports("libeddsa_amd.so")
+    assert set(NAMES) <= exported_names("libeddsa_amd.so")
     assert "typedef struct eddsa_amd_signer eddsa_amd_signer;" in text and "#define EDDSA_AMD_SIGNER_MAX_KEYS ((size_t)1 << 20)" in text
     # no new debug name: what the debug library exports on top of the shipped one is what its header declares
     debug_h = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "eddsa_amd_debug.h")).read(), flags=re.S)
-    extra = _exports("libeddsa_amd_debug.so") - _exports("libeddsa_amd.so")
+    extra = exported_names("libeddsa_amd_debug.so") - exported_names("libeddsa_amd.so")
     assert extra <= set(re.findall(r"\b(eddsa_amd_\w+)\s*\(", debug_h)), extra
     assert not [n for n in extra if "signer" in n or "sign_keyed" in n]
 
 
 def test_the_header_states_the_contract():
-    text = " ".join(re.sub(r"\n \*", " ", _header()).split())
+    text = " ".join(re.sub(r"\n \*", " ", header_text()).split())
     for phrase in ("the scalar a mod l (32 bytes), the prefix (32 bytes) and the public key A = (a mod l) B encoded (32 bytes) - 96 bytes per key",
                    "h = SHA-512(seed), a = h[0..32) clamped, prefix = h[32..64)",
                    "sigs[i] is byte for byte what ed25519_sign_batch writes for (secs[key_idx[i]], its public key, message i)",
@@ -172,11 +163,7 @@ def test_without_the_hip_translation_unit_creating_a_signer_is_not_supported(tmp
 @pytest.fixture(scope="module")
 def check(tmp_path_factory):
     """tests/host_check/signer_check.cpp built with the flags of the hostcheck fixture (conftest.py), outside the tree"""
-    lib = str(tmp_path_factory.mktemp("signer_check") / "libsignercheck.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-DED_HOST_CHECK", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(ROOT, "libeddsa_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_check", "signer_check.cpp"), "-o", lib])
-    h = ctypes.CDLL(lib)
+    h = build_check(tmp_path_factory, "signer")
     h.sgc_violations.restype = ctypes.c_long
     return h
 
