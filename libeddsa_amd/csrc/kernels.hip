@@ -436,13 +436,28 @@ k_verify_exact_lane_chain(uint8_t* ok, const uint8_t* sigs, size_t sig_stride, c
   }
 }
 
+// where a lane of the one-lane main kernels works: its block's tile, its slot i of the workspace (< the capacity) and, in a keyed
+// pass (keyed_kernels.h), the item's key - key 0 for a slot past the pass and for an index that names no key
+struct main_pos { size_t tile, i; uint32_t key; };
+template <bool KEYED = false>
+ED_DEV main_pos main_at(const uint32_t* key_idx = nullptr, uint32_t count = 0, size_t n = 0) {
+  main_pos p;
+  p.tile = blockIdx.x;
+  p.i = p.tile * BLOCK + threadIdx.x;
+  p.key = 0;
+  if constexpr (KEYED) {
+    p.key = p.i < n ? key_idx[p.i] : 0u;
+    p.key = p.key < count ? p.key : 0u;
+  }
+  return p;
+}
+
 __global__ void __launch_bounds__(BLOCK, 4)
 k_verify_main(const uint32_t* digits, const uint32_t* table, const uint32_t* base16, uint32_t* accout) {
-  const size_t tile = blockIdx.x;
-  const size_t i = tile * BLOCK + threadIdx.x;   // < workspace capacity
+  const main_pos p = main_at();
   ge acc;
-  verify_main_lane(acc, digits + digit_slot(i), table + table_slot(i), base16);
-  acc_put_xyz(acc_column(accout, tile, threadIdx.x), acc);
+  verify_main_lane(acc, digits + digit_slot(p.i), table + table_slot(p.i), base16);
+  acc_put_xyz(acc_column(accout, p.tile, threadIdx.x), acc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -490,6 +505,21 @@ constexpr unsigned MAIN_LDS_RESERVE = 74 * 1024;   // (2 x 74 of the CU's 160 KB
 // (measured and dropped: three blocks of 128 lanes with 50 KB each, 1.5 waves per SIMD - a resident set of 226 MB, which fits the
 // 256 MB Infinity Cache: profiles/r03_verify_ab.txt)
 constexpr int MAIN_HALF_BLOCK = BLOCK, MAIN_HALF_BLOCKS_PER_CU = 2;
+// The lane's digit words go to LDS once (word w of lane t at [w][t]: no bank conflicts); returns the lane's column.  Read from
+// memory window by window they were the hottest lines of L2 - one per resident item, 16 MB of its 32 - and L2 is what the table
+// lines need: its hits are worth 12 % to k_verify_main_half (profiles/r04_main_half_loads_ab.txt), and with the digits out of it
+// the pass gained 1.5 %.  (The launch reserves MAIN_LDS_RESERVE bytes per block anyway; this uses 28 KB of them.)
+ED_DEV const uint32_t* stage_digit_words(const uint32_t* hd) {
+  extern __shared__ uint32_t digit_words[];
+  const uint4* g = reinterpret_cast<const uint4*>(hd);
+#pragma unroll
+  for (int q = 0; q < HALF_DIGIT_WORDS / 4; q++) {
+    const uint4 v = g[q];
+    digit_words[(4 * q) * MAIN_HALF_BLOCK + threadIdx.x] = v.x; digit_words[(4 * q + 1) * MAIN_HALF_BLOCK + threadIdx.x] = v.y;
+    digit_words[(4 * q + 2) * MAIN_HALF_BLOCK + threadIdx.x] = v.z; digit_words[(4 * q + 3) * MAIN_HALF_BLOCK + threadIdx.x] = v.w;
+  }
+  return digit_words + threadIdx.x;
+}
 // WITH_LONG: after k_verify_prepare_pair (mid-size passes), which leaves the items without a short pair to this kernel:
 // the wave of such an item (2 in 10^7 with the wide search) runs the long loop
 template <int WINDOWS, bool WITH_LONG = false>
@@ -500,22 +530,7 @@ k_verify_main_half(uint8_t* ok, const uint32_t* hdigits, const uint32_t* table, 
   const size_t slot = (size_t)blockIdx.x * MAIN_HALF_BLOCK + threadIdx.x;
   if (slot >= (size_t)offcount[EDK_ONLIST_WORD]) return;
   const size_t i = onlist[slot];
-  const uint32_t* hd = hdigits + hdigit_slot(i);
-  // The lane's digit words go to LDS once (word w of lane t at [w][t]: no bank conflicts).  Read from memory window by
-  // window they were the hottest lines of L2 - one per resident item, 16 MB of its 32 - and L2 is what the table lines
-  // need: its hits are worth 12 % to this kernel (profiles/r04_main_half_loads_ab.txt), and with the digits out of it the
-  // pass gained 1.5 %.  (The launch reserves MAIN_LDS_RESERVE bytes per block anyway; this uses 28 KB of them.)
-  extern __shared__ uint32_t digit_words[];
-  {
-    const uint4* g = reinterpret_cast<const uint4*>(hd);
-#pragma unroll
-    for (int q = 0; q < HALF_DIGIT_WORDS / 4; q++) {
-      const uint4 v = g[q];
-      digit_words[(4 * q) * MAIN_HALF_BLOCK + threadIdx.x] = v.x; digit_words[(4 * q + 1) * MAIN_HALF_BLOCK + threadIdx.x] = v.y;
-      digit_words[(4 * q + 2) * MAIN_HALF_BLOCK + threadIdx.x] = v.z; digit_words[(4 * q + 3) * MAIN_HALF_BLOCK + threadIdx.x] = v.w;
-    }
-  }
-  const uint32_t* hl = digit_words + threadIdx.x;
+  const uint32_t* hl = stage_digit_words(hdigits + hdigit_slot(i));
   const bool long_loop = WITH_LONG && __any((hl[HALF_STATUS_WORD * MAIN_HALF_BLOCK] & HALF_LONG) != 0);
   // a zero digit reads item 0's entry 0 - the neutral element, like every item's own: one line for the chip, not one per item
   const bool neutral = verify_half_main_lane<WITH_LONG, WINDOWS>(hl, table + table_slot(i), rtable + table_slot(i), base16, long_loop, MAIN_HALF_BLOCK, table);
@@ -852,15 +867,19 @@ k_genpub_point(uint32_t* accout, const uint8_t* secs, size_t n, const uint32_t* 
   }
 }
 
-// Z of a comb result is never 0 (B and its multiples are curve points)
-struct encode_finish_policy {
-  uint8_t* out; uint32_t* acc; size_t n; int K;
+// the base of the policies that finish a comb result: its Z is never 0 (B and its multiples are curve points)
+struct comb_finish {
+  uint32_t* acc; size_t n; int K;
   ED_DEV void den(int k, fe& z) const {
     const finish_pos p = finish_at(k, acc, K);
     fe_set(z, 1);
     if (p.i < n) acc_load(z, p.acc, ACC_Z);
     den_commit(z, true, acc, k, K);
   }
+};
+
+struct encode_finish_policy : comb_finish {
+  uint8_t* out;
   ED_DEV void item(int k) const {
     const finish_pos p = finish_at(k, acc, K);
     if (p.i >= n) return;
@@ -874,7 +893,14 @@ struct encode_finish_policy {
 
 __global__ void __launch_bounds__(BLOCK, 2)
 k_encode_finish(uint8_t* out, uint32_t* acc, size_t n, int K) {
-  finish_batch8(encode_finish_policy{out, acc, n, K}, acc);
+  finish_batch8(encode_finish_policy{{acc, n, K}, out}, acc);
+}
+
+// a | r of a position, the secret scalars of its item, wait in the position's slot of aux between the kernels of a sign pass
+constexpr int AUX_WORDS = 16;
+ED_DEV void aux_store(uint32_t* aux, size_t pos, const uint32_t aw[8], const uint32_t rw[8]) {
+  store8(aux + AUX_WORDS * pos, aw);
+  store8(aux + AUX_WORDS * pos + 8, rw);
 }
 
 template <int PARTS>
@@ -912,36 +938,54 @@ k_sign_point(uint32_t* accout, uint32_t* aux, const uint8_t* secs, const uint8_t
   }
 }
 
-struct sign_finish_policy {
-  uint8_t* sigs; uint32_t* acc; uint32_t* aux; const uint8_t* pubs; const uint8_t* msgs;
-  const uint64_t* msg_off; const uint64_t* msg_end; size_t msg_len; size_t n; int K; const uint32_t* perm;
-  ED_DEV void den(int k, fe& z) const {
-    const finish_pos p = finish_at(k, acc, K);
-    fe_set(z, 1);
-    if (p.i < n) acc_load(z, p.acc, ACC_Z);
-    den_commit(z, true, acc, k, K);
-  }
+// The finish of every sign pass: R encoded, the challenge t hashed - DOM: under the dom2 prefix staged at `dom` (Ed25519ctx /
+// Ed25519ph) - and S = r + t a.  KEYED (signer sets, signer_kernels.h): A = pubs[key_idx[item]], the set's key; an index outside
+// the set (>= count) gets 64 zero bytes (its a and r are zero, its point the neutral element).
+// Secrets: a | r are fetched only after the hash (sixteen registers less across it) and do not outlive the call in HBM: the
+// position's slot of aux is zeroed as soon as it is read.  A keyed pass wipes the position's point on top: (X : Y : Z) of R = r B
+// and the prefix products of the shared inversion determine r up to the projective factor, and a signer's workspace is the one a
+// long-lived signing process keeps.
+template <bool DOM, bool KEYED>
+struct sign_finish_policy : comb_finish {
+  uint8_t* sigs; uint32_t* aux; const uint8_t* pubs; const uint8_t* msgs;
+  const uint64_t* msg_off; const uint64_t* msg_end; size_t msg_len; const uint32_t* perm;
+  const uint32_t* dom = nullptr; uint32_t dom_len = 0;        // DOM
+  uint32_t count = 0; const uint32_t* key_idx = nullptr;      // KEYED
   ED_DEV void item(int k) const {
     const finish_pos p = finish_at(k, acc, K);
-    if (p.i >= n) return;
-    const size_t it = perm ? perm[p.i] : p.i;      // the item this position carries (k_sign_point)
     fe x, y, zinv;
-    acc_load(x, p.acc, ACC_X); acc_load(y, p.acc, ACC_Y); acc_load(zinv, p.acc, ACC_Z);
-    uint32_t Rw[8], Sw[8], pub[8];
+    if constexpr (KEYED) {                         // the position's point and prefix products are wiped once read
+      if (p.i < n) { acc_load(x, p.acc, ACC_X); acc_load(y, p.acc, ACC_Y); acc_load(zinv, p.acc, ACC_Z); }
+      uint32_t* o = acc_column(acc, p.tile, threadIdx.x);   // slots past the end hold the committed 1 (and what an idle lane of the point kernel left)
+#pragma unroll
+      for (int j = 0; j < 10; j++) { o[acc_at(ACC_X, j)] = 0; o[acc_at(ACC_Y, j)] = 0; o[acc_at(ACC_Z, j)] = 0; o[acc_at(ACC_W, j)] = 0; }
+    }
+    if (p.i >= n) return;
+    const size_t it = perm ? perm[p.i] : p.i;      // the item this position carries (the pass's scalars kernel, or k_sign_point)
+    if constexpr (!KEYED) { acc_load(x, p.acc, ACC_X); acc_load(y, p.acc, ACC_Y); acc_load(zinv, p.acc, ACC_Z); }
+    const uint32_t key = KEYED ? key_idx[it] : 0u;
+    const bool known = !KEYED || key < count;
+    uint32_t Rw[8], Sw[8], pub[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     encode_lane(Rw, x, y, zinv);
-    load32(pub, pubs, it, 32);
+    if constexpr (KEYED) { if (known) load32(pub, pubs, key, 32); }
+    else load32(pub, pubs, it, 32);
     const uint8_t* m; size_t mlen;
     msg_span(m, mlen, msgs, msg_off, msg_end, msg_len, msg_len, it);
     sc t;
-    sign_challenge_lane(t, Rw, pub, m, mlen);              // the secret scalars are fetched only after the hash
-    uint32_t aw[8], rw[8];
-    uint32_t* d = aux + 16 * p.i;
+    if constexpr (DOM) sign_dom_challenge_lane(t, dom, dom_len, Rw, pub, m, mlen);
+    else sign_challenge_lane(t, Rw, pub, m, mlen);
+    uint32_t aw[8], rw[8];                         // the secret scalars are fetched only after the hash
+    uint32_t* d = aux + AUX_WORDS * p.i;
     load8(aw, d);
     load8(rw, d + 8);
     const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the secrets do not outlive the call in HBM
     store8(d, zero);
     store8(d + 8, zero);
     sign_response_lane(Sw, t, aw, rw);
+    if constexpr (KEYED) {                         // an index outside the set: 64 zero bytes
+#pragma unroll
+      for (int j = 0; j < 8; j++) { Rw[j] = known ? Rw[j] : 0u; Sw[j] = known ? Sw[j] : 0u; }
+    }
     store32(sigs, it, 64, Rw);
     store32(sigs + 32, it, 64, Sw);
   }
@@ -950,7 +994,7 @@ struct sign_finish_policy {
 __global__ void __launch_bounds__(BLOCK, 2)
 k_sign_finish(uint8_t* sigs, uint32_t* acc, uint32_t* aux, const uint8_t* pubs, const uint8_t* msgs,
               const uint64_t* msg_off, const uint64_t* msg_end, size_t msg_len, size_t n, int K, const uint32_t* perm) {
-  finish_batch8(sign_finish_policy{sigs, acc, aux, pubs, msgs, msg_off, msg_end, msg_len, n, K, perm}, acc);
+  finish_batch8(sign_finish_policy<false, false>{{acc, n, K}, sigs, aux, pubs, msgs, msg_off, msg_end, msg_len, perm}, acc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -997,8 +1041,7 @@ k_sign_dom_scalars(uint32_t* aux, const uint8_t* secs, const uint8_t* msgs, cons
   uint32_t sk[8], aw[8], rw[8];
   load32(sk, secs, item, 32);
   sign_dom_scalars_lane(aw, rw, lds_dom, dom.len, sk, m, mlen);
-  store8(aux + 16 * g, aw);
-  store8(aux + 16 * g + 8, rw);
+  aux_store(aux, g, aw, rw);
 }
 
 // k_sign_point without its hashes: r comes from aux (k_sign_dom_scalars).  An idle lane takes the last position's r and keeps
@@ -1022,49 +1065,12 @@ k_sign_dom_point(uint32_t* accout, const uint32_t* aux, size_t n, const uint32_t
   }
 }
 
-// sign_finish_policy with the prefixed challenge
-struct sign_dom_finish_policy {
-  uint8_t* sigs; uint32_t* acc; uint32_t* aux; const uint8_t* pubs; const uint8_t* msgs;
-  const uint64_t* msg_off; const uint64_t* msg_end; size_t msg_len; size_t n; int K; const uint32_t* perm;
-  const uint32_t* dom; uint32_t dom_len;
-  ED_DEV void den(int k, fe& z) const {
-    const finish_pos p = finish_at(k, acc, K);
-    fe_set(z, 1);
-    if (p.i < n) acc_load(z, p.acc, ACC_Z);
-    den_commit(z, true, acc, k, K);
-  }
-  ED_DEV void item(int k) const {
-    const finish_pos p = finish_at(k, acc, K);
-    if (p.i >= n) return;
-    const size_t it = perm ? perm[p.i] : p.i;      // the item this position carries (k_sign_dom_scalars)
-    fe x, y, zinv;
-    acc_load(x, p.acc, ACC_X); acc_load(y, p.acc, ACC_Y); acc_load(zinv, p.acc, ACC_Z);
-    uint32_t Rw[8], Sw[8], pub[8];
-    encode_lane(Rw, x, y, zinv);
-    load32(pub, pubs, it, 32);
-    const uint8_t* m; size_t mlen;
-    msg_span(m, mlen, msgs, msg_off, msg_end, msg_len, msg_len, it);
-    sc t;
-    sign_dom_challenge_lane(t, dom, dom_len, Rw, pub, m, mlen);
-    uint32_t aw[8], rw[8];
-    uint32_t* d = aux + 16 * p.i;
-    load8(aw, d);
-    load8(rw, d + 8);
-    const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the secrets do not outlive the call in HBM
-    store8(d, zero);
-    store8(d + 8, zero);
-    sign_response_lane(Sw, t, aw, rw);
-    store32(sigs, it, 64, Rw);
-    store32(sigs + 32, it, 64, Sw);
-  }
-};
-
 __global__ void __launch_bounds__(BLOCK, 2)
 k_sign_dom_finish(uint8_t* sigs, uint32_t* acc, uint32_t* aux, const uint8_t* pubs, const uint8_t* msgs,
                   const uint64_t* msg_off, const uint64_t* msg_end, size_t msg_len, size_t n, int K, const uint32_t* perm, edk_dom dom) {
   __shared__ uint32_t lds_dom[EDK_DOM_WORDS];
   stage_dom(lds_dom, dom);
-  finish_batch8(sign_dom_finish_policy{sigs, acc, aux, pubs, msgs, msg_off, msg_end, msg_len, n, K, perm, lds_dom, dom.len}, acc);
+  finish_batch8(sign_finish_policy<true, false>{{acc, n, K}, sigs, aux, pubs, msgs, msg_off, msg_end, msg_len, perm, lds_dom, dom.len}, acc);
 }
 
 template <int PARTS>
@@ -1734,19 +1740,13 @@ hipError_t edk_sign_keyed(uint8_t* sigs, const edk_signer_set* set, const uint32
   if (const hipError_t e = msg_order(&perm, ws->perm, ws->lenbins, msg_off, msg_end, n, stream); e != hipSuccess) return e;
   static const edk_dom no_dom = {};
   const edk_dom& dom = ws->dom ? *ws->dom : no_dom;
-  if (ws->dom)
-    hipLaunchKernelGGL(k_sign_keyed_scalars<true>, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, ws->aux, set->a, set->prefix, count, key_idx, msgs,
-                       msg_off, msg_end, msg_len, n, perm, dom);
-  else
-    hipLaunchKernelGGL(k_sign_keyed_scalars<false>, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, ws->aux, set->a, set->prefix, count, key_idx, msgs,
-                       msg_off, msg_end, msg_len, n, perm, dom);
+  const auto scalars = ws->dom ? k_sign_keyed_scalars<true> : k_sign_keyed_scalars<false>;
+  const auto finish = ws->dom ? k_sign_keyed_finish<true> : k_sign_keyed_finish<false>;
+  hipLaunchKernelGGL(scalars, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, ws->aux, set->a, set->prefix, count, key_idx, msgs, msg_off, msg_end,
+                     msg_len, n, perm, dom);
   if (const hipError_t e = launch_point(k_sign_dom_point<POINT_SPLIT>, k_sign_dom_point<1>, n, ws, stream, ws->acc, (const uint32_t*)ws->aux, n, comb); e != hipSuccess) return e;
-  if (ws->dom)
-    hipLaunchKernelGGL(k_sign_keyed_finish<true>, dim3(f.grid), dim3(BLOCK), 0, stream, sigs, ws->acc, ws->aux, set->pubs, count, key_idx, msgs,
-                       msg_off, msg_end, msg_len, n, f.k, perm, dom);
-  else
-    hipLaunchKernelGGL(k_sign_keyed_finish<false>, dim3(f.grid), dim3(BLOCK), 0, stream, sigs, ws->acc, ws->aux, set->pubs, count, key_idx, msgs,
-                       msg_off, msg_end, msg_len, n, f.k, perm, dom);
+  hipLaunchKernelGGL(finish, dim3(f.grid), dim3(BLOCK), 0, stream, sigs, ws->acc, ws->aux, set->pubs, count, key_idx, msgs, msg_off, msg_end,
+                     msg_len, n, f.k, perm, dom);
   return hipGetLastError();
 }
 

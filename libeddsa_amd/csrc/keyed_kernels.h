@@ -1,5 +1,6 @@
 // keyed_kernels.h - the kernels of key-set verification (include/eddsa_amd.h: eddsa_amd_keyset, ed25519_verify_keyed*), part of
-// kernels.hip's translation unit (it uses that file's BLOCK, wave_append and launch shapes) and included by nothing else.
+// kernels.hip's translation unit (it uses that file's BLOCK, wave_append, launch shapes and the item bodies it shares with the
+// unkeyed kernels) and included by nothing else.
 //
 //   k_keyset_build           once per key set, one lane per key: the table 0..8 * (-A) and the on-curve flag (keyed_lanes.h)
 //   k_verify_prepare_keyed   k_verify_prepare with the key taken by index: no square root and no table; <true>: its digest form
@@ -160,18 +161,7 @@ k_verify_main_half_keyed(uint8_t* ok, const uint32_t* hdigits, const uint32_t* k
   const size_t slot = (size_t)blockIdx.x * MAIN_HALF_BLOCK + threadIdx.x;
   if (slot >= (size_t)offcount[EDK_ONLIST_WORD]) return;
   const size_t i = onlist[slot];
-  const uint32_t* hd = hdigits + hdigit_slot(i);
-  extern __shared__ uint32_t digit_words[];      // as in k_verify_main_half
-  {
-    const uint4* g = reinterpret_cast<const uint4*>(hd);
-#pragma unroll
-    for (int q = 0; q < HALF_DIGIT_WORDS / 4; q++) {
-      const uint4 v = g[q];
-      digit_words[(4 * q) * MAIN_HALF_BLOCK + threadIdx.x] = v.x; digit_words[(4 * q + 1) * MAIN_HALF_BLOCK + threadIdx.x] = v.y;
-      digit_words[(4 * q + 2) * MAIN_HALF_BLOCK + threadIdx.x] = v.z; digit_words[(4 * q + 3) * MAIN_HALF_BLOCK + threadIdx.x] = v.w;
-    }
-  }
-  const uint32_t* hl = digit_words + threadIdx.x;
+  const uint32_t* hl = stage_digit_words(hdigits + hdigit_slot(i));
   const bool neutral = verify_half_main_lane<false, WINDOWS>(hl, keytab + table_slot(key_idx[i]), rtable + table_slot(i), base16, false,
                                                              MAIN_HALF_BLOCK, keytab);
   half_verdict_store(ok, i, flags[i], neutral, 1);
@@ -182,13 +172,10 @@ k_verify_main_half_keyed(uint8_t* ok, const uint32_t* hdigits, const uint32_t* k
 __global__ void __launch_bounds__(BLOCK, 4)
 k_verify_main_keyed(const uint32_t* digits, const uint32_t* keytab, const uint32_t* key_idx, uint32_t count, size_t n,
                     const uint32_t* base16, uint32_t* accout) {
-  const size_t tile = blockIdx.x;
-  const size_t i = tile * BLOCK + threadIdx.x;   // < workspace capacity
-  uint32_t k = i < n ? key_idx[i] : 0u;
-  k = k < count ? k : 0u;
+  const main_pos p = main_at<true>(key_idx, count, n);
   ge acc;
-  verify_main_lane(acc, digits + digit_slot(i), keytab + table_slot(k), base16);
-  acc_put_xyz(acc_column(accout, tile, threadIdx.x), acc);
+  verify_main_lane(acc, digits + digit_slot(p.i), keytab + table_slot(p.key), base16);
+  acc_put_xyz(acc_column(accout, p.tile, threadIdx.x), acc);
 }
 
 // ---- comb key sets (eddsa_amd_keyset_create_comb; keyed_lanes.h) ----
@@ -212,17 +199,14 @@ k_keyset_comb_build(uint32_t* comb, const uint8_t* keys, size_t count) {
 __global__ void __launch_bounds__(BLOCK, 2)
 k_verify_main_comb_keyed(const uint32_t* digits, const uint32_t* keycomb, const uint32_t* keytab, const uint32_t* key_idx, uint32_t count,
                          size_t n, const uint32_t* bcomb, uint32_t* accout) {
-  const size_t tile = blockIdx.x;
-  const size_t i = tile * BLOCK + threadIdx.x;   // < workspace capacity
-  uint32_t k = i < n ? key_idx[i] : 0u;
-  k = k < count ? k : 0u;
+  const main_pos p = main_at<true>(key_idx, count, n);
   __shared__ uint32_t comb_words[2 * 9 * BLOCK];   // [t | S][word][lane]: the lane's two scalars plus the comb's offset
   uint32_t* yt = comb_words + threadIdx.x;
   uint32_t* ys = yt + 9 * BLOCK;
-  verify_comb_words_lane(yt, ys, BLOCK, digits + digit_slot(i));
+  verify_comb_words_lane(yt, ys, BLOCK, digits + digit_slot(p.i));
   ge acc;
-  verify_comb_lane(acc, yt, ys, BLOCK, keycomb + comb_slot(k), keytab + table_slot(k), bcomb);
-  acc_put_xyz(acc_column(accout, tile, threadIdx.x), acc);
+  verify_comb_lane(acc, yt, ys, BLOCK, keycomb + comb_slot(p.key), keytab + table_slot(p.key), bcomb);
+  acc_put_xyz(acc_column(accout, p.tile, threadIdx.x), acc);
 }
 
 }  // namespace ed

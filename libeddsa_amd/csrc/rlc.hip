@@ -131,32 +131,42 @@ ED_DEV void rlc_hash_store(uint32_t* ts, uint32_t* leaf, size_t i, const uint32_
 // ---------------------------------------------------------------------------------------------
 // R1: per item, t and S mod l (ed25519-sha512.c:162-172) and the item's leaf of the batch hash tree
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(RLC_BLOCK, 2)
-k_rlc_hash(edk_verify_items src, size_t n, uint32_t* ts, uint32_t* leaf, const uint32_t* perm) {
-  const size_t g = (size_t)blockIdx.x * RLC_BLOCK + threadIdx.x;
-  if (g >= n) return;
-  const size_t i = perm ? perm[g] : g;           // ragged messages: a wave hashes items of one length (edk_msg_order)
-  uint32_t rw[8], aw[8], sw[8], tw[8], lf[8];
-  load32(rw, src.sigs, i, src.sig_stride);
-  load32(aw, src.pubs, i, src.pub_stride);
+// item i with R = rw and the key bytes aw: src.pubs' in k_rlc_hash, the key set's by index in k_rlc_hash_keyed (rlc_keyed.h)
+ED_DEV void rlc_hash_item(const edk_verify_items& src, size_t i, const uint32_t rw[8], const uint32_t aw[8], uint32_t* ts, uint32_t* leaf) {
+  uint32_t sw[8], tw[8], lf[8];
   load32(sw, src.sigs + 32, i, src.sig_stride);
   const uint8_t* m; size_t mlen;
   msg_span(m, mlen, src.msgs, src.msg_off, src.msg_end, src.msg_len, src.msg_stride, i);
   rlc_hash_lane(tw, sw, lf, rw, aw, src.sigs + i * src.sig_stride + 32, m, mlen);
   rlc_hash_store(ts, leaf, i, tw, sw, lf);
 }
-// the same for caller-supplied digests (ed25519_verify_digests_rlc*): item i's 64 bytes of SHA-512(R || A || M) lie in the message
-// slot of src; nothing but the leaf is hashed
+// the same for caller-supplied digests (ed25519_verify_digests_rlc*, ed25519_verify_keyed_digests_rlc*): item i's 64 bytes of
+// SHA-512(R || A || M) lie in the message slot of src; nothing but the leaf is hashed
+ED_DEV void rlc_digest_item(const uint8_t* digests, size_t digest_stride, const uint8_t* sigs, size_t sig_stride, size_t i, uint32_t* ts,
+                            uint32_t* leaf) {
+  uint32_t dw[16], sw[8], tw[8], lf[8];
+  load32(dw, digests, i, digest_stride);
+  load32(dw + 8, digests + 32, i, digest_stride);
+  load32(sw, sigs + 32, i, sig_stride);
+  rlc_digest_lane(tw, sw, lf, dw, sigs + i * sig_stride + 32);
+  rlc_hash_store(ts, leaf, i, tw, sw, lf);
+}
+
+__global__ void __launch_bounds__(RLC_BLOCK, 2)
+k_rlc_hash(edk_verify_items src, size_t n, uint32_t* ts, uint32_t* leaf, const uint32_t* perm) {
+  const size_t g = (size_t)blockIdx.x * RLC_BLOCK + threadIdx.x;
+  if (g >= n) return;
+  const size_t i = perm ? perm[g] : g;           // ragged messages: a wave hashes items of one length (edk_msg_order)
+  uint32_t rw[8], aw[8];
+  load32(rw, src.sigs, i, src.sig_stride);
+  load32(aw, src.pubs, i, src.pub_stride);
+  rlc_hash_item(src, i, rw, aw, ts, leaf);
+}
 __global__ void __launch_bounds__(RLC_BLOCK, 2)
 k_rlc_hash_digest(edk_verify_items src, size_t n, uint32_t* ts, uint32_t* leaf) {
   const size_t i = (size_t)blockIdx.x * RLC_BLOCK + threadIdx.x;
   if (i >= n) return;
-  uint32_t dw[16], sw[8], tw[8], lf[8];
-  load32(dw, src.msgs, i, src.msg_stride);
-  load32(dw + 8, src.msgs + 32, i, src.msg_stride);
-  load32(sw, src.sigs + 32, i, src.sig_stride);
-  rlc_digest_lane(tw, sw, lf, dw, src.sigs + i * src.sig_stride + 32);
-  rlc_hash_store(ts, leaf, i, tw, sw, lf);
+  rlc_digest_item(src.msgs, src.msg_stride, src.sigs, src.sig_stride, i, ts, leaf);
 }
 
 // R2: one level of the hash tree: node j = SHA-512(children 16 j .. 16 j + 15)[0..32).  (A lane hashes its children's 512 bytes
@@ -181,6 +191,12 @@ k_rlc_tree(const uint32_t* in, uint32_t* out, size_t count) {
 // COFACTORED (the launcher's choice, src.equation; the arguments are the same): an R that is no canonical encoding is not
 // rejected through RLC_R_VALID but sends its group to the per-item kernels like a point of small order - the cofactored
 // equation accepts every encoding that decodes, and those kernels decide it (kernels.hip: k_cofactor_*)
+// the tail of the points kernels: the item's flags, and its group's routing flag when the item asks for the per-item kernels
+ED_DEV void rlc_route(uint8_t fl, size_t i, uint8_t* flags, uint32_t* gflags) {
+  flags[i] = fl;
+  if (fl & RLC_PER_ITEM) atomicOr(gflags + RLC_GROUP_WORDS * (i / RLC_G), 1u);
+}
+
 template <bool COFACTORED>
 __global__ void __launch_bounds__(RLC_BLOCK, 2)
 k_rlc_points(edk_verify_items src, size_t n, uint32_t* niels_a, uint32_t* niels_r, uint8_t* flags, uint32_t* gflags) {
@@ -195,8 +211,7 @@ k_rlc_points(edk_verify_items src, size_t n, uint32_t* niels_a, uint32_t* niels_
   fl |= rlc_decode_r_lane(nl, w);
   if (COFACTORED && (fl & RLC_R_VALID) == 0) fl |= RLC_PER_ITEM;
   niels_store(niels_r + 32 * i, nl);
-  flags[i] = fl;
-  if (fl & RLC_PER_ITEM) atomicOr(gflags + RLC_GROUP_WORDS * (i / RLC_G), 1u);
+  rlc_route(fl, i, flags, gflags);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -207,10 +222,31 @@ ED_DEV void add_words9(uint32_t a[9], const uint32_t b[9]) {
 #pragma unroll
   for (int k = 0; k < 9; k++) { c += (uint64_t)a[k] + b[k]; a[k] = (uint32_t)c; c >>= 32; }
 }
+// sum of z_i S_i over the block's 256 items (zs: the lane's term, a 9-word integer; reduced mod l per group later) -> bsum[block]
+ED_DEV void block_sum9(uint32_t zs[9], uint32_t* bsum) {
+  __shared__ uint32_t red[RLC_BLOCK * 9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) red[k * RLC_BLOCK + threadIdx.x] = zs[k];
+  __syncthreads();
+  for (int stride = RLC_BLOCK / 2; stride >= 1; stride >>= 1) {
+    if ((int)threadIdx.x < stride) {
+      uint32_t o[9];
+#pragma unroll
+      for (int k = 0; k < 9; k++) o[k] = red[k * RLC_BLOCK + threadIdx.x + stride];
+      add_words9(zs, o);
+#pragma unroll
+      for (int k = 0; k < 9; k++) red[k * RLC_BLOCK + threadIdx.x] = zs[k];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) bsum[10 * (size_t)blockIdx.x + k] = zs[k];
+  }
+}
 
 __global__ void __launch_bounds__(RLC_BLOCK, 2)
 k_rlc_scalars(size_t n, const uint32_t* ts, const uint32_t* seed, const uint8_t* flags, int8_t* dig, uint32_t* bsum) {
-  __shared__ uint32_t red[RLC_BLOCK * 9];
   const size_t i = (size_t)blockIdx.x * RLC_BLOCK + threadIdx.x;
   uint32_t zs[9];
 #pragma unroll
@@ -235,25 +271,7 @@ k_rlc_scalars(size_t n, const uint32_t* ts, const uint32_t* seed, const uint8_t*
       for (int wd = 0; wd < RLC_WINDOWS; wd++) d[(size_t)wd * RLC_G] = 0;
     }
   }
-  // sum of z_i S_i over the block's 256 items (a 9-word integer; reduced mod l per group later)
-#pragma unroll
-  for (int k = 0; k < 9; k++) red[k * RLC_BLOCK + threadIdx.x] = zs[k];
-  __syncthreads();
-  for (int stride = RLC_BLOCK / 2; stride >= 1; stride >>= 1) {
-    if ((int)threadIdx.x < stride) {
-      uint32_t o[9];
-#pragma unroll
-      for (int k = 0; k < 9; k++) o[k] = red[k * RLC_BLOCK + threadIdx.x + stride];
-      add_words9(zs, o);
-#pragma unroll
-      for (int k = 0; k < 9; k++) red[k * RLC_BLOCK + threadIdx.x] = zs[k];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < 9; k++) bsum[10 * (size_t)blockIdx.x + k] = zs[k];
-  }
+  block_sum9(zs, bsum);
 }
 
 // R4b: per group, s_g = sum of z_i S_i mod l and its signed byte digits (the base point's windows)

@@ -1,5 +1,6 @@
 // rlc_keyed.h - the kernels of batch verification over a key set (include/eddsa_amd.h: ed25519_verify_keyed_rlc*), part of
-// rlc.hip's translation unit (it uses that file's layout, constants and helpers) and included by nothing else.
+// rlc.hip's translation unit (it uses that file's layout, constants, helpers and the item bodies it shares with the unkeyed
+// kernels) and included by nothing else.
 //
 //   k_rlc_keys            once per pass, one lane per key of the set (at most RLC_G): -A_k as an affine niels point and the key's
 //                         routing flag - the square roots of a pass are `count`, not one per item
@@ -41,24 +42,16 @@ k_rlc_hash_keyed(edk_verify_items src, size_t n, uint32_t* ts, uint32_t* leaf, c
   const size_t g = (size_t)blockIdx.x * RLC_BLOCK + threadIdx.x;
   if (g >= n) return;
   const size_t i = perm ? perm[g] : g;
-  uint32_t rw[8], aw[8], sw[8], tw[8], lf[8];
+  uint32_t aw[8];
   const uint32_t k = key_idx[i];
   if (k < count) load32(aw, keys, k, 32); else keyed_no_key(aw);
   store32(keybytes, i, 32, aw);
-  if constexpr (DIGEST) {
-    uint32_t dw[16];
-    load32(dw, src.msgs, i, src.msg_stride);
-    load32(dw + 8, src.msgs + 32, i, src.msg_stride);
-    load32(sw, src.sigs + 32, i, src.sig_stride);
-    rlc_digest_lane(tw, sw, lf, dw, src.sigs + i * src.sig_stride + 32);
-  } else {
+  if constexpr (DIGEST) rlc_digest_item(src.msgs, src.msg_stride, src.sigs, src.sig_stride, i, ts, leaf);
+  else {
+    uint32_t rw[8];
     load32(rw, src.sigs, i, src.sig_stride);
-    load32(sw, src.sigs + 32, i, src.sig_stride);
-    const uint8_t* m; size_t mlen;
-    msg_span(m, mlen, src.msgs, src.msg_off, src.msg_end, src.msg_len, src.msg_stride, i);
-    rlc_hash_lane(tw, sw, lf, rw, aw, src.sigs + i * src.sig_stride + 32, m, mlen);
+    rlc_hash_item(src, i, rw, aw, ts, leaf);
   }
-  rlc_hash_store(ts, leaf, i, tw, sw, lf);
 }
 
 template <bool COFACTORED>
@@ -77,9 +70,8 @@ k_rlc_points_keyed(edk_verify_items src, size_t n, const uint32_t* key_idx, uint
     fl |= keyflags[k];
     if (COFACTORED && (fl & RLC_R_VALID) == 0) fl |= RLC_PER_ITEM;
   } else
-    fl = 0;
-  flags[i] = fl;
-  if (fl & RLC_PER_ITEM) atomicOr(gflags + RLC_GROUP_WORDS * (i / RLC_G), 1u);
+    fl = 0;                                      // (no key: no term, and it routes its group nowhere)
+  rlc_route(fl, i, flags, gflags);
 }
 
 // acc: `groups` x `count` accumulators of RLC_KEY_ACC_WORDS 64-bit words, zeroed on the stream at the start of the pass.  A
@@ -88,7 +80,6 @@ k_rlc_points_keyed(edk_verify_items src, size_t n, const uint32_t* key_idx, uint
 __global__ void __launch_bounds__(RLC_BLOCK, 2)
 k_rlc_scalars_keyed(size_t n, const uint32_t* ts, const uint32_t* seed, const uint8_t* flags, const uint32_t* key_idx, uint32_t count,
                     int8_t* dig, uint32_t* bsum, unsigned long long* acc) {
-  __shared__ uint32_t red[RLC_BLOCK * 9];
   const size_t i = (size_t)blockIdx.x * RLC_BLOCK + threadIdx.x;
   const size_t g = i / RLC_G;                    // (the grid covers whole groups; a block lies in one)
   uint32_t zs[9], term[8];
@@ -136,25 +127,7 @@ k_rlc_scalars_keyed(size_t n, const uint32_t* ts, const uint32_t* seed, const ui
       }
     }
   }
-  // sum of z_i S_i over the block's 256 items, as in k_rlc_scalars
-#pragma unroll
-  for (int k = 0; k < 9; k++) red[k * RLC_BLOCK + threadIdx.x] = zs[k];
-  __syncthreads();
-  for (int stride = RLC_BLOCK / 2; stride >= 1; stride >>= 1) {
-    if ((int)threadIdx.x < stride) {
-      uint32_t o[9];
-#pragma unroll
-      for (int k = 0; k < 9; k++) o[k] = red[k * RLC_BLOCK + threadIdx.x + stride];
-      add_words9(zs, o);
-#pragma unroll
-      for (int k = 0; k < 9; k++) red[k * RLC_BLOCK + threadIdx.x] = zs[k];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < 9; k++) bsum[10 * (size_t)blockIdx.x + k] = zs[k];
-  }
+  block_sum9(zs, bsum);
 }
 
 // One lane per (group, k < RLC_G): the 32 digits of key k's scalar in that group into column k of the group's -A rows; zero

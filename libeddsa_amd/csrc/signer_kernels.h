@@ -1,14 +1,14 @@
 // signer_kernels.h - the kernels of signer sets (include/eddsa_amd.h: eddsa_amd_signer, ed25519_sign_keyed*), part of kernels.hip's
-// translation unit (it uses that file's BLOCK, point_tile, stage_dom and finish_batch8) and included by nothing else.
+// translation unit (it uses that file's BLOCK, stage_dom, aux_store, sign_finish_policy and finish_batch8) and included by nothing else.
 //
 //   k_signer_build<EXPANDED>   once per signer set, one lane per key: a mod l, the prefix and the encoded A = a B (signer_lanes.h)
 //   k_sign_keyed_scalars<DOM>  one lane per position: a and the prefix by key index, r = H([dom2 ||] prefix || M') mod l; a | r go
 //                              to the position's slot of aux, the layout k_sign_dom_scalars leaves
 //   (R = r B)                  k_sign_dom_point<PARTS> through launch_point, unchanged: it takes r from aux in every shape
-//   k_sign_keyed_finish<DOM>   sign_finish_policy / sign_dom_finish_policy with A taken from the set by index
-// Kernels of their own beside the sign kernels, whose code objects stay what they were.  Against ed25519_sign_batch a keyed pass
-// hashes two SHA-512 inputs per item instead of three (no SHA-512(seed)) and reads 4 bytes of index where that reads 64 bytes of
-// keys.  Nothing here branches on, or addresses memory by, a, a prefix or r: the key index and its range check are public.
+//   k_sign_keyed_finish<DOM>   sign_finish_policy<DOM, true>: A taken from the set by index
+// Kernels of their own around the bodies of the sign kernels, whose code objects stay what they were.  Against ed25519_sign_batch a
+// keyed pass hashes two SHA-512 inputs per item instead of three (no SHA-512(seed)) and reads 4 bytes of index where that reads 64
+// bytes of keys.  Nothing here branches on, or addresses memory by, a, a prefix or r: the key index and its range check are public.
 // <DOM> selects the hash; the dom2 prefix is an argument of both instantiations (a zeroed one where it is not read), so that
 // the two share one argument list.
 #pragma once
@@ -66,59 +66,11 @@ k_sign_keyed_scalars(uint32_t* aux, const uint32_t* set_a, const uint32_t* set_p
     sign_keyed_nonce_lane<DOM>(rw, lds_dom, dom.len, pw, m, mlen);
     load8(aw, set_a + 8 * (size_t)k);            // fetched behind the hash: eight registers less across it
   }
-  store8(aux + 16 * g, aw);
-  store8(aux + 16 * g + 8, rw);
+  aux_store(aux, g, aw, rw);
 }
 
-// sign_finish_policy / sign_dom_finish_policy with A = the set's key key_idx[item].  It wipes the position's a | r like those and,
-// on top, the position's point: (X : Y : Z) of R = r B and the prefix products of the shared inversion determine r up to the
-// projective factor, and a signer's workspace is the one a long-lived signing process keeps.  An index outside the set: 64 zero
-// bytes (its a and r are zero, its point the neutral element).
-template <bool DOM>
-struct sign_keyed_finish_policy {
-  uint8_t* sigs; uint32_t* acc; uint32_t* aux; const uint8_t* set_pubs; uint32_t count; const uint32_t* key_idx; const uint8_t* msgs;
-  const uint64_t* msg_off; const uint64_t* msg_end; size_t msg_len; size_t n; int K; const uint32_t* perm;
-  const uint32_t* dom; uint32_t dom_len;
-  ED_DEV void den(int k, fe& z) const {
-    const finish_pos p = finish_at(k, acc, K);
-    fe_set(z, 1);
-    if (p.i < n) acc_load(z, p.acc, ACC_Z);
-    den_commit(z, true, acc, k, K);
-  }
-  ED_DEV void item(int k) const {
-    const finish_pos p = finish_at(k, acc, K);
-    fe x, y, zinv;
-    if (p.i < n) { acc_load(x, p.acc, ACC_X); acc_load(y, p.acc, ACC_Y); acc_load(zinv, p.acc, ACC_Z); }
-    uint32_t* o = acc_column(acc, p.tile, threadIdx.x);   // slots past the end hold the committed 1 (and what an idle lane of the point kernel left)
-#pragma unroll
-    for (int j = 0; j < 10; j++) { o[acc_at(ACC_X, j)] = 0; o[acc_at(ACC_Y, j)] = 0; o[acc_at(ACC_Z, j)] = 0; o[acc_at(ACC_W, j)] = 0; }
-    if (p.i >= n) return;
-    const size_t it = perm ? perm[p.i] : p.i;      // the item this position carries (k_sign_keyed_scalars)
-    const uint32_t key = key_idx[it];
-    const bool known = key < count;
-    uint32_t Rw[8], Sw[8], pub[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    encode_lane(Rw, x, y, zinv);
-    if (known) load32(pub, set_pubs, key, 32);
-    const uint8_t* m; size_t mlen;
-    msg_span(m, mlen, msgs, msg_off, msg_end, msg_len, msg_len, it);
-    sc t;
-    if constexpr (DOM) sign_dom_challenge_lane(t, dom, dom_len, Rw, pub, m, mlen);
-    else sign_challenge_lane(t, Rw, pub, m, mlen);          // the secret scalars are fetched only after the hash
-    uint32_t aw[8], rw[8];
-    uint32_t* d = aux + 16 * p.i;
-    load8(aw, d);
-    load8(rw, d + 8);
-    const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the secrets do not outlive the call in HBM
-    store8(d, zero);
-    store8(d + 8, zero);
-    sign_response_lane(Sw, t, aw, rw);
-#pragma unroll
-    for (int j = 0; j < 8; j++) { Rw[j] = known ? Rw[j] : 0u; Sw[j] = known ? Sw[j] : 0u; }
-    store32(sigs, it, 64, Rw);
-    store32(sigs + 32, it, 64, Sw);
-  }
-};
-
+// sign_finish_policy<DOM, true> (kernels.hip): A = the set's key key_idx[item]; it wipes the position's point beside its a | r, and an
+// index outside the set gets 64 zero bytes.
 template <bool DOM>
 __global__ void __launch_bounds__(BLOCK, 2)
 k_sign_keyed_finish(uint8_t* sigs, uint32_t* acc, uint32_t* aux, const uint8_t* set_pubs, uint32_t count, const uint32_t* key_idx,
@@ -126,8 +78,8 @@ k_sign_keyed_finish(uint8_t* sigs, uint32_t* acc, uint32_t* aux, const uint8_t* 
                     edk_dom dom) {
   __shared__ uint32_t lds_dom[DOM ? EDK_DOM_WORDS : 1];
   if constexpr (DOM) stage_dom(lds_dom, dom);
-  finish_batch8(sign_keyed_finish_policy<DOM>{sigs, acc, aux, set_pubs, count, key_idx, msgs, msg_off, msg_end, msg_len, n, K, perm, lds_dom,
-                                              dom.len}, acc);
+  finish_batch8(sign_finish_policy<DOM, true>{{acc, n, K}, sigs, aux, set_pubs, msgs, msg_off, msg_end, msg_len, perm, lds_dom, dom.len,
+                                              count, key_idx}, acc);
 }
 
 }  // namespace ed
