@@ -1,12 +1,8 @@
 #!/usr/bin/env python3
 """Device-resident rate of every batched entry point at 2^20 items (kernel-only view, torch stream)."""
-import os, sys, time
 import torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
-import libeddsa_amd as ed, workload
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
-ed.init(0)
+import rate_kit, workload
+ed = rate_kit.bind()
 n = 1 << 20
 d = lambda a: torch.from_numpy(a).cuda()
 sk, msg = workload.sign_inputs(n)
@@ -24,9 +20,5 @@ ops = {
     "sk_ed25519_to_x25519_batch": lambda: ed.sk_ed25519_to_x25519_batch(sk),
 }
 for name, f in ops.items():
-    f(); f(); torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(10): f()
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / 10
+    dt = rate_kit.steady(f, warm=2, iters=10) / 1e3
     print(f"{name:32s} {dt*1e3:8.3f} ms  {n/dt/1e6:9.1f} M/s")

@@ -1,13 +1,10 @@
 #!/usr/bin/env python3
 """What does chunking alone cost?  The config-2 batch, resident in HBM, verified (a) in one call, (b) in the host
 pipeline's chunk schedule on three streams side by side, (c) the same in stream order - no copies anywhere."""
-import os, sys, time
+import time
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
-import libeddsa_amd as ed, workload
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
-ed.init(0)
+import rate_kit, workload
+ed = rate_kit.bind()
 n = 1 << 20
 sk, msg = workload.sign_inputs(n, seed=1, config=2)
 d = lambda a: torch.from_numpy(a).cuda()

@@ -21,24 +21,18 @@ bad 11.87 ms (+25 %), all bad 22.20 ms (+134 %); rlc 4.38 -> 4.40 ms (+0.4 %); e
 against 9.48-9.49 ms.  The 1 % row shows the one-lane evaluation dominating a short list: 1.3 ms for 10 486 items, the latency of
 one chain; a four-lane form for short lists is a follow-up.
 """
-import os
 import sys
 
-import torch
+import torch  # noqa: F401  (loaded before the library, as in every script that uses it)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
-import libeddsa_amd as ed  # noqa: E402
+import rate_kit
 
-REPEATS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-LOG_N = int(sys.argv[2]) if len(sys.argv) > 2 else 20
-BASELINE = len(sys.argv) > 3 and sys.argv[3] == "baseline"
-assert REPEATS >= 3
-ed.init(0)
+REPEATS, LOG_N, _, FLAGS = rate_kit.cli(sys.argv[1:])
+BASELINE = "baseline" in FLAGS
+ed = rate_kit.bind(debug=False)
 n = 1 << LOG_N
-g = torch.Generator(device="cuda").manual_seed(20261019)
-dsk = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device="cuda", generator=g)
-dmsg = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device="cuda", generator=g)
+rnd = rate_kit.rnd(20261019)
+dsk, dmsg = rnd(n, 32), rnd(n, 32)
 dpk = ed.ed25519_genpub_batch(dsk)
 dsig = ed.ed25519_sign_batch(dsk, dpk, dmsg, msg_len=32)
 some_bad, all_bad = dsig.clone(), dsig.clone()
@@ -55,39 +49,23 @@ if not BASELINE:
              ("eq 1, all bad", 1, verify, all_bad, 0), ("rlc, eq 0", 0, rlc, dsig, n), ("rlc, eq 1", 1, rlc, dsig, n)]
 
 
-def timed(row, iters):
-    _, equation, call, sig, _ = row
-    if not BASELINE:
-        ed.set_verify_equation(equation)
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    call(sig)                                       # untimed: the repeat starts from this row's own state
-    a.record()
-    for _ in range(iters):
-        call(sig)
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
 try:
-    iters = {}
-    for row in ROWS:                                # warm-up and the verdicts; sizes a repeat to about 0.1 s
-        if not BASELINE:
-            ed.set_verify_equation(row[1])
-        assert int(row[2](row[3]).sum()) == row[4], row[0]
-        iters[row[0]] = max(2, min(50, int(100.0 / max(timed(row, 2), 1e-3))))
-    ms = {row[0]: [] for row in ROWS}
-    for _ in range(REPEATS):
-        for row in ROWS:
-            ms[row[0]].append(timed(row, iters[row[0]]))
+    forms = {}
+    for label, equation, call, sig, accepted in ROWS:   # the verdicts; baseline never touches the switch
+        switch = None if BASELINE else (lambda equation=equation: ed.set_verify_equation(equation))
+        if switch:
+            switch()
+        assert int(call(sig).sum()) == accepted, label
+        forms[label] = (switch, lambda call=call, sig=sig: call(sig))
+    ms = rate_kit.alternate(forms, REPEATS)
 finally:
     if not BASELINE:
         ed.set_verify_equation(0)
 
 print(f"{ed.library_path()}: 2^{LOG_N} items, msg_len 32, {REPEATS} repeats")
-base = sorted(ms["equation 0"])[REPEATS // 2]
-for row in ROWS:
-    v = sorted(ms[row[0]])
+base = ms["equation 0"][REPEATS // 2]
+for row in ROWS:                                   # its own row: the kit's label width, the spread also in per cent
+    v = ms[row[0]]
     med = v[REPEATS // 2]
-    print(f"  {row[0]:14s} {med:8.3f} ms  [{v[0]:.3f} .. {v[-1]:.3f}]  spread {v[-1] - v[0]:.3f} ms ({100 * (v[-1] - v[0]) / med:.1f} %)"
+    print(f"  {row[0]:{rate_kit.LABEL_WIDTH}s} {med:8.3f} ms  [{v[0]:.3f} .. {v[-1]:.3f}]  spread {v[-1] - v[0]:.3f} ms ({100 * (v[-1] - v[0]) / med:.1f} %)"
           f"  {n / med / 1e3:7.2f} M/s  {100 * (med - base) / base:+7.2f} % against equation 0", flush=True)

@@ -1,14 +1,11 @@
 #!/usr/bin/env python3
 """Do verify passes issued by several host threads, each on its own stream, overlap on the GPU?
 Time T threads x R passes of n items against one thread doing T x R passes."""
-import os, sys, threading, time
+import threading, time
 import numpy as np
 import torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
-import libeddsa_amd as ed, workload
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
-ed.init(0)
+import rate_kit, workload
+ed = rate_kit.bind()
 R = 40
 for lg in (12, 14, 16):
     n = 1 << lg

@@ -4,7 +4,7 @@
 #   tools/ct_counters.sh <tag>  -> gpurun_out/profiles_out/<tag>_ct_counters.json   (run through gpurun)
 set -u
 TAG=${1:-r02}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=$REPO/gpurun_out/ct_$TAG
 rm -rf $OUT && mkdir -p $OUT $REPO/gpurun_out/profiles_out

@@ -9,9 +9,7 @@ import sys
 import numpy as np
 import torch
 
-sys.path.insert(0, __file__.rsplit("/", 2)[0])
-import libeddsa_amd as ed
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
+import rate_kit
 
 cls = sys.argv[1] if len(sys.argv) > 1 else "random"
 n = 1 << 16
@@ -27,7 +25,7 @@ elif cls == "mixed":
 else:
     sec = rng.integers(0, 256, (n, 32), dtype=np.uint8)
 msg = np.zeros((n, 32), np.uint8)
-ed.init(0)
+ed = rate_kit.bind()
 d_sec, d_msg = torch.from_numpy(sec).cuda(), torch.from_numpy(msg).cuda()
 for _ in range(3):
     for m in (n, 1 << 12):

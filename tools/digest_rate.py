@@ -13,21 +13,17 @@ workload's expected verdicts before anything is timed.
   tools/digest_rate.py [repeats=5] [log2 of the large batches=20]
 """
 import hashlib
-import os
 import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
-import libeddsa_amd as ed  # noqa: E402
-import workload  # noqa: E402
+import rate_kit
+import workload
+from rate_kit import alternate
 
-REPEATS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-LOG_N = int(sys.argv[2]) if len(sys.argv) > 2 else 20
-assert REPEATS >= 3
-ed.init(0)
+REPEATS, LOG_N, _, _ = rate_kit.cli(sys.argv[1:])
+ed = rate_kit.bind(debug=False)
 dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()   # noqa: E731
 
 
@@ -38,33 +34,11 @@ def digests_of(sig, pk, msgs):
     return out
 
 
-def timed(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fn()                                            # untimed: the repeat starts from this form's own state, not from its neighbour's
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def alternate(forms):
-    """forms: {label: callable} -> {label: sorted per-call ms of REPEATS repeats}, the forms taking turns"""
-    iters = {}
-    for k, fn in forms.items():                     # warm-up; sizes a repeat to about 0.1 s
-        fn(); torch.cuda.synchronize()
-        iters[k] = max(2, min(50, int(100.0 / max(timed(fn, 2), 1e-3))))
-    out = {k: [] for k in forms}
-    for _ in range(REPEATS):
-        for k, fn in forms.items():
-            out[k].append(timed(fn, iters[k]))
-    return {k: sorted(v) for k, v in out.items()}
-
-
 def show(label, n, ms):
+    """this script's own row (the kit's label width; the spread also as a share of the median, which its conditions read): returns
+    the median and the spread"""
     med = ms[len(ms) // 2]
-    print(f"  {label:44s} {med:9.3f} ms  [{ms[0]:.3f} .. {ms[-1]:.3f}]  spread {ms[-1] - ms[0]:.3f} ms ({100 * (ms[-1] - ms[0]) / med:.1f} %)"
+    print(f"  {label:{rate_kit.LABEL_WIDTH}s} {med:9.3f} ms  [{ms[0]:.3f} .. {ms[-1]:.3f}]  spread {ms[-1] - ms[0]:.3f} ms ({100 * (ms[-1] - ms[0]) / med:.1f} %)"
           f"  {n / med / 1e3:8.2f} M/s", flush=True)
     return med, ms[-1] - ms[0]
 
@@ -90,7 +64,7 @@ def fixed_row(n, mlen):
     by_dig = lambda: ed.ed25519_verify_digests(dsig, dpk, ddig)                  # noqa: E731
     assert np.array_equal(by_msg().cpu().numpy(), expect) and np.array_equal(by_dig().cpu().numpy(), expect)
     print(f"2^{LOG_N} items, config-2 mix, msg_len {mlen} ({int(expect.sum())} accepted):")
-    r = alternate({"message": by_msg, "digest": by_dig})
+    r = alternate({"message": by_msg, "digest": by_dig}, REPEATS)
     m, m_spread = show("message form", n, r["message"])
     d, _ = show("digest form", n, r["digest"])
     print(f"  digest form against message form: {100 * (d - m) / m:+.2f} %", flush=True)
@@ -136,7 +110,7 @@ for name, (dsig, blob, doff, ddig) in reversed(sets.items()):
 for name, (dsig, blob, doff, ddig) in sets.items():
     forms["digest form,  " + name] = lambda dsig=dsig, ddig=ddig: ed.ed25519_verify_digests(dsig, dpk, ddig)
 print("2^16 valid items, 32-byte messages / one message in 1024 of 1 MiB:")
-r = alternate(forms)
+r = alternate(forms, REPEATS)
 res = {k: show(k, n, v) for k, v in r.items()}
 (d0, s0), (d1, s1) = res["digest form,  all 32 B"], res["digest form,  1 in 1024 of 1 MiB"]
 print(f"  condition (the digest form's time on the two sets differs by no more than its own repeat spread, {max(s0, s1):.3f} ms): "

@@ -3,13 +3,10 @@
 memory under acquire / release): the same passes over and over - every key random, every second key random, exactly 9000 keys off
 the curve, self-check mode 2 - alone and from two host threads on two streams at once; every verdict vector must equal the first
 one (and, for mode 2, the genuine verdicts).  tools/exact_soak.py [rounds]"""
-import os, sys, threading
+import sys, threading
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
-import libeddsa_amd as ed, workload
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
-ed.init(0)
+import rate_kit, workload
+ed = rate_kit.bind()
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 n = 1 << 20
 sk, msg = workload.sign_inputs(n)

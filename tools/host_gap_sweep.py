@@ -2,14 +2,11 @@
 """Where the host-to-host verify call (2^20 items of the config-2 mix, numpy arrays in, numpy array out) loses against the
 device-resident pass: the rate by copier threads, by first chunk, and from page-locked caller memory (no staging copy).
 tools/host_gap_sweep.py  ->  profiles/r06_host_gap.txt"""
-import os, sys, time, ctypes
+import time, ctypes
 import numpy as np
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch
-import libeddsa_amd as ed, workload
-ed.use_debug_library()
-ed.init(0)
+import rate_kit, workload
+ed = rate_kit.bind()
 n = 1 << 20
 sk, msg = workload.sign_inputs(n, seed=1, config=2)
 pk = ed.ed25519_genpub_batch(sk); sig = ed.ed25519_sign_batch(sk, pk, msg)

@@ -3,16 +3,12 @@
 buffer, 2^20 items: from ordinary (malloc / numpy) memory, staged by the copier pool with 0..8 helper threads, and
 from page-locked memory (eddsa_amd_host_alloc), which is used in place.  DESIGN.md quotes these; bench.py's `value`
 never includes transfers.      python tools/host_path_bench.py [log2n]"""
-import os, sys, time
+import sys, time
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch  # noqa: F401  (one HIP runtime per process: torch's)
-import libeddsa_amd as ed
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
-import workload
+import rate_kit, workload
 
-ed.init(0)
+ed = rate_kit.bind()
 n = 1 << (int(sys.argv[1]) if len(sys.argv) > 1 else 20)
 sk, msg = workload.sign_inputs(n, seed=1, config=2)
 pk = ed.ed25519_genpub_batch(sk)

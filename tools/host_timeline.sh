@@ -2,7 +2,7 @@
 # timeline (kernels and copies) of the LAST host-pointer call of tools/host_trace.py:
 #   tools/host_timeline.sh <verify|x25519|sign> [log2n]   -> gpurun_out/host_tl_<op>.txt
 OP=${1:-verify}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=$REPO/gpurun_out/host_tl_$OP
 rm -rf $OUT; mkdir -p $OUT

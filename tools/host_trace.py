@@ -1,15 +1,11 @@
 #!/usr/bin/env python3
 """one host-pointer call repeated, for a rocprofv3 --kernel-trace --memory-copy-trace timeline:
 host_trace.py <verify|x25519|sign> [log2n]"""
-import os, sys, time
+import sys, time
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch  # noqa: F401
-import libeddsa_amd as ed
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
-import workload
-ed.init(0)
+import rate_kit, workload
+ed = rate_kit.bind()
 op = sys.argv[1] if len(sys.argv) > 1 else "verify"
 n = 1 << (int(sys.argv[2]) if len(sys.argv) > 2 else (10 if op.endswith("1") else 20))
 sk, msg = workload.sign_inputs(n, seed=1, config=2)

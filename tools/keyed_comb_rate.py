@@ -16,83 +16,40 @@ all three passes accept every item, and the comb pass rejects items whose index 
   tools/keyed_comb_rate.py [repeats=5] [log2 of the batch=20] [--parent path/to/libeddsa_amd_debug.so]
 """
 import os
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import libeddsa_amd as ed  # noqa: E402
+import torch  # noqa: F401  (loaded before the library, as in every script that uses it)
 
-args = [a for a in sys.argv[1:] if not a.startswith("--")]
-PARENT = sys.argv[sys.argv.index("--parent") + 1] if "--parent" in sys.argv else None
-if PARENT:
-    args.remove(PARENT)
-ONLY_UNCHANGED = "--only-unchanged" in sys.argv    # (the child processes of row 5)
-REPEATS = int(args[0]) if len(args) > 0 else 5
-LOG_N = int(args[1]) if len(args) > 1 else 20
-assert REPEATS >= 3
-if not os.environ.get("EDDSA_AMD_LIBRARY"):
-    ed.use_debug_library()                         # the product's objects plus the phase timer (a --parent library is bound as given)
-import torch  # noqa: E402
+import rate_kit
+from rate_kit import alternate
 
-ed.init(0)
-
-
-def timed(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fn()
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def alternate(forms, repeats=REPEATS):
-    iters = {}
-    for k, fn in forms.items():
-        fn(); torch.cuda.synchronize()
-        iters[k] = max(2, min(50, int(100.0 / max(timed(fn, 2), 1e-3))))
-    out = {k: [] for k in forms}
-    for _ in range(repeats):
-        for k, fn in forms.items():
-            out[k].append(timed(fn, iters[k]))
-    return {k: sorted(v) for k, v in out.items()}
+REPEATS, LOG_N, PARENT, FLAGS = rate_kit.cli(sys.argv[1:])
+ed = rate_kit.bind()                               # the product's objects plus the phase timer (a --parent library is bound as given)
 
 
 def show(label, n, ms, base=None, against="the plain key set"):
-    med = ms[len(ms) // 2]
-    rel = "" if base is None else f"  {100 * (med - base) / base:+6.2f} % against {against}"
-    print(f"  {label:46s} {med:9.3f} ms  [{ms[0]:.3f} .. {ms[-1]:.3f}]  spread {ms[-1] - ms[0]:.3f} ms  {n / med / 1e3:8.2f} M/s{rel}", flush=True)
-    return med
+    return rate_kit.show(label, n, ms, base, against)
 
 
 n = 1 << LOG_N
-g = torch.Generator(device="cuda").manual_seed(216)
-rnd = lambda *shape: torch.randint(0, 256, shape, dtype=torch.uint8, device="cuda", generator=g)   # noqa: E731
+rnd = rate_kit.rnd(216)
 MAX_KEYS = min(ed.KEYSET_COMB_MAX_KEYS, n) if hasattr(ed, "KEYSET_COMB_MAX_KEYS") else 1024
 sk_all, msg = rnd(MAX_KEYS, 32), rnd(n, 32)
 pk_all = ed.ed25519_genpub_batch(sk_all)
 
 
 def items(nkeys):
-    """the batch with its keys drawn from the first nkeys: item i under key (i * 2654435761) mod nkeys"""
-    who = (torch.arange(n, device="cuda", dtype=torch.int64) * 2654435761) % nkeys
-    sk, pk = sk_all[who].contiguous(), pk_all[who].contiguous()
-    sig = ed.ed25519_sign_batch(sk, pk, msg, msg_len=32)
-    return sig, pk, who.to(torch.int32).contiguous()
+    return rate_kit.keyed_items(n, nkeys, sk_all, pk_all, msg)
 
 
-if ONLY_UNCHANGED:
+if rate_kit.CHILD_FLAG in FLAGS:                    # (the child processes of row 5)
     sig, pk, idx = items(1024)
     with ed.keyset_create(pk_all[:1024].contiguous()) as ks:
-        forms = {"u": lambda: ed.ed25519_verify_batch(sig, pk, msg, msg_len=32), "k": lambda: ed.ed25519_verify_keyed(sig, ks, idx, msg, msg_len=32)}
-        assert bool(forms["u"]().all()) and bool(forms["k"]().all())
-        r = alternate(forms, 3)
-    print("UNKEYED", " ".join(f"{x:.4f}" for x in r["u"]))
-    print("KEYED", " ".join(f"{x:.4f}" for x in r["k"]))
+        forms = {"UNKEYED": lambda: ed.ed25519_verify_batch(sig, pk, msg, msg_len=32),
+                 "KEYED": lambda: ed.ed25519_verify_keyed(sig, ks, idx, msg, msg_len=32)}
+        assert all(bool(fn().all()) for fn in forms.values())
+        rate_kit.emit(alternate(forms, 3))
     sys.exit(0)
 
 
@@ -115,21 +72,13 @@ for nkeys in (1, 1024, MAX_KEYS):
             assert all(bool(fn().all()) for fn in forms.values())
             if nkeys > 1:
                 assert not bool(ed.ed25519_verify_keyed(sig[:4096], comb, ((idx[:4096] + 1) % nkeys).contiguous(), msg[:4096], msg_len=32).any())
-            r = alternate(forms)
+            r = alternate(forms, REPEATS)
             print(f"  {label}:")
             u = show("ed25519_verify_batch_dev", n, r["unkeyed"])
             p = show("ed25519_verify_keyed_dev, plain key set", n, r["plain"], u, "the unkeyed pass")
             show("ed25519_verify_keyed_dev, comb key set", n, r["comb"], p)
             if nkeys == 1024 and label.startswith("mode 1"):
-                print("  per kernel (ms): prepare (+ tables, halve) / main / finish")
-                for k, fn in forms.items():
-                    ed.set_profiling(True)
-                    for _ in range(10):
-                        fn()
-                    torch.cuda.synchronize()
-                    ph = ed.verify_phase_ms()
-                    ed.set_profiling(False)
-                    print(f"    {k:8s} {ph[0]:.3f} / {ph[1]:.3f} / {ph[2]:.3f}")
+                rate_kit.phase_split(forms)
         finally:
             ed.set_verify_equation(False)
             ed.set_offcurve_mode(1)
@@ -146,7 +95,7 @@ with ed.keyset_create(pk_all[:1024].contiguous()) as plain, ed.keyset_create(pk_
         s_, p_, i_, m_ = (t[:m].contiguous() for t in (sig, pk, idx, msg))
         forms = three(s_, p_, i_, m_, plain, comb)
         assert all(bool(fn().all()) for fn in forms.values())
-        r = alternate(forms)
+        r = alternate(forms, REPEATS)
         u = show(f"{m:7d} items  unkeyed", m, r["unkeyed"])
         p = show(f"{m:7d} items  plain key set", m, r["plain"], u, "the unkeyed pass")
         show(f"{m:7d} items  comb key set", m, r["comb"], p)
@@ -167,15 +116,8 @@ for nkeys in (1024, MAX_KEYS):
 print()
 
 if PARENT:
-    print(f"the unchanged calls, this build against {os.path.relpath(PARENT, ROOT)}, fresh processes alternating (2^{LOG_N} items under 1024 keys):")
-    mine = os.path.join(ROOT, "libeddsa_amd", "libeddsa_amd_debug.so")
-    rows = {(b, f): [] for b in ("parent", "this") for f in ("UNKEYED", "KEYED")}
-    for _ in range(REPEATS):
-        for label, lib in (("parent", PARENT), ("this", mine)):
-            o = subprocess.check_output([sys.executable, os.path.abspath(__file__), "3", str(LOG_N), "--only-unchanged"],
-                                        env=dict(os.environ, EDDSA_AMD_LIBRARY=lib), text=True, timeout=300)
-            for f in ("UNKEYED", "KEYED"):
-                rows[(label, f)] += [float(x) for x in [l for l in o.splitlines() if l.startswith(f)][0].split()[1:]]
+    print(f"the unchanged calls, this build against {os.path.relpath(PARENT, rate_kit.ROOT)}, fresh processes alternating (2^{LOG_N} items under 1024 keys):")
+    rows = rate_kit.parent_ab(__file__, LOG_N, REPEATS, rate_kit.CHILD_FLAG, ("UNKEYED", "KEYED"), PARENT, rate_kit.DEBUG_LIBRARY)
     for f, name in (("UNKEYED", "ed25519_verify_batch_dev"), ("KEYED", "ed25519_verify_keyed_dev, plain key set")):
-        show(f"{name}: parent build", n, sorted(rows[("parent", f)]))
-        show(f"{name}: this build", n, sorted(rows[("this", f)]))
+        show(f"{name}: parent build", n, rows[("parent", f)])
+        show(f"{name}: this build", n, rows[("this", f)])

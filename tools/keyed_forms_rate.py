@@ -20,60 +20,18 @@ every form accepts every item.
 """
 import hashlib
 import os
-import subprocess
 import sys
 
 import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import libeddsa_amd as ed  # noqa: E402
+import rate_kit
+from rate_kit import alternate, show
 
-args = [a for a in sys.argv[1:] if not a.startswith("--")]
-PARENT = sys.argv[sys.argv.index("--parent") + 1] if "--parent" in sys.argv else None
-if PARENT:
-    args.remove(PARENT)
-ONLY_UNCHANGED = "--only-unchanged" in sys.argv    # (the child processes of row 4)
-REPEATS = int(args[0]) if len(args) > 0 else 5
-LOG_N = int(args[1]) if len(args) > 1 else 20
+REPEATS, LOG_N, PARENT, FLAGS = rate_kit.cli(sys.argv[1:])
 NKEYS = 1024
-assert REPEATS >= 3
-if not os.environ.get("EDDSA_AMD_LIBRARY"):
-    ed.use_debug_library()                         # the product's objects (a --parent library is bound as given)
-import torch  # noqa: E402
-
-ed.init(0)
+ed = rate_kit.bind()                               # the product's objects (a --parent library is bound as given)
 ed.set_rlc_min_items(0)
-
-
-def timed(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fn()
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def alternate(forms, repeats=REPEATS):
-    iters = {}
-    for k, fn in forms.items():
-        fn(); torch.cuda.synchronize()
-        iters[k] = max(2, min(50, int(100.0 / max(timed(fn, 2), 1e-3))))
-    out = {k: [] for k in forms}
-    for _ in range(repeats):
-        for k, fn in forms.items():
-            out[k].append(timed(fn, iters[k]))
-    return {k: sorted(v) for k, v in out.items()}
-
-
-def show(label, n, ms, base=None, against=""):
-    med = ms[len(ms) // 2]
-    rel = "" if base is None else f"  {100 * (med - base) / base:+6.2f} % against {against}"
-    print(f"  {label:58s} {med:9.3f} ms  [{ms[0]:.3f} .. {ms[-1]:.3f}]  spread {ms[-1] - ms[0]:.3f} ms  {n / med / 1e3:8.2f} M/s{rel}", flush=True)
-    return med
 
 
 def accepts(forms):
@@ -82,23 +40,20 @@ def accepts(forms):
 
 
 n = 1 << LOG_N
-g = torch.Generator(device="cuda").manual_seed(217)
-rnd = lambda *shape: torch.randint(0, 256, shape, dtype=torch.uint8, device="cuda", generator=g)   # noqa: E731
+rnd = rate_kit.rnd(217)
 sk_all, msg = rnd(NKEYS, 32), rnd(n, 32)
 pk_all = ed.ed25519_genpub_batch(sk_all)
-who = (torch.arange(n, device="cuda", dtype=torch.int64) * 2654435761) % NKEYS
-sk, pk, idx = sk_all[who].contiguous(), pk_all[who].contiguous(), who.to(torch.int32).contiguous()
-sig = ed.ed25519_sign_batch(sk, pk, msg, msg_len=32)
+sig, pk, idx = rate_kit.keyed_items(n, NKEYS, sk_all, pk_all, msg)
+sk = sk_all[idx.long()].contiguous()
 plain, comb = ed.keyset_create(pk_all), ed.keyset_create(pk_all, comb=True)
 
-if ONLY_UNCHANGED:
+if rate_kit.CHILD_FLAG in FLAGS:                    # (the child processes of row 4)
     forms = {"UNKEYED": lambda: ed.ed25519_verify_batch(sig, pk, msg, msg_len=32),
              "PLAIN": lambda: ed.ed25519_verify_keyed(sig, plain, idx, msg, msg_len=32),
              "COMB": lambda: ed.ed25519_verify_keyed(sig, comb, idx, msg, msg_len=32),
              "KRLC": lambda: ed.ed25519_verify_keyed_rlc(sig, plain, idx, msg, msg_len=32)}
     accepts(forms)
-    for k, v in alternate(forms, 3).items():
-        print(k, " ".join(f"{x:.4f}" for x in v))
+    rate_kit.emit(alternate(forms, 3))
     sys.exit(0)
 
 
@@ -121,7 +76,7 @@ forms = {"msg_plain": lambda: ed.ed25519_verify_keyed(sig, plain, idx, msg, msg_
          "dig_rlc": lambda: ed.ed25519_verify_keyed_digests_rlc(sig, plain, idx, dig)}
 accepts(forms)
 assert not bool(ed.ed25519_verify_keyed_digests(sig[:4096], comb, ((idx[:4096] + 1) % NKEYS).contiguous(), dig[:4096]).any())
-r = alternate(forms)
+r = alternate(forms, REPEATS)
 for kind, name in (("plain", "plain key set"), ("comb", "comb key set"), ("rlc", "the combination")):
     call = "ed25519_verify_keyed_rlc_dev" if kind == "rlc" else "ed25519_verify_keyed_dev"
     m = show(f"{call}, 32-byte messages, {name}", n, r["msg_" + kind])
@@ -147,7 +102,7 @@ forms = {"plain": lambda: ed.ed25519_verify_batch(sig, pk, msg, msg_len=32),
          "kctx_comb": lambda: ed.ed25519ctx_verify_keyed(sig_ctx, comb, idx, msg, context, msg_len=32),
          "kph_comb": lambda: ed.ed25519ph_verify_keyed(sig_ph, comb, idx, pre, context)}
 accepts(forms)
-r = alternate(forms)
+r = alternate(forms, REPEATS)
 u = show("ed25519_verify_batch_dev", n, r["plain"])
 uc = show("ed25519ctx_verify_batch_dev", n, r["ctx"], u, "plain Ed25519")
 up = show("ed25519ph_verify_batch_dev", n, r["ph"], u, "plain Ed25519")
@@ -183,28 +138,21 @@ if m3 <= n:
              "dig": lambda: ed.ed25519_verify_keyed_digests(sig3, comb, i3, dig3),
              "ph": lambda: ed.ed25519ph_verify_keyed(sig3ph, comb, i3, pre3, context)}
     accepts(forms)
-    r = alternate(forms)
+    r = alternate(forms, REPEATS)
     m = show("ed25519_verify_keyed_dev on the messages", m3, r["msg"])
     show("ed25519_verify_keyed_digests_dev on their digests", m3, r["dig"], m, "the message form")
     show("ed25519ph_verify_keyed_dev on their prehashes", m3, r["ph"], m, "the message form")
     print()
 
 if PARENT:
-    print(f"row 4: the unchanged calls, this build against {os.path.relpath(PARENT, ROOT)}, fresh processes alternating (2^{LOG_N} items under {NKEYS} keys):")
-    mine = os.path.join(ROOT, "libeddsa_amd", "libeddsa_amd_debug.so")
+    print(f"row 4: the unchanged calls, this build against {os.path.relpath(PARENT, rate_kit.ROOT)}, fresh processes alternating (2^{LOG_N} items under {NKEYS} keys):")
     names = (("UNKEYED", "ed25519_verify_batch_dev"), ("PLAIN", "ed25519_verify_keyed_dev, plain key set"),
              ("COMB", "ed25519_verify_keyed_dev, comb key set"), ("KRLC", "ed25519_verify_keyed_rlc_dev"))
-    rows = {(b, f): [] for b in ("parent", "this") for f, _ in names}
     plain.close(); comb.close()
-    for _ in range(REPEATS):
-        for label, lib in (("parent", PARENT), ("this", mine)):
-            o = subprocess.check_output([sys.executable, os.path.abspath(__file__), "3", str(LOG_N), "--only-unchanged"],
-                                        env=dict(os.environ, EDDSA_AMD_LIBRARY=lib), text=True, timeout=300)
-            for f, _ in names:
-                rows[(label, f)] += [float(x) for x in [l for l in o.splitlines() if l.startswith(f)][0].split()[1:]]
+    rows = rate_kit.parent_ab(__file__, LOG_N, REPEATS, rate_kit.CHILD_FLAG, [f for f, _ in names], PARENT, rate_kit.DEBUG_LIBRARY)
     for f, name in names:
-        p = show(f"{name}: parent build", n, sorted(rows[("parent", f)]))
-        t = sorted(rows[("this", f)])
+        p = show(f"{name}: parent build", n, rows[("parent", f)])
+        t = rows[("this", f)]
         show(f"{name}: this build", n, t, p, "the parent build")
-        lo, hi = min(rows[("parent", f)]), max(rows[("parent", f)])
+        lo, hi = rows[("parent", f)][0], rows[("parent", f)][-1]
         print(f"    this build's median is {'inside' if lo <= t[len(t) // 2] <= hi else 'OUTSIDE'} the parent build's own repeats [{lo:.3f} .. {hi:.3f}]")

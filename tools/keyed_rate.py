@@ -17,74 +17,27 @@ both passes accept every item, and the keyed pass rejects items whose index is s
   tools/keyed_rate.py [repeats=5] [log2 of the batch=20] [--parent path/to/libeddsa_amd_debug.so] [--only-small]
 """
 import os
-import subprocess
 import sys
 import time
 
 import numpy as np
+import torch  # noqa: F401  (loaded before the library, as in every script that uses it)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import libeddsa_amd as ed  # noqa: E402
+import rate_kit
+from rate_kit import alternate, show
 
-args = [a for a in sys.argv[1:] if not a.startswith("--")]
-PARENT = sys.argv[sys.argv.index("--parent") + 1] if "--parent" in sys.argv else None
-if PARENT:
-    args.remove(PARENT)
-ONLY_UNKEYED = "--only-unkeyed" in sys.argv        # (the child processes of row 6)
-REPEATS = int(args[0]) if len(args) > 0 else 5
-LOG_N = int(args[1]) if len(args) > 1 else 20
-assert REPEATS >= 3
-if not os.environ.get("EDDSA_AMD_LIBRARY"):
-    ed.use_debug_library()                         # the product's objects plus the phase timer (a --parent library is bound as given)
-import torch  # noqa: E402
-
-ed.init(0)
-
-
-def timed(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fn()
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def alternate(forms, repeats=REPEATS):
-    iters = {}
-    for k, fn in forms.items():
-        fn(); torch.cuda.synchronize()
-        iters[k] = max(2, min(50, int(100.0 / max(timed(fn, 2), 1e-3))))
-    out = {k: [] for k in forms}
-    for _ in range(repeats):
-        for k, fn in forms.items():
-            out[k].append(timed(fn, iters[k]))
-    return {k: sorted(v) for k, v in out.items()}
-
-
-def show(label, n, ms, base=None):
-    med = ms[len(ms) // 2]
-    rel = "" if base is None else f"  {100 * (med - base) / base:+6.2f} % against the unkeyed pass"
-    print(f"  {label:44s} {med:9.3f} ms  [{ms[0]:.3f} .. {ms[-1]:.3f}]  spread {ms[-1] - ms[0]:.3f} ms  {n / med / 1e3:8.2f} M/s{rel}", flush=True)
-    return med
-
+REPEATS, LOG_N, PARENT, FLAGS = rate_kit.cli(sys.argv[1:])
+ed = rate_kit.bind()                               # the product's objects plus the phase timer (a --parent library is bound as given)
+AGAINST = "the unkeyed pass"
 
 n = 1 << LOG_N
-g = torch.Generator(device="cuda").manual_seed(215)
-rnd = lambda *shape: torch.randint(0, 256, shape, dtype=torch.uint8, device="cuda", generator=g)   # noqa: E731
+rnd = rate_kit.rnd(215)
 sk_all, msg = rnd(n, 32), rnd(n, 32)
 pk_all = ed.ed25519_genpub_batch(sk_all)
 
 
 def items(nkeys):
-    """the batch with its keys drawn from the first nkeys: item i under key (i * 2654435761) mod nkeys"""
-    who = (torch.arange(n, device="cuda", dtype=torch.int64) * 2654435761) % nkeys
-    sk, pk = sk_all[who].contiguous(), pk_all[who].contiguous()
-    sig = ed.ed25519_sign_batch(sk, pk, msg, msg_len=32)
-    return sig, pk, who.to(torch.int32).contiguous()
+    return rate_kit.keyed_items(n, nkeys, sk_all, pk_all, msg)
 
 
 def small_passes():
@@ -97,21 +50,20 @@ def small_passes():
             s_, p_, i_, m_ = (t[:m].contiguous() for t in (sig, pk, idx, msg))
             forms = {"unkeyed": lambda: ed.ed25519_verify_batch(s_, p_, m_, msg_len=32), "keyed": lambda: ed.ed25519_verify_keyed(s_, ks, i_, m_, msg_len=32)}
             assert bool(forms["unkeyed"]().all()) and bool(forms["keyed"]().all())
-            r = alternate(forms)
+            r = alternate(forms, REPEATS)
             base = show(f"{m:7d} items  ed25519_verify_batch_dev", m, r["unkeyed"])
-            show(f"{m:7d} items  ed25519_verify_keyed_dev", m, r["keyed"], base)
+            show(f"{m:7d} items  ed25519_verify_keyed_dev", m, r["keyed"], base, AGAINST)
     print()
 
 
-if "--only-small" in sys.argv:
+if "--only-small" in FLAGS:
     small_passes()
     sys.exit(0)
 
-if ONLY_UNKEYED:
+if rate_kit.CHILD_FLAG in FLAGS:                    # (the child processes of row 6)
     sig, pk, _ = items(1024)
     assert bool(ed.ed25519_verify_batch(sig, pk, msg, msg_len=32).all())
-    r = alternate({"u": lambda: ed.ed25519_verify_batch(sig, pk, msg, msg_len=32)}, 3)["u"]
-    print("UNKEYED", " ".join(f"{x:.4f}" for x in r))
+    rate_kit.emit(alternate({"UNKEYED": lambda: ed.ed25519_verify_batch(sig, pk, msg, msg_len=32)}, 3))
     sys.exit(0)
 
 print(f"verify, 2^{LOG_N} valid items in HBM, 32-byte messages, device-pointer forms, the two alternating ({REPEATS} repeats):")
@@ -124,20 +76,12 @@ for nkeys in (1, 1024, 1 << 16, n):
     assert bool(forms["unkeyed"]().all()) and bool(forms["keyed"]().all())
     if nkeys > 1:
         assert not bool(ed.ed25519_verify_keyed(sig[:4096], ks, ((idx[:4096] + 1) % nkeys).contiguous(), msg[:4096], msg_len=32).any())
-    r = alternate(forms)
+    r = alternate(forms, REPEATS)
     print(f" {nkeys} distinct keys (key set: {nkeys * (32 + 1 + 1152) / 1e6:.1f} MB):")
     base = show("ed25519_verify_batch_dev", n, r["unkeyed"])
-    show("ed25519_verify_keyed_dev", n, r["keyed"], base)
+    show("ed25519_verify_keyed_dev", n, r["keyed"], base, AGAINST)
     if nkeys == 1024:
-        print("  per kernel (ms): prepare (+ tables, halve) / main / finish")
-        for k, fn in forms.items():
-            ed.set_profiling(True)
-            for _ in range(10):
-                fn()
-            torch.cuda.synchronize()
-            ph = ed.verify_phase_ms()
-            ed.set_profiling(False)
-            print(f"    {k:8s} {ph[0]:.3f} / {ph[1]:.3f} / {ph[2]:.3f}")
+        rate_kit.phase_split(forms)
         kept = (sig.cpu().numpy(), pk.cpu().numpy(), idx.cpu().numpy().view(np.uint32), msg.cpu().numpy(), pk_all[:1024].cpu().numpy())
     ks.close()
 print()
@@ -153,7 +97,7 @@ with ed.keyset_create(hk) as ks:
         for k, fn in hforms.items():
             t0 = time.perf_counter(); fn(); out[k].append(1e3 * (time.perf_counter() - t0))
     base = show("ed25519_verify_batch", n, sorted(out["unkeyed"]))
-    show("ed25519_verify_keyed", n, sorted(out["keyed"]), base)
+    show("ed25519_verify_keyed", n, sorted(out["keyed"]), base, AGAINST)
 print()
 
 print("eddsa_amd_keyset_create from host keys (upload, tables, synchronisation), ms:")
@@ -169,13 +113,7 @@ print()
 small_passes()
 
 if PARENT:
-    print(f"ed25519_verify_batch_dev, this build against {os.path.relpath(PARENT, ROOT)}, fresh processes alternating (1024 keys' items):")
-    mine = os.path.join(ROOT, "libeddsa_amd", "libeddsa_amd_debug.so")
-    rows = {"parent": [], "this": []}
-    for _ in range(REPEATS):
-        for label, lib in (("parent", PARENT), ("this", mine)):
-            o = subprocess.check_output([sys.executable, os.path.abspath(__file__), "3", str(LOG_N), "--only-unkeyed"],
-                                        env=dict(os.environ, EDDSA_AMD_LIBRARY=lib), text=True, timeout=300)
-            rows[label] += [float(x) for x in o.split("UNKEYED")[1].split()]
-    show("parent build", n, sorted(rows["parent"]))
-    show("this build", n, sorted(rows["this"]))
+    print(f"ed25519_verify_batch_dev, this build against {os.path.relpath(PARENT, rate_kit.ROOT)}, fresh processes alternating (1024 keys' items):")
+    rows = rate_kit.parent_ab(__file__, LOG_N, REPEATS, rate_kit.CHILD_FLAG, ("UNKEYED",), PARENT, rate_kit.DEBUG_LIBRARY)
+    show("parent build", n, rows[("parent", "UNKEYED")])
+    show("this build", n, rows[("this", "UNKEYED")])

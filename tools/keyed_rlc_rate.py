@@ -16,73 +16,31 @@ every form accepts every item, the combination decides all of them, and the keye
   tools/keyed_rlc_rate.py --trace keyed_rlc|rlc|keyed NKEYS    ten passes of one form, for a kernel trace (the per-kernel split)
 """
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import libeddsa_amd as ed  # noqa: E402
+import torch
 
-args = [a for a in sys.argv[1:] if not a.startswith("--")]
-PARENT = sys.argv[sys.argv.index("--parent") + 1] if "--parent" in sys.argv else None
-TRACE = sys.argv[sys.argv.index("--trace") + 1:][:2] if "--trace" in sys.argv else None
-for a in ([PARENT] if PARENT else []) + (TRACE or []):
-    args.remove(a)
-ONLY_EXISTING = "--only-existing" in sys.argv      # (the child processes of row 3)
-REPEATS = int(args[0]) if len(args) > 0 else 5
-LOG_N = int(args[1]) if len(args) > 1 else 20
-assert REPEATS >= 3
-if not os.environ.get("EDDSA_AMD_LIBRARY"):
-    ed.use_debug_library()
-import torch  # noqa: E402
+import rate_kit
+from rate_kit import alternate, show
 
-ed.init(0)
+ARGV = sys.argv[1:]
+TRACE = None
+if "--trace" in ARGV:
+    at = ARGV.index("--trace")
+    TRACE = ARGV[at + 1:at + 3]
+    del ARGV[at:at + 3]
+REPEATS, LOG_N, PARENT, FLAGS = rate_kit.cli(ARGV)
+ed = rate_kit.bind()
 ed.set_rlc_min_items(0)
 
-
-def timed(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fn()
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def alternate(forms, repeats=REPEATS):
-    iters = {}
-    for k, fn in forms.items():
-        fn(); torch.cuda.synchronize()
-        iters[k] = max(2, min(50, int(100.0 / max(timed(fn, 2), 1e-3))))
-    out = {k: [] for k in forms}
-    for _ in range(repeats):
-        for k, fn in forms.items():
-            out[k].append(timed(fn, iters[k]))
-    return {k: sorted(v) for k, v in out.items()}
-
-
-def show(label, n, ms, base=None, against=""):
-    med = ms[len(ms) // 2]
-    rel = "" if base is None else f"  {100 * (med - base) / base:+6.2f} % against {against}"
-    print(f"  {label:44s} {med:9.3f} ms  [{ms[0]:.3f} .. {ms[-1]:.3f}]  spread {ms[-1] - ms[0]:.3f} ms  {n / med / 1e3:8.2f} M/s{rel}", flush=True)
-    return med
-
-
 n = 1 << LOG_N
-g = torch.Generator(device="cuda").manual_seed(216)
-rnd = lambda *shape: torch.randint(0, 256, shape, dtype=torch.uint8, device="cuda", generator=g)   # noqa: E731
+rnd = rate_kit.rnd(216)
 sk_all, msg = rnd(8192, 32), rnd(n, 32)
 pk_all = ed.ed25519_genpub_batch(sk_all)
 
 
 def items(nkeys):
-    """the batch with its keys drawn from the first nkeys: item i under key (i * 2654435761) mod nkeys"""
-    who = (torch.arange(n, device="cuda", dtype=torch.int64) * 2654435761) % nkeys
-    sk, pk = sk_all[who].contiguous(), pk_all[who].contiguous()
-    sig = ed.ed25519_sign_batch(sk, pk, msg, msg_len=32)
-    return sig, pk, who.to(torch.int32).contiguous()
+    return rate_kit.keyed_items(n, nkeys, sk_all, pk_all, msg)
 
 
 def forms_of(ks, sig, pk, idx, m, keyed_rlc=True):
@@ -108,14 +66,12 @@ if TRACE:
     print("TRACED", TRACE[0], nkeys)
     sys.exit(0)
 
-if ONLY_EXISTING:
+if rate_kit.CHILD_FLAG in FLAGS:                    # (the child processes of row 3)
     sig, pk, idx = items(1024)
     with ed.keyset_create(pk_all[:1024].contiguous()) as ks:
         f = forms_of(ks, sig, pk, idx, msg, keyed_rlc=False)
         assert bool(f["rlc"]().all()) and bool(f["keyed"]().all())
-        r = alternate(f, 3)
-    for k in ("rlc", "keyed"):
-        print("EXISTING", k, " ".join(f"{x:.4f}" for x in r[k]))
+        rate_kit.emit(alternate(f, 3))
     sys.exit(0)
 
 print(f"2^{LOG_N} valid items in HBM, 32-byte messages, device-pointer forms, the three alternating ({REPEATS} repeats):")
@@ -128,7 +84,7 @@ for nkeys in (1, 1024, 8192):
         assert st == (n, 0, 0, (n + 8191) // 8192), st
         if nkeys > 1:
             assert not bool(ed.ed25519_verify_keyed_rlc(sig[:8192], ks, ((idx[:8192] + 1) % nkeys).contiguous(), msg[:8192], msg_len=32).any())
-        r = alternate(f)
+        r = alternate(f, REPEATS)
         print(f" {nkeys} keys:")
         base = show(NAMES["rlc"], n, r["rlc"])
         show(NAMES["keyed"], n, r["keyed"], base, "the unkeyed combination")
@@ -143,24 +99,15 @@ with ed.keyset_create(pk_all[:1024].contiguous()) as ks:
         if m > n:
             break
         s_, p_, i_, m_ = (t[:m].contiguous() for t in (sig, pk, idx, msg))
-        r = alternate(forms_of(ks, s_, p_, i_, m_))
+        r = alternate(forms_of(ks, s_, p_, i_, m_), REPEATS)
         base = show(f"2^{lg} items  {NAMES['keyed']}", m, r["keyed"])
         show(f"2^{lg} items  {NAMES['rlc']}", m, r["rlc"], base, "the keyed per-item pass")
         show(f"2^{lg} items  {NAMES['keyed_rlc']}", m, r["keyed_rlc"], base, "the keyed per-item pass")
 print()
 
 if PARENT:
-    print(f"the two existing passes, this build against {os.path.relpath(PARENT, ROOT)}, fresh processes alternating (1024 keys' items):")
-    mine = os.path.join(ROOT, "libeddsa_amd", "libeddsa_amd_debug.so")
-    rows = {}
-    for _ in range(REPEATS):
-        for label, lib in (("parent", PARENT), ("this", mine)):
-            o = subprocess.check_output([sys.executable, os.path.abspath(__file__), "3", str(LOG_N), "--only-existing"],
-                                        env=dict(os.environ, EDDSA_AMD_LIBRARY=lib), text=True, timeout=300)
-            for line in o.splitlines():
-                if line.startswith("EXISTING"):
-                    _, k, *vals = line.split()
-                    rows.setdefault((k, label), []).extend(float(x) for x in vals)
+    print(f"the two existing passes, this build against {os.path.relpath(PARENT, rate_kit.ROOT)}, fresh processes alternating (1024 keys' items):")
+    rows = rate_kit.parent_ab(__file__, LOG_N, REPEATS, rate_kit.CHILD_FLAG, ("rlc", "keyed"), PARENT, rate_kit.DEBUG_LIBRARY)
     for k in ("rlc", "keyed"):
-        for label in ("parent", "this"):
-            show(f"{NAMES[k]}, {label} build", n, sorted(rows[(k, label)]))
+        for build in ("parent", "this"):
+            show(f"{NAMES[k]}, {build} build", n, rows[(build, k)])

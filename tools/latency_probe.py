@@ -1,9 +1,7 @@
 """Latency of one call of each single-item function (batch of one, host buffers) and of small verify batches."""
-import time, numpy as np, sys, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
-import libeddsa_amd as ed
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
-ed.init(0)
+import time, numpy as np
+import rate_kit
+ed = rate_kit.bind()
 sk = bytes(range(32)); pk = ed.ed25519_genpub(sk); msg = b"x" * 32; sig = ed.ed25519_sign(sk, pk, msg)
 for name, f in (("ed25519_verify", lambda: ed.ed25519_verify(sig, pk, msg)), ("ed25519_sign", lambda: ed.ed25519_sign(sk, pk, msg)),
                 ("x25519", lambda: ed.x25519(sk, pk)), ("ed25519_genpub", lambda: ed.ed25519_genpub(sk))):

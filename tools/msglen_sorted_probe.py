@@ -1,23 +1,17 @@
 #!/usr/bin/env python3
 """Does the ORDER of ragged messages matter when the chip is full?  2^20 items, lengths uniform in 0 .. L, as drawn and sorted by
 length (what a length-sorted hash pre-pass would see): verify, sign and the batch verification (rlc), device-resident."""
-import os, sys, time
+import sys
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
-import libeddsa_amd as ed
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
-ed.init(0)
+import rate_kit
+ed = rate_kit.bind()
 n = 1 << (int(sys.argv[1]) if len(sys.argv) > 1 else 20)
 g = torch.Generator(device="cuda").manual_seed(7)
 dsk = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device="cuda", generator=g)
 dpk = ed.ed25519_genpub_batch(dsk)
 
-def rate(fn, reps=3):
-    fn(); torch.cuda.synchronize(); t0 = time.perf_counter()
-    for _ in range(reps): fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / reps
+def rate(fn):
+    return rate_kit.steady(fn, warm=1, iters=3) / 1e3
 
 for L in (1024, 4096, 8192):
     rng = np.random.default_rng(L)

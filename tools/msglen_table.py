@@ -2,24 +2,18 @@
 """Verify and sign against the message length, device-resident inputs: fixed lengths 32 B .. 64 KiB, ragged lengths drawn
 uniformly from 0 .. 64 KiB, and the skewed case (32-byte messages, one in 1024 of 1 MiB).  A lane hashes its message
 block by block (csrc/sha512.h); a wave ends with its longest message."""
-import os, sys, time
+import sys
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
-import libeddsa_amd as ed
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
-ed.init(0)
+import rate_kit
+ed = rate_kit.bind()
 n = 1 << (int(sys.argv[1]) if len(sys.argv) > 1 else 16)
 g = torch.Generator(device="cuda").manual_seed(7)
 dsk = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device="cuda", generator=g)
 dpk = ed.ed25519_genpub_batch(dsk)
 
 
-def rate(fn, reps=3):
-    fn(); torch.cuda.synchronize(); t0 = time.perf_counter()
-    for _ in range(reps): fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / reps
+def rate(fn):
+    return rate_kit.steady(fn, warm=1, iters=3) / 1e3
 
 
 def row(label, blob, off, mlen, total_bytes, max_len):

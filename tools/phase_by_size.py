@@ -1,10 +1,8 @@
 """HIP-event phase times of one verify pass by size, for valid signatures only and for the config-2 mix (whose
 off-curve keys bring the exact path's kernels beside the main kernel)."""
-import os, sys, numpy as np, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo")); sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "tools"))
-import libeddsa_amd as ed, workload
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
-ed.init(0)
+import sys, numpy as np, torch
+import rate_kit, workload
+ed = rate_kit.bind()
 d = lambda a: torch.from_numpy(a).cuda()
 for l in ([int(a) for a in sys.argv[1:]] or (20, 19, 18, 17, 16)):
     n = 1 << l

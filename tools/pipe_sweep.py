@@ -1,13 +1,9 @@
 """Host buffer to host buffer rates of verify / x25519 / sign for several chunk schedules and kernel orderings of the host pipeline (eddsa_amd_set_pipeline, eddsa_amd_set_pipeline_chain)."""
-import os, sys, time
+import time, ctypes
 import numpy as np
-ROOT = "/root/repo"
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch
-import libeddsa_amd as ed
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
-import workload, ctypes
-ed.init(0)
+import rate_kit, workload
+ed = rate_kit.bind()
 n = 1 << 20
 sk, msg = workload.sign_inputs(n, seed=1, config=2)
 pk = ed.ed25519_genpub_batch(sk); sig = ed.ed25519_sign_batch(sk, pk, msg)

@@ -1,14 +1,11 @@
 """Host buffer to host buffer rate of ed25519_verify_batch (2^20 items, numpy arrays) by chunk schedule, for the config-2 mix
 (an exact chain beside every chunk's main kernel) and for valid signatures only (no exact path below 2^19 items): what the
 chains cost the host pipeline.  tools/pipe_verify_sweep.py"""
-import os, sys, time, ctypes
+import sys, time, ctypes
 import numpy as np
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch
-import libeddsa_amd as ed, workload
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
-ed.init(0)
+import rate_kit, workload
+ed = rate_kit.bind()
 n = 1 << 20
 sk, msg = workload.sign_inputs(n, seed=1, config=2)
 pk = ed.ed25519_genpub_batch(sk); sig = ed.ed25519_sign_batch(sk, pk, msg)

@@ -3,7 +3,7 @@
 # per kernel, each group its own rocprofv3 run:   tools/pmc_by_size.sh <tag> [sizes...]   -> gpurun_out/pmc_<tag>/summary.txt
 TAG=${1:-sz}; shift
 SIZES=${@:-17 18 20}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=$REPO/gpurun_out/pmc_$TAG
 rm -rf $OUT && mkdir -p $OUT

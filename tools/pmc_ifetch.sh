@@ -2,7 +2,7 @@
 # Instruction-fetch counters of one verify pass of 2^20 items and of the sign / x25519 passes, per kernel:
 #   tools/pmc_ifetch.sh   -> gpurun_out/pmc_ifetch/summary.txt
 # (is a kernel whose straight-line code is larger than the 64 KB instruction cache held up by its fetches?)
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=$REPO/gpurun_out/pmc_ifetch
 rm -rf $OUT && mkdir -p $OUT

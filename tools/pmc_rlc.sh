@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC counters of the RLC kernels (separate pass, no tracing): tools/pmc_rlc.sh <tag>
-TAG=${1:-rlc}; R=${GRAFT_REPO_ROOT:-/root/repo}
+TAG=${1:-rlc}; R=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $R/gpurun_out/$TAG; cd /tmp && export TMPDIR=/tmp
 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAVES GRBM_GUI_ACTIVE --output-format csv -d $R/gpurun_out/$TAG/pmc -- python3 $R/tools/rlc_rate.py 3 > $R/gpurun_out/$TAG/rate_pmc.log 2>&1
 python3 - $R/gpurun_out/$TAG <<'PY'

@@ -1,5 +1,5 @@
 #!/bin/bash
-TAG=${1:-rlc}; R=${GRAFT_REPO_ROOT:-/root/repo}
+TAG=${1:-rlc}; R=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $R/gpurun_out/$TAG; cd /tmp && export TMPDIR=/tmp
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/gpurun_out/$TAG/pmc_fetch -- python3 $R/tools/rlc_rate.py 3 > $R/gpurun_out/$TAG/rate_pmc2.log 2>&1
 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $R/gpurun_out/$TAG/pmc_tcc -- python3 $R/tools/rlc_rate.py 3 > $R/gpurun_out/$TAG/rate_pmc3.log 2>&1

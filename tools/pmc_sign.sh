@@ -1,7 +1,7 @@
 #!/bin/bash
 # VALU-busy and LDS counters of the fixed-base point kernels: tools/pmc_sign.sh <tag> -> gpurun_out/pmc_sign_<tag>.txt
 TAG=${1:-s}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=$REPO/gpurun_out/pmc_sign_$TAG
 rm -rf $OUT && mkdir -p $OUT

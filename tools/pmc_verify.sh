@@ -1,7 +1,7 @@
 #!/bin/bash
 # VALU instruction counts of the verify kernels: tools/pmc_verify.sh <tag>
 TAG=${1:-v}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT

@@ -9,25 +9,18 @@ process; every repeat is `iters` calls between two events; the spread of a row i
 baseline: policy 0 only and no call of set_verify_policy - the row to compare between two builds of the library on one box
 (tools/ab.sh with EDDSA_AMD_LIBRARY; a build from before the rules existed reads the bits as "exact").
 """
-import os
 import sys
 
-import numpy as np
-import torch
+import torch  # noqa: F401  (loaded before the library, as in every script that uses it)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
-import libeddsa_amd as ed  # noqa: E402
+import rate_kit
 
-REPEATS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-LOG_N = int(sys.argv[2]) if len(sys.argv) > 2 else 20
-BASELINE = len(sys.argv) > 3 and sys.argv[3] == "baseline"
-assert REPEATS >= 3
-ed.init(0)
+REPEATS, LOG_N, _, FLAGS = rate_kit.cli(sys.argv[1:])
+BASELINE = "baseline" in FLAGS
+ed = rate_kit.bind(debug=False)
 n = 1 << LOG_N
-g = torch.Generator(device="cuda").manual_seed(20261019)
-dsk = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device="cuda", generator=g)
-dmsg = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device="cuda", generator=g)
+rnd = rate_kit.rnd(20261019)
+dsk, dmsg = rnd(n, 32), rnd(n, 32)
 dpk = ed.ed25519_genpub_batch(dsk)
 dsig = ed.ed25519_sign_batch(dsk, dpk, dmsg, msg_len=32)
 verify = lambda: ed.ed25519_verify_batch(dsig, dpk, dmsg, msg_len=32)   # noqa: E731
@@ -39,38 +32,23 @@ if not BASELINE:
              ("R_NOT_SMALL", ed.VERIFY_R_NOT_SMALL), ("STRICT", ed.VERIFY_STRICT)]
 
 
-def timed(policy, iters):
-    if not BASELINE:
-        ed.set_verify_policy(policy)
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    verify()                                        # untimed: the repeat starts from this policy's own state
-    a.record()
-    for _ in range(iters):
-        verify()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
 try:
-    iters = {}
-    for label, policy in ROWS:                      # warm-up (honest signatures satisfy every rule); sizes a repeat to about 0.1 s
-        if not BASELINE:
-            ed.set_verify_policy(policy)
+    forms = {}
+    for label, policy in ROWS:                      # honest signatures satisfy every rule; baseline never touches the switch
+        switch = None if BASELINE else (lambda policy=policy: ed.set_verify_policy(policy))
+        if switch:
+            switch()
         assert bool(verify().all())
-        iters[label] = max(2, min(50, int(100.0 / max(timed(policy, 2), 1e-3))))
-    ms = {label: [] for label, _ in ROWS}
-    for _ in range(REPEATS):
-        for label, policy in ROWS:
-            ms[label].append(timed(policy, iters[label]))
+        forms[label] = (switch, verify)
+    ms = rate_kit.alternate(forms, REPEATS)
 finally:
     if not BASELINE:
         ed.set_verify_policy(0)
 
 print(f"{ed.library_path()}: 2^{LOG_N} valid items, msg_len 32, {REPEATS} repeats")
-base = sorted(ms["policy 0"])[REPEATS // 2]
-for label, _ in ROWS:
-    v = sorted(ms[label])
+base = ms["policy 0"][REPEATS // 2]
+for label, _ in ROWS:                              # its own row: the kit's label width, the spread also in per cent
+    v = ms[label]
     med = v[REPEATS // 2]
-    print(f"  {label:12s} {med:8.3f} ms  [{v[0]:.3f} .. {v[-1]:.3f}]  spread {v[-1] - v[0]:.3f} ms ({100 * (v[-1] - v[0]) / med:.1f} %)"
+    print(f"  {label:{rate_kit.LABEL_WIDTH}s} {med:8.3f} ms  [{v[0]:.3f} .. {v[-1]:.3f}]  spread {v[-1] - v[0]:.3f} ms ({100 * (v[-1] - v[0]) / med:.1f} %)"
           f"  {n / med / 1e3:7.2f} M/s  {100 * (med - base) / base:+6.2f} % against policy 0", flush=True)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Power, clocks and temperature while one op of the bench runs back to back: tools/power_probe.sh [verify|x25519|sign]
 OP=${1:-verify}
-cd $GRAFT_REPO_ROOT
+cd "$(cd "$(dirname "$0")/.." && pwd)"
 mkdir -p gpurun_out
 python3 bench.py --op $OP --steps 4000 --warmup 2 --cpu-sample 4096 > gpurun_out/pw_bench_$OP.log 2>&1 &
 PID=$!

@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 kernel stats of tools/rlc_rate.py (run through gpurun): tools/prof_rlc.sh <tag>
-TAG=${1:-rlc}; R=${GRAFT_REPO_ROOT:-/root/repo}
+TAG=${1:-rlc}; R=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $R/gpurun_out/$TAG; cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/$TAG/prof -- python3 $R/tools/rlc_rate.py 5 > $R/gpurun_out/$TAG/rate_profiled.log 2>&1
 python3 - $R/gpurun_out/$TAG <<'PY'

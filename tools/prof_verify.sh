@@ -1,7 +1,7 @@
 #!/bin/bash
 # kernel stats of the verify bench only: tools/prof_verify.sh <tag>  -> gpurun_out/prof_<tag>/verify_stats.csv
 TAG=${1:-v}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT

@@ -4,7 +4,7 @@
 # --kernel-trace --stats and every --pmc group run as SEPARATE passes (never combined).
 set -u
 TAG=${1:-r01}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=$REPO/gpurun_out/prof_$TAG
 rm -rf $OUT && mkdir -p $OUT

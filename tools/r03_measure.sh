@@ -1,6 +1,6 @@
 #!/bin/bash
 # The host-side measurements DESIGN.md 4 quotes, in one go (run on the GPU box): -> gpurun_out/r03_host_side.txt
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(cd "$(dirname "$0")/.." && pwd)"
 OUT=gpurun_out/r03_host_side.txt
 {
 echo "== tools/host_path_bench.py: 2^20 items host buffer to host buffer"

@@ -7,13 +7,10 @@ import sys
 import numpy as np
 import torch
 
-sys.path.insert(0, __file__.rsplit("/", 2)[0])
-sys.path.insert(0, __file__.rsplit("/", 1)[0])
-import libeddsa_amd as ed
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
+import rate_kit
 import workload
 
-ed.init(0)
+ed = rate_kit.bind()
 n = 1 << 20
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 sk, msg = workload.sign_inputs(n, seed=1, config=2)

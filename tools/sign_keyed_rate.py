@@ -16,64 +16,19 @@ over its repeats.  Before anything is timed every keyed form's signatures are co
                                                      against the build of the commit before, alternating in fresh processes
                                                      (tools/ab.sh; the library comes from EDDSA_AMD_LIBRARY)
 """
-import os
 import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import libeddsa_amd as ed  # noqa: E402
+import rate_kit
+from rate_kit import alternate, show, timed, wall
 
-UNCHANGED = len(sys.argv) > 1 and sys.argv[1] == "unchanged"
-ARGS = sys.argv[2:] if UNCHANGED else sys.argv[1:]
-REPEATS = int(ARGS[0]) if len(ARGS) > 0 else 5
-LOG_N = int(ARGS[1]) if len(ARGS) > 1 else 20
-assert REPEATS >= 3
+REPEATS, LOG_N, _, FLAGS = rate_kit.cli(sys.argv[1:])
+UNCHANGED = "unchanged" in FLAGS
 CONTEXT = b"foo"
-ed.init(0)
-
-
-def timed(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fn()                                            # untimed: the repeat starts from this form's own state, not from its neighbour's
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def wall(fn, iters=1):
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t) * 1e3 / iters
-
-
-def alternate(forms, clock=timed):
-    """forms: {label: callable} -> {label: sorted per-call ms of REPEATS repeats}, the forms taking turns"""
-    iters = {}
-    for k, fn in forms.items():                     # warm-up; sizes a repeat to about 0.1 s
-        fn(); torch.cuda.synchronize()
-        iters[k] = max(2, min(50, int(100.0 / max(clock(fn, 2), 1e-3))))
-    out = {k: [] for k in forms}
-    for _ in range(REPEATS):
-        for k, fn in forms.items():
-            out[k].append(clock(fn, iters[k]))
-    return {k: sorted(v) for k, v in out.items()}
-
-
-def show(label, n, ms, base=None):
-    med = ms[len(ms) // 2]
-    rel = "" if base is None else f"  {100 * (med - base) / base:+6.2f} % against the unkeyed form"
-    print(f"  {label:52s} {med:9.3f} ms  [{ms[0]:.3f} .. {ms[-1]:.3f}]  spread {ms[-1] - ms[0]:.3f} ms  {n / med / 1e3:8.2f} M/s{rel}", flush=True)
-    return med
+ed = rate_kit.bind(debug=False)
 
 
 def pair(title, n, unkeyed_label, unkeyed, keyed_label, keyed, clock=timed):
@@ -81,20 +36,20 @@ def pair(title, n, unkeyed_label, unkeyed, keyed_label, keyed, clock=timed):
     assert bool(torch.equal(want, got)) if torch.is_tensor(want) else np.array_equal(want, got), title
     del want, got
     print(title)
-    r = alternate({unkeyed_label: unkeyed, keyed_label: keyed}, clock)
+    r = alternate({unkeyed_label: unkeyed, keyed_label: keyed}, REPEATS, clock)
     base = show(unkeyed_label, n, r[unkeyed_label])
-    show(keyed_label, n, r[keyed_label], base)
+    show(keyed_label, n, r[keyed_label], base, "the unkeyed form")
     print()
 
 
 n = 1 << LOG_N
-g = torch.Generator(device="cuda").manual_seed(2520)
+g = torch.Generator(device="cuda").manual_seed(2520)    # its own generator: the signer indices are drawn from it as well
 rnd = lambda *shape: torch.randint(0, 256, shape, dtype=torch.uint8, device="cuda", generator=g)   # noqa: E731
 seeds, msg, pre = rnd(n, 32), rnd(n, 32), rnd(n, 64)
 
 if UNCHANGED:
     pk = ed.ed25519_genpub_batch(seeds)
-    r = alternate({"sign": lambda: ed.ed25519_sign_batch(seeds, pk, msg, msg_len=32)})
+    r = alternate({"sign": lambda: ed.ed25519_sign_batch(seeds, pk, msg, msg_len=32)}, REPEATS)
     show(f"ed25519_sign_batch_dev, 2^{LOG_N} items", n, r["sign"])
     sys.exit(0)
 

@@ -2,7 +2,7 @@
 # counters of the kernels of ONE single-item call (instructions per wave, cycles, hence the clock the chip ran at):
 #   tools/single_call_pmc.sh <verify1|sign1|genpub1|x255191>   -> gpurun_out/single_pmc_<op>.txt
 OP=${1:-verify1}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=$REPO/gpurun_out/single_pmc_$OP
 rm -rf $OUT; mkdir -p $OUT

@@ -3,7 +3,7 @@
 #   tests/c/host_side_stress.c   chunked ragged batches, single-item calls, trace toggling, fault hooks, concurrent shutdowns
 #   tests/c/threaded_callers.c   threads looping over the eddsa.h single-item functions (the combiner)
 # Every result is compared with the golden tables by the programs themselves; the exit status says whether all were right.
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(cd "$(dirname "$0")/.." && pwd)"
 T=${1:-64}; R=${2:-400}
 python3 - <<'PY'
 import hashlib

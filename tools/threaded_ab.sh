@@ -1,6 +1,6 @@
 #!/bin/bash
 # threaded single-item callers against two builds of the library: tools/threaded_ab.sh ab/C.so ab/D.so
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(cd "$(dirname "$0")/.." && pwd)"
 python3 - <<'PY'
 import hashlib
 def golden_msg(i):

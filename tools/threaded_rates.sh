@@ -1,5 +1,5 @@
 #!/bin/bash
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(cd "$(dirname "$0")/.." && pwd)"
 python3 - <<'PY'
 import hashlib
 def golden_msg(i):

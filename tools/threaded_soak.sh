@@ -1,4 +1,4 @@
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(cd "$(dirname "$0")/.." && pwd)"
 python3 - <<'PY'
 import hashlib
 def golden_msg(i):

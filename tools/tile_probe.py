@@ -2,14 +2,11 @@
 """Does tiling a 2^20-item verify pass pay?  The batch resident in HBM, verified in one call and as equal tiles of 2^L items
 on 1, 2 or 3 streams, for valid signatures only (no exact path below 2^18 items: the pair search is the wide one) and for
 the config-2 mix (an exact chain beside every tile):  tools/tile_probe.py [reps]"""
-import os, sys, time
+import sys, time
 import numpy as np, torch
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
-import libeddsa_amd as ed, workload
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
+import rate_kit, workload
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 7
-ed.init(0)
+ed = rate_kit.bind()
 n = 1 << 20
 sk, msg = workload.sign_inputs(n, seed=1, config=2)
 d = lambda a: torch.from_numpy(a).cuda()

@@ -1,16 +1,13 @@
 #!/usr/bin/env python3
 """One verify pass of 2^L items, repeated: tools/verify_pass.py L [reps] [valid|mix] [gap_ms]
 (the program rocprofv3 runs for the counter passes of tools/pmc_by_size.sh; prints the wall ms per pass)."""
-import os, sys, time
+import sys, time
 import numpy as np, torch
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
-import libeddsa_amd as ed, workload
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
+import rate_kit, workload
 L = int(sys.argv[1]); reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 kind = sys.argv[3] if len(sys.argv) > 3 else "mix"
 gap = float(sys.argv[4]) if len(sys.argv) > 4 else 0.0
-ed.init(0)
+ed = rate_kit.bind()
 n = 1 << L
 sk, msg = workload.sign_inputs(n, seed=1, config=2)
 d = lambda a: torch.from_numpy(a).cuda()

@@ -1,13 +1,9 @@
 """One verify pass (config-2 mix, device-resident) by size: SIZES=19,18,17 python tools/verify_sizes.py"""
-import os, sys, time
+import os, time
 import numpy as np
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch
-import libeddsa_amd as ed
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
-import workload
-ed.init(0)
+import rate_kit, workload
+ed = rate_kit.bind()
 if os.environ.get("OFFCURVE_MODE"): ed.set_offcurve_mode(int(os.environ["OFFCURVE_MODE"]))
 if os.environ.get("VERIFY_ALGO"): ed.set_verify_algo(int(os.environ["VERIFY_ALGO"]))   # 1 full-length, 2 half-length, whatever the size
 for lg in [int(x) for x in os.environ.get("SIZES", "20,19,18,17,16,15,14,13,12").split(",")]:

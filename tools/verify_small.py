@@ -1,11 +1,9 @@
 """Time of one verify pass for small batches, device-resident, back to back (no host sync between calls):
 valid signatures only (no key off the curve, so the exact path has nothing to do) and the config-2 recipe
 (corruptions and edge vectors: the reference-order chain for the off-curve keys sets the floor)."""
-import os, sys, time, numpy as np, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo")); sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "tools"))
-import libeddsa_amd as ed, workload
-ed.use_debug_library()   # the hooks (route selection, phase timings, traces) live in libeddsa_amd_debug.so
-ed.init(0)
+import numpy as np, torch
+import rate_kit, workload
+ed = rate_kit.bind()
 d = lambda a: torch.from_numpy(a).cuda()
 for algo in (0, 1):
     ed.set_verify_algo(algo)
@@ -17,8 +15,5 @@ for algo in (0, 1):
             pk = ed.ed25519_genpub_batch(d(sk)); sig = ed.ed25519_sign_batch(d(sk), pk, d(msg)).cpu().numpy(); pk = pk.cpu().numpy()
             if not clean: workload.corrupt_for_verify(sig, pk, msg)
             ds, dp, dm = d(sig), d(pk), d(msg)
-            for _ in range(5): ed.ed25519_verify_batch(ds, dp, dm)
-            torch.cuda.synchronize(); t0 = time.perf_counter()
-            for _ in range(30): ed.ed25519_verify_batch(ds, dp, dm)
-            torch.cuda.synchronize(); print(f"2^{l}: {(time.perf_counter()-t0)/30*1e3:.3f}", end="  ")
+            print(f"2^{l}: {rate_kit.steady(lambda: ed.ed25519_verify_batch(ds, dp, dm)):.3f}", end="  ")
         print("ms")
