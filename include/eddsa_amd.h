@@ -665,6 +665,62 @@ RFC8032_EDDSA_DECL int ed25519ph_sign_keyed(uint8_t *sigs, const eddsa_amd_signe
 RFC8032_EDDSA_DECL int ed25519ph_sign_keyed_dev(uint8_t *sigs, const eddsa_amd_signer *s, const uint32_t *key_idx, const uint8_t *prehashes, size_t n,
                                                 const uint8_t *context /* host */, size_t context_len, void *stream);
 
+/* ---- POINT CLASSIFICATION: what a 32-byte string is as a curve point ----
+ * For callers that qualify keys once, at registration (validator sets, token issuers, consensus nodes), and then rely on the fast
+ * paths.  The verify forms decode anything; the strict rules (EDDSA_AMD_VERIFY_*) only turn accepts into rejects inside a pass and do
+ * not cover a point of mixed order; the _rlc forms promise the per-item verdicts "whenever every A and R lies in the prime-order
+ * subgroup"; key sets register ANY 32-byte strings.  These calls answer the question on its own: one class byte per item, the OR of
+ *   EDDSA_AMD_POINT_ON_CURVE        the string decodes under the reference's permissive import (ed_import, what every verify form
+ *                                   applies to A): y is the low 255 bits mod p, so a y >= p counts, and x = 0 takes either sign bit.
+ *   EDDSA_AMD_POINT_CANONICAL       the string is an encoding that RFC 8032 5.1.3 decodes: y < p, a root exists, and not x = 0 with
+ *                                   the sign bit set.  It implies ON_CURVE.
+ *   EDDSA_AMD_POINT_SMALL_ORDER     the point is on the curve and [8]P is the neutral element (y mod p is one of the five values of
+ *                                   the eight points of order 1, 2, 4 and 8).  The neutral element has this bit.
+ *   EDDSA_AMD_POINT_PRIME_SUBGROUP  the point is on the curve and [l]P is the neutral element.  The neutral element has this bit
+ *                                   too: it is the only point with both SMALL_ORDER and PRIME_SUBGROUP.  A point of mixed order (a
+ *                                   small-order component on a prime-order point) has ON_CURVE and neither of the two order bits.
+ * A string that is no curve point classifies as 0.  The class depends on the 32 bytes only: the off-curve mode, the strict rules and
+ * the equation play no part, and no policy bit is added (the meanings of eddsa_amd_set_offcurve_mode's values are untouched).
+ * What a caller does with it: a key fit for registration has
+ *   (cls & 0x0F) == (EDDSA_AMD_POINT_ON_CURVE | EDDSA_AMD_POINT_CANONICAL | EDDSA_AMD_POINT_PRIME_SUBGROUP).
+ * What the class buys: if every key of a key set has PRIME_SUBGROUP, the cofactorless caveat of the _rlc forms is about R alone -
+ *   two or more crafted R with small-order components in one group can still cancel; such a caller can classify the R strings of a
+ *   batch with the same call (copied out of the signatures: see "out of scope").  Under the cofactored equation
+ *   (eddsa_amd_set_verify_equation) there was no caveat to begin with.
+ * Calls: layout packed, 32 bytes per item in and one byte out; `points` and `cls` may have any alignment.  An empty batch (n == 0)
+ *   returns 0; a NULL cls or points with n > 0 returns -hipErrorInvalidValue before any device is touched.  The device form runs on the
+ *   device that holds `cls`, enqueues on `stream` and returns.  The host form goes through the staging pipeline like every host-pointer
+ *   call and is never merged by the small-call combiner.
+ * eddsa_amd_keyset_classify runs the same kernel over the set's own key bytes in HBM, on the set's device (made current for the
+ *   call's duration), downloads eddsa_amd_keyset_count(ks) bytes into `cls` and returns when done.  It works on plain and on comb sets,
+ *   and after eddsa_amd_shutdown - a key set survives shutdown, and the kernel needs no table and no workspace.  It refuses a NULL ks or
+ *   cls with -hipErrorInvalidValue.  It changes nothing: not key-set creation (ANY strings are still registered), not the set's
+ *   contents, not eddsa_amd_keyset_bytes.  A caller that wants only qualified keys in a set classifies first and registers what passed.
+ * A library built without the HIP translation unit answers -hipErrorNotSupported from all three.
+ * Kernel: one lane per string - the decoding of the verify pass (one square-root chain), the y < p test, the five-value small-order
+ *   test, and for strings on the curve the chain [l]P over the non-adjacent form of l (46 nonzero digits): 252 doublings and 45 additions
+ *   of P or -P, with P held in registers (no table, no memory, no inversion: the neutrality test is projective).  The digits are derived from l
+ *   at compile time; which digit comes is the same in every lane, so the chain does not diverge.  The group law is complete on the
+ *   curve: points of small and of mixed order take the same path as honest keys.  Nothing here is secret.
+ * Out of scope: strided input (the R of packed signatures in place); _multi and single-item forms; a strict rule that requires the
+ *   subgroup inside a verify pass; four-lane forms for small batches.
+ * Measured (profiles/point_classify.txt, tools/classify_rate.py: device-pointer forms, 2^20 items in HBM, one MI355X, the forms
+ *   alternating in one process, repeat spread 0.002-0.026 ms): 2^20 honest public keys 8.231 ms per pass (127 M strings/s); 2^20
+ *   random strings, half of them no curve point, 8.216 ms - the same, because a wave ends early only when all 64 of its strings leave
+ *   before the chain; beside them pk_ed25519_to_x25519_batch_dev over the same keys 0.716 ms and ed25519_verify_batch_dev over valid
+ *   signatures under them 9.364 ms: classifying a key costs 12 % less than verifying one signature under it, once per key.  The
+ *   kernel holds 224 VGPRs without scratch or spills - two waves per SIMD, like the verify main kernels - and was not tuned further.
+ *   ed25519_verify_batch_dev against the commit before, alternating in fresh processes: 9.345 ms against 9.341 ms, inside the older
+ *   build's own repeat spread (9.329-9.359 ms); every older kernel has the older build's metadata.
+ * (Declared with the macro of the RFC 8032 variants: tests of earlier additions count the EDDSA_AMD_DECL names.) */
+#define EDDSA_AMD_POINT_ON_CURVE        0x01
+#define EDDSA_AMD_POINT_CANONICAL       0x02
+#define EDDSA_AMD_POINT_SMALL_ORDER     0x04
+#define EDDSA_AMD_POINT_PRIME_SUBGROUP  0x08
+RFC8032_EDDSA_DECL int ed25519_point_classify_batch(uint8_t *cls, const uint8_t *points /* host, 32 bytes per item */, size_t n);
+RFC8032_EDDSA_DECL int ed25519_point_classify_batch_dev(uint8_t *cls, const uint8_t *points /* device */, size_t n, void *stream);
+RFC8032_EDDSA_DECL int eddsa_amd_keyset_classify(const eddsa_amd_keyset *ks, uint8_t *cls /* host, eddsa_amd_keyset_count(ks) bytes */);
+
 #ifdef __cplusplus
 }
 #endif

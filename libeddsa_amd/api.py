@@ -573,6 +573,22 @@ def sk_ed25519_to_x25519_batch(secs):
                    "sk_ed25519_to_x25519_batch", [(secs, 32, "secs")], 32, 32)
 
 
+# the bits of a class byte: EDDSA_AMD_POINT_*, include/eddsa_amd.h
+POINT_ON_CURVE = 0x01
+POINT_CANONICAL = 0x02
+POINT_SMALL_ORDER = 0x04
+POINT_PRIME_SUBGROUP = 0x08
+
+
+def point_classify_batch(points):
+    """what each 32-byte string is as a curve point (include/eddsa_amd.h: ed25519_point_classify_batch) -> (n,) uint8, the OR of
+    POINT_ON_CURVE, POINT_CANONICAL, POINT_SMALL_ORDER and POINT_PRIME_SUBGROUP; 0 for a string that is no curve point.  A key fit
+    for registration has cls & 0x0F == POINT_ON_CURVE | POINT_CANONICAL | POINT_PRIME_SUBGROUP.  bytes / numpy: the host form;
+    a CUDA uint8 tensor: the device form, on the current stream."""
+    return _run_32("ed25519_point_classify_batch", "ed25519_point_classify_batch_dev", "ed25519_point_classify_batch",
+                   [(points, 32, "points")], 1, 32).reshape(-1)
+
+
 def ed25519_verify_batch(sigs, pubs, msgs, msg_off=None, msg_len=None):
     """loop of ed25519_verify (reference lib/eddsa.h:52) -> (n,) uint8, 1 = accept.
 
@@ -640,6 +656,12 @@ class Keyset:
         lib = library()
         lib.eddsa_amd_keyset_bytes.restype = ctypes.c_size_t
         return int(lib.eddsa_amd_keyset_bytes(self._handle()))
+
+    def classify(self):
+        """the class byte of every key of the set (point_classify_batch over the set's own bytes in HBM) -> (count,) uint8, host"""
+        cls = np.zeros(self.count, dtype=np.uint8)
+        _check(library().eddsa_amd_keyset_classify(self._handle(), _np_ptr(cls)), "eddsa_amd_keyset_classify")
+        return cls
 
     def close(self):
         if self._h is not None:

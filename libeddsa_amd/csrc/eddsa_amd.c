@@ -654,6 +654,18 @@ int sk_to_x_on(struct engine *e, uint8_t *out, const uint8_t *in, size_t n, hipS
     return er == hipSuccess ? 0 : -(int)er;
 }
 
+/* edk_point_classify is a WEAK reference (edk_classify.h), like edk_signer_build: the host side is also linked without the HIP
+ * translation unit (tests/fake_hip) - classifying is then hipErrorNotSupported */
+extern __typeof__(edk_point_classify) edk_point_classify __attribute__((weak));
+
+int classify_on(struct engine *e, uint8_t *cls, const uint8_t *points, size_t n, hipStream_t st)
+{
+    (void)e;
+    if (!edk_point_classify) return -(int)hipErrorNotSupported;
+    hipError_t er = edk_point_classify(cls, points, n, st);
+    return er == hipSuccess ? 0 : -(int)er;
+}
+
 /* Batch verification by random linear combination (reference lib/ed25519-sha512.c:13-14, its TODO;
  * SURVEY 8(f)-3): see include/eddsa_amd.h.  One pass of at most CHUNK_MAX items; larger batches are
  * split into independent sub-batches. */
@@ -1136,6 +1148,39 @@ int sk_ed25519_to_x25519_batch_dev(uint8_t *out, const uint8_t *in, size_t n, vo
     int rc = 0;
     if (n == 0 || (rc = enter_dev(&c, out))) return rc;
     return leave_with(&c, sk_to_x_on(c.e, out, in, n, (hipStream_t)stream));
+}
+
+/* point classification (include/eddsa_amd.h): an empty batch is done, NULLs are refused and a build without the kernel says so before
+ * any device is asked */
+int ed25519_point_classify_batch_dev(uint8_t *cls, const uint8_t *points, size_t n, void *stream)
+{
+    struct call c;
+    int rc = 0;
+    if (n == 0) return 0;
+    if (!cls || !points) return -(int)hipErrorInvalidValue;
+    if (!edk_point_classify) return -(int)hipErrorNotSupported;
+    if ((rc = enter_dev(&c, cls))) return rc;
+    return leave_with(&c, classify_on(c.e, cls, points, n, (hipStream_t)stream));
+}
+
+/* The class bytes of a key set's own keys, where they lie.  No engine is asked for - the kernel reads no table and takes no workspace,
+ * and the set outlives eddsa_amd_shutdown: the set's device is made current, the classes land in a temporary buffer of `count` bytes
+ * that is freed on every path, and the download waits for the kernel. */
+int eddsa_amd_keyset_classify(const eddsa_amd_keyset *ks, uint8_t *cls)
+{
+    int saved = -1, rc = 0;
+    uint8_t *d_cls = NULL;
+    if (!ks || !cls) return -(int)hipErrorInvalidValue;
+    if (!edk_point_classify) return -(int)hipErrorNotSupported;
+    TRY(hipGetDevice(&saved));
+    TRY(hipSetDevice(ks->device));
+    TRY(hipMalloc((void **)&d_cls, ks->count));
+    TRY(edk_point_classify(d_cls, ks->keys, ks->count, NULL));
+    TRY(hipMemcpy(cls, d_cls, ks->count, hipMemcpyDeviceToHost));
+out:
+    if (d_cls) { HIP_NOTE(hipStreamSynchronize(NULL)); HIP_NOTE(hipFree(d_cls)); }
+    if (saved >= 0) HIP_NOTE(hipSetDevice(saved));
+    return rc;
 }
 
 /* ------------------------------------------------------------------------------------------

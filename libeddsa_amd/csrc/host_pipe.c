@@ -947,6 +947,7 @@ RUN_1IN(run_genpub, genpub_on)
 RUN_1IN(run_xbase, xbase_on)
 RUN_1IN(run_pk_to_x, pk_to_x_on)
 RUN_1IN(run_sk_to_x, sk_to_x_on)
+RUN_1IN(run_classify, classify_on)                 /* (one byte out, like a verdict) */
 
 /* The table of operations.  A row says what the pipeline and the combiner need to know of a call: whether small calls may be merged
  * (kind), the widths of its inputs, its chunk sizes, the order of its chunks' kernels and what is wiped - not which form of verify
@@ -966,9 +967,10 @@ RUN_1IN(run_sk_to_x, sk_to_x_on)
  *   OP_SIGN_UNMERGED     Ed25519ctx / Ed25519ph
  *   OP_SIGN_KEYED        every form over a signer set: 4 bytes of key index per item where the others upload 64 bytes of keys; never
  *                        merged - two small calls may carry different signer sets.  A signing process keeps nothing of a call in the
- *                        staging buffers: which key signed what, and the signatures, are zeroed there like the other operations' secrets */
+ *                        staging buffers: which key signed what, and the signatures, are zeroed there like the other operations' secrets
+ *   OP_CLASSIFY          ed25519_point_classify_batch: 32 bytes in, one class byte out, nothing secret; never merged */
 enum { OP_VERIFY, OP_VERIFY_UNMERGED, OP_VERIFY_RLC, OP_VERIFY_RECORDS, OP_VERIFY_KEYED, OP_VERIFY_KEYED_RLC, OP_SIGN, OP_SIGN_UNMERGED, OP_SIGN_KEYED,
-       OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X };
+       OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X, OP_CLASSIFY };
 #define VERIFY_ROW(kind_, w1_, chunk_, first_) { .n_in = 2, .in_w = { 64, w1_, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify, .wipe = WIPE_NONE, \
     .chain = 0, .kind = kind_, .chunk = chunk_, .first_chunk = first_, .reports = 1 }
 static const struct op g_ops[] = {
@@ -988,6 +990,7 @@ static const struct op g_ops[] = {
     [OP_XBASE] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_xbase, .wipe = WIPE_IN0, .chain = 1, .kind = KIND_XBASE },
     [OP_PK_TO_X] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_pk_to_x, .wipe = WIPE_NONE, .chain = 1, .kind = KIND_PK_TO_X },
     [OP_SK_TO_X] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_sk_to_x, .wipe = WIPE_IN0 | WIPE_OUT, .chain = 1, .kind = KIND_SK_TO_X },
+    [OP_CLASSIFY] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 1, .run = run_classify, .wipe = WIPE_NONE, .chain = 1, .kind = KIND_NONE },
 };
 
 /* a call of operation `id` (in1, msgs, msg_off: NULL where the operation has none) */
@@ -1187,6 +1190,14 @@ int ed25519_genpub_batch(uint8_t *pubs, const uint8_t *secs, size_t n) { return 
 int x25519_base_batch(uint8_t *out, const uint8_t *scalars, size_t n) { return pipe_run(job(OP_XBASE, out, scalars, NULL, NULL, NULL, 0), n); }
 int pk_ed25519_to_x25519_batch(uint8_t *out, const uint8_t *in, size_t n) { return pipe_run(job(OP_PK_TO_X, out, in, NULL, NULL, NULL, 0), n); }
 int sk_ed25519_to_x25519_batch(uint8_t *out, const uint8_t *in, size_t n) { return pipe_run(job(OP_SK_TO_X, out, in, NULL, NULL, NULL, 0), n); }
+
+/* point classification (include/eddsa_amd.h): an empty batch is done and NULLs are refused before any device is asked */
+int ed25519_point_classify_batch(uint8_t *cls, const uint8_t *points, size_t n)
+{
+    if (n == 0) return 0;
+    if (!cls || !points) return -(int)hipErrorInvalidValue;
+    return pipe_run(job(OP_CLASSIFY, cls, points, NULL, NULL, NULL, 0), n);
+}
 
 /* ------------------------------------------------------------------------------------------
  * several devices in one process, host-pointer forms: thread d runs the ordinary pipeline of device d

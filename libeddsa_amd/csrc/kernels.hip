@@ -20,9 +20,11 @@
 //   k_keyset_build, k_verify_*_keyed          key-set verification (keyed_kernels.h): the key's table by index
 //   k_keyset_comb_build, k_verify_main_comb_keyed   comb key sets (keyed_kernels.h): a comb per key, both scalars fixed-base
 //   k_signer_build, k_sign_keyed_*            signer sets (signer_kernels.h): the secret scalar, the prefix and A by key index
+//   k_point_classify                          point classification (classify_kernels.h): curve, canonical, small and prime order
 #include "eddsa_kernels.h"
 #include "edk_keyed.h"
 #include "edk_signer.h"
+#include "edk_classify.h"
 #include "edk_checked.h"
 #include "kernel_io.h"
 #include "lanes.h"
@@ -1261,6 +1263,7 @@ k_verify_main_sums_quad(uint8_t* ok, const uint32_t* hdigits, const uint32_t* su
 
 #include "keyed_kernels.h"   // key-set verification: kernels of its own beside the ones above
 #include "signer_kernels.h"  // signer sets: likewise, beside the sign kernels
+#include "classify_kernels.h"  // point classification: one kernel, no workspace
 
 // =============================================================================================
 // launchers (host side of this translation unit)
@@ -1767,6 +1770,13 @@ hipError_t edk_pk_to_x(uint8_t* out, const uint8_t* in, size_t n, hipStream_t st
 hipError_t edk_sk_to_x(uint8_t* out, const uint8_t* in, size_t n, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_sk_to_x, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, out, in, n);
+  return hipGetLastError();
+}
+
+// point classification (edk_classify.h): one class byte per 32-byte string.  Asynchronous on `stream`
+hipError_t edk_point_classify(uint8_t* cls, const uint8_t* points, size_t n, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_point_classify, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, cls, points, n);
   return hipGetLastError();
 }
 
