@@ -50,12 +50,14 @@ EDDSA_AMD_DECL int eddsa_amd_debug_hip_calls(void);
 /* ---- route selection (a measurement and test aid; the verdicts are the same on every route) ----
  * 0 (default): every pass checks u*(S*B - t*A - R) = 0 with half-length u, v = u*t mod 8l (132 doublings instead of
  * 252; csrc/halve.h) - passes of up to 24 576 items with four lanes per item, larger ones with one; passes of 257 ..
- * 2^19 - 1 items search u, v < 2^138 and run 35 windows, larger ones 2^134 and 34; passes of 24 577 .. 2^18 - 1 items
+ * 2^19 - 1 items search u, v < 2^138 and run 35 windows, larger ones balanced pairs (both at most 0x777...7, 33 nibbles) and
+ * 33 (keyed ones 2^134 and 34); passes of 24 577 .. 2^18 - 1 items
  * prepare with three lanes per item (the table of what runs at which size, its thresholds and the asserts that pin
  * them: csrc/kernels.hip, verify_route_of);
  * 1: the full-length evaluation of S*B - t*A (four lanes per item up to 2^14 items); 2: the half-length one with one
  * lane per item whatever the size; 3: the arrangement of 24 577 .. 2^18 - 1 items at any size below 2^18 - a pass of
- * 2^18 items or more has no such arrangement and takes the full-length route of algo 1.  With off-curve keys
+ * 2^18 items or more has no such arrangement and takes the full-length route of algo 1; 4: the arrangement of passes of
+ * 2^19 items or more (balanced pairs, 33 windows) from one item on.  With off-curve keys
  * rejected (eddsa_amd_set_offcurve_mode(0)) every pass takes the full-length route, whatever is set here. */
 EDDSA_AMD_DECL void eddsa_amd_set_verify_algo(int algo);
 /* items of the first chunk of a host-pointer call and the cap of its later chunks; 0 = the defaults: the first chunk 2^16

@@ -62,7 +62,8 @@ EDDSA_PROBE_DECL int eddsa_amd_probe_layer(int op, int form, uint8_t *out, size_
 
 /* the device's search for the half-length pair (u, v), v = u*t mod 8l, on n given scalars t < l (32 bytes each, host
  * memory); out48 per item: v (20 bytes, little-endian) | |u| (20) | u < 0 (1) | found (1) | 6 bytes of padding.
- * wide != 0: |u|, v < 2^138 (what passes below 2^18 items use) instead of 2^134 */
+ * wide = 0: |u|, v < 2^134; 1 (any value but 0 and 2): < 2^138 (what passes below 2^19 items use); 2: the balanced search of
+ * full-size passes, both at most B33 = 0x777...7 (33 nibbles: 33 windows) */
 EDDSA_PROBE_DECL int eddsa_amd_probe_halve(uint8_t *out48, const uint8_t *t32, size_t n, int wide);
 
 #ifdef __cplusplus

@@ -256,17 +256,19 @@ def set_verify_equation(cofactored=False):
 def set_verify_algo(algo=0):
     """0 (default): half-length scalars (four lanes per item up to 24 576 items, one above); 1: always full-length;
     2: half-length with one lane per item whatever the size; 3: the arrangement of 24 577 .. 2^18 items (three-lane
-    preparation, one-lane evaluation) at any size below 2^18.  Same verdicts; a measurement and test aid."""
+    preparation, one-lane evaluation) at any size below 2^18; 4: the arrangement of full-size passes (balanced pairs, 33 windows)
+    at any size.  Same verdicts; a measurement and test aid."""
     _hooks().eddsa_amd_set_verify_algo(int(algo))
 
 
 def debug_halve(ts, wide=False):
-    """diagnostic: the device's pair search on scalars t (ints below l); returns a list of (found, u, v)"""
+    """diagnostic: the device's pair search on scalars t (ints below l); returns a list of (found, u, v).  wide: False = pairs
+    below 2^134, True = below 2^138, 2 = the balanced search of full-size passes (both up to B33, 33 windows)"""
     n = len(ts)
     tin = np.frombuffer(b"".join(int(t).to_bytes(32, "little") for t in ts), np.uint8).copy()
     out = np.zeros(48 * max(n, 1), np.uint8)
     _check(probe_library().eddsa_amd_probe_halve(out.ctypes.data_as(ctypes.c_void_p), tin.ctypes.data_as(ctypes.c_void_p), _c_size(n),
-                                                 ctypes.c_int(int(bool(wide)))), "eddsa_amd_probe_halve")
+                                                 ctypes.c_int(2 if wide == 2 and wide is not True else int(bool(wide)))), "eddsa_amd_probe_halve")
     res = []
     for i in range(n):
         row = out[48 * i:48 * i + 48].tobytes()

@@ -1457,11 +1457,12 @@ out:
 
 /* Which evaluation ed25519_verify* uses (same verdicts; a measurement and test aid).  0 (default): half-length
  * scalars (csrc/halve.h), four lanes per item up to 2^15 items and one above; 1: full-length windows always;
- * 2: half-length scalars with one lane per item always. */
+ * 2: half-length scalars with one lane per item always; 3: the mid-size arrangement below 2^18 items; 4: the arrangement of
+ * full-size passes (balanced pairs, 33 windows) at any size.  Any other value: 0. */
 void eddsa_amd_set_verify_algo(int algo)
 {
     pthread_rwlock_wrlock(&g_table);
-    g_verify_algo = algo >= 1 && algo <= 3 ? algo : 0;
+    g_verify_algo = algo >= 1 && algo <= 4 ? algo : 0;
     pthread_rwlock_unlock(&g_table);
 }
 

@@ -14,6 +14,15 @@
 // candidates examined, or whose expansion has a quotient of 31 bits or more before that which the Lehmer rounds
 // have not already used up in partial steps (together about 1 in 10^4 random t), are handed to the exact path like off-curve keys.
 //
+// Three searches, each with its count of signed four-bit windows (kernels.hip: verify_route_of says which pass takes which):
+//   halve_scalar_lane<134>   |u|, v < 2^134, 34 windows   keyed passes of 2^19 items and more, unkeyed ones of up to 256
+//   halve_scalar_lane<138>   |u|, v < 2^138, 35 windows   the passes between (2 give-ups in 10^7)
+//   halve_balanced_lane      |u|, v <= B33,  33 windows   unkeyed passes of 2^19 items and more (1.9 give-ups in 10^3); the floor:
+//                                                         the lattice of the pairs has determinant 2^255, 32 windows hold 2^126.9
+// The first two stop at the first remainder below their bound, whose cofactor is then about ten bits shorter than the bound; the
+// third stops where remainder and cofactor are of one size and knows a way out of an even cofactor, which a bound with no bits
+// to spare needs (with the first rule a bound of 2^131 gives up on 6 t in 10^3).
+//
 // Public data only (verification): control flow and timing depend on t.
 #pragma once
 #include "sc25519.h"
@@ -155,9 +164,14 @@ constexpr int HALF_LEHMER_MIN_BITS = 151;        // rounds run while both remain
 // legitimate (possibly partial) Euclidean step and the true remainders stay nonnegative.  A half-step is refused
 // when it cannot be shown to leave its remainder above 2^141 - nothing that halve_scalar_lane's rule would have
 // to examine (remainders below 2^134, or 2^138) is ever produced here; the plain loop does the last bits.
-// Returns whether anything was applied.
+// Returns whether anything was applied.  FLOOR_BITS: that floor; 141 for halve_scalar_lane, 129 for halve_balanced_lane,
+// which examines nothing above 2^128.
+ED_DEV constexpr double halve_pow2(int bits) { double d = 1.0; for (int k = 0; k < bits; k++) d *= 2.0; return d; }
+static_assert(halve_pow2(141) == 0x1p141 && halve_pow2(129) == 0x1p129, "exact powers of two");
+template <int FLOOR_BITS = 141>
 ED_DEV bool halve_lehmer_round(uint32_t r0[8], uint32_t r1[8], uint32_t u0[5], uint32_t u1[5], double& d0, double& d1) {
   const double E = (d0 > d1 ? d0 : d1) * 0x1p-24;
+  constexpr double FLOOR = halve_pow2(FLOOR_BITS);
   double y0 = d0, y1 = d1, a0 = 1.0, b0 = 0.0, a1 = 0.0, b1 = 1.0;
   bool progress = false, live = true;
   for (int it = 0; it < 40 && live; it++) {
@@ -165,12 +179,12 @@ ED_DEV bool halve_lehmer_round(uint32_t r0[8], uint32_t r1[8], uint32_t u0[5], u
     {                                            // R0' by R1'
       const double q = __builtin_floor(halve_ratio(y0 - E, y1 + E) * (1.0 - 0x1p-40));
       const double na = __builtin_fma(q, a1, a0), nb = __builtin_fma(q, b1, b0), ny = __builtin_fma(-q, y1, y0);
-      if (q >= 1.0 && na < 0x1p24 && nb < 0x1p24 && ny - E >= 0x1p141) { a0 = na; b0 = nb; y0 = ny; any = true; }
+      if (q >= 1.0 && na < 0x1p24 && nb < 0x1p24 && ny - E >= FLOOR) { a0 = na; b0 = nb; y0 = ny; any = true; }
     }
     {                                            // R1' by R0'
       const double q = __builtin_floor(halve_ratio(y1 - E, y0 + E) * (1.0 - 0x1p-40));
       const double na = __builtin_fma(q, a0, a1), nb = __builtin_fma(q, b0, b1), ny = __builtin_fma(-q, y0, y1);
-      if (q >= 1.0 && na < 0x1p24 && nb < 0x1p24 && ny - E >= 0x1p141) { a1 = na; b1 = nb; y1 = ny; any = true; }
+      if (q >= 1.0 && na < 0x1p24 && nb < 0x1p24 && ny - E >= FLOOR) { a1 = na; b1 = nb; y1 = ny; any = true; }
     }
     live = any;
     progress = progress || any;
@@ -269,6 +283,140 @@ ED_DEV bool halve_scalar_lane(uint32_t vw[5], uint32_t uw[5], bool& uneg, const 
     usel[k] = which ? u1[k] : u0[k];
   }
   halve_magnitude<BITS>(uw, uneg, usel);
+  return good;
+}
+
+// ---- the balanced search: pairs that fit 33 windows ----
+// B33 = 7 (16^33 - 1) / 15 = 0x777...7 (33 nibbles), about 2^130.9: the largest value whose recoding into signed four-bit
+// digits (+ 0x88...8, lanes.h) leaves every window above 32 at digit 0.  The lattice {(u, v): u t = v mod 8l} has determinant
+// 2^255, so no bound below 2^127.5 can be met by every t, and a 32-window bound (2^126.9) by hardly any: 33 is the floor.
+constexpr int HALF_WINDOWS_BALANCED = 33;
+constexpr int HALF_BITS_BALANCED = 131;          // the template argument that selects this search where a bound is one (B33 < 2^131)
+ED_DEV constexpr uint32_t halve_B33(int i) { return i < 4 ? 0x77777777u : i == 4 ? 0x7u : 0u; }
+// the highest window with a nonzero digit in the recoding of B33 + plus (plus = 0, 1), the digits as verify_half_main_lane reads them
+constexpr int halve_b33_top_window(uint32_t plus) {
+  int top = -1;
+  uint64_t c = plus;
+  for (int k = 0; k < 8; k++) {
+    c += (uint64_t)halve_B33(k) + 0x88888888u;
+    const uint32_t w = (uint32_t)c;
+    c >>= 32;
+    for (int n = 0; n < 8; n++)
+      if ((int)((w >> (4 * n)) & 15u) - 8 != 0) top = 8 * k + n;
+  }
+  return c == 0 ? top : 64;
+}
+static_assert(halve_b33_top_window(0) == HALF_WINDOWS_BALANCED - 1 && halve_b33_top_window(1) == HALF_WINDOWS_BALANCED,
+              "B33 fits 33 windows, B33 + 1 does not");
+static_assert(HALF_WINDOWS_BALANCED == HALF_BITS_BALANCED / 4 + 1, "the template argument names the bound's window count like the other two");
+
+// a <= B33 for a W-word number
+template <int W>
+ED_DEV bool halve_fits_b33(const uint32_t a[W]) {
+  int64_t c = 0;
+#pragma unroll
+  for (int k = 0; k < W; k++) { c += (int64_t)halve_B33(k) - (int64_t)a[k]; c >>= 32; }
+  return c == 0;                                 // no borrow: B33 - a >= 0
+}
+
+constexpr int HALF_BALANCED_STOP_BITS = 128;     // the search stops at the first remainder below 2^128
+// The Lehmer rounds must not produce a remainder below the stop, and nothing above it is examined: their floor is one bit above
+// it, and a round is started only with ten bits to gain, as 151 stands to 141 (a round costs what three plain iterations do).
+// (Measured with the floor seven bits above the stop as 141 stands to 134, 135 / 145: two more plain iterations per item and
+// 0.03-0.06 ms on a pass of 2^20: profiles/verify_balanced_pairs.txt.)
+constexpr int HALF_BALANCED_LEHMER_FLOOR = 129, HALF_BALANCED_LEHMER_MIN_BITS = 139;
+static_assert(HALF_BALANCED_LEHMER_FLOOR > HALF_BALANCED_STOP_BITS && HALF_BALANCED_LEHMER_MIN_BITS == HALF_BALANCED_LEHMER_FLOOR + HALF_LEHMER_MIN_BITS - 141,
+              "no round reaches below the stop; the rounds' two thresholds keep their distance");
+// t (< l) -> v, |u| (five words each, both <= B33, u odd), uneg = (u < 0) with v = u t (mod 8 l); false when the candidates
+// hold no such pair (1.7 t in 10^3).  halve_scalar_lane takes the first remainder below its bound, which leaves |u| ten bits
+// shorter than v; a bound of 33 windows has no room for that.  Here the search runs to the first remainder r_k < 2^128 (then
+// |u_k| <= 8l / r_(k-1) < 2^127: both fit) and takes (u_k, r_k) when u_k is odd.  When it is even, u_(k-1) is odd and so is
+// every u_(k-1) - j u_k: the candidates are the pairs (u_(k-1) - j u_k, r_(k-1) - j r_k), j = 0 (the step before), 1, 2, ...
+// (partial steps) up to the quotient (the step after), in that order.  Their remainders fall and their cofactors grow with j,
+// so the first j whose remainder is <= B33 decides: j = 0 when r_(k-1) <= B33, else floor((r_(k-1) - B33 - 1) / r_k) + 1.  (The
+// step after is never that one: the last partial step before it leaves r_k + r_(k+1) < 2^129 < B33.)  Where that candidate's
+// cofactor does not fit, no completed or partial step with an odd cofactor fits - earlier ones have larger remainders, later
+// ones larger cofactors - so the result is a function of t alone and the give-ups are those of a search over all of them.
+ED_DEV bool halve_balanced_lane(uint32_t vw[5], uint32_t uw[5], bool& uneg, const uint32_t tw[8]) {
+  uint32_t r0[8], r1[8], u0[5], u1[5];
+#pragma unroll
+  for (int k = 0; k < 8; k++) { r0[k] = halve_N(k); r1[k] = tw[k]; }
+#pragma unroll
+  for (int k = 0; k < 5; k++) { u0[k] = 0; u1[k] = 0; }
+  u1[0] = 1;
+  // hit: a completed step has left a remainder below 2^128; which = 1: it is r1 (the step before: r0), 0: the other way round
+  bool hit = halve_below(r1, HALF_BALANCED_STOP_BITS), bad = false;
+  int which = 1;
+  double d0 = halve_to_double(r0), d1 = halve_to_double(r1);
+  for (int round = 0; round < 8; round++) {
+    if (hit || halve_below(r0, HALF_BALANCED_LEHMER_MIN_BITS) || halve_below(r1, HALF_BALANCED_LEHMER_MIN_BITS)) break;
+    if (!halve_lehmer_round<HALF_BALANCED_LEHMER_FLOOR>(r0, r1, u0, u1, d0, d1)) break;
+    HALVE_COUNT(0);
+  }
+  // the plain loop of halve_scalar_lane; its `done` is hit || bad here
+  bool act = !hit && !halve_less(r0, r1);
+  for (int it = 0; it < 160; it++) {
+    if (hit || bad) break;
+    HALVE_COUNT(1);
+    {                                            // r0 by r1
+      if (halve_reduce(r0, u0, r1, u1, d0, d1, act)) bad = true;
+      d0 = halve_to_double(r0);
+      const bool lt = halve_less(r0, r1);
+      if (!bad && act && lt && halve_below(r0, HALF_BALANCED_STOP_BITS)) { hit = true; which = 0; }
+      act = !hit && !bad && lt;
+    }
+    {                                            // r1 by r0
+      if (halve_reduce(r1, u1, r0, u0, d1, d0, act)) bad = true;
+      d1 = halve_to_double(r1);
+      const bool lt = halve_less(r1, r0);
+      if (!bad && act && lt && halve_below(r1, HALF_BALANCED_STOP_BITS)) { hit = true; which = 1; }
+      act = !hit && !bad && !halve_less(r0, r1);
+    }
+  }
+  // (ra, ua): the step before, (rb, ub): the hit
+  uint32_t ra[8], rb[8], ua[5], ub[5];
+#pragma unroll
+  for (int k = 0; k < 8; k++) { ra[k] = which ? r0[k] : r1[k]; rb[k] = which ? r1[k] : r0[k]; }
+#pragma unroll
+  for (int k = 0; k < 5; k++) { ua[k] = which ? u0[k] : u1[k]; ub[k] = which ? u1[k] : u0[k]; }
+  bool good = hit && !bad;
+  if (good && (ub[0] & 1u) == 0) {
+    if (!halve_fits_b33<8>(ra)) {
+      // (ra, ua) -= (floor(D / rb) + 1) (rb, ub) with D = ra - B33 - 1: D by quotients that never exceed the true one, like
+      // every step above (a second and a third round take what the first one's margin left: at most 2), ...
+      int64_t c = -1;
+#pragma unroll
+      for (int k = 0; k < 8; k++) { c += (int64_t)ra[k] - (int64_t)halve_B33(k); ra[k] = (uint32_t)c; c >>= 32; }
+      ED_CHECK(c == 0);
+      const double db = halve_to_double(rb);
+      for (int it = 0; it < 4 && good && !halve_less(ra, rb); it++)
+        if (halve_reduce(ra, ua, rb, ub, halve_to_double(ra), db, true)) good = false;
+      good = good && halve_less(ra, rb);
+      // ... then the + 1, and B33 + 1 back: the remainder is D mod rb + B33 + 1 - rb, in [B33 + 2 - rb, B33]
+      uint64_t a = 1;
+      c = 0;
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        a += (uint64_t)ra[k] + halve_B33(k);
+        c += (int64_t)(uint32_t)a - (int64_t)rb[k];
+        ra[k] = (uint32_t)c;
+        a >>= 32;
+        c >>= 32;
+      }
+      c = 0;
+#pragma unroll
+      for (int k = 0; k < 5; k++) { c += (int64_t)ua[k] - (int64_t)ub[k]; ua[k] = (uint32_t)c; c >>= 32; }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) rb[k] = ra[k];
+#pragma unroll
+    for (int k = 0; k < 5; k++) ub[k] = ua[k];
+  }
+  // the bounds are checked on what goes out, whichever way it came
+  halve_magnitude<HALF_BITS_BALANCED>(uw, uneg, ub);
+  good = good && halve_fits_b33<8>(rb) && halve_fits_b33<5>(uw) && (uw[0] & 1u) != 0;
+#pragma unroll
+  for (int k = 0; k < 5; k++) vw[k] = rb[k];
   return good;
 }
 

@@ -1305,11 +1305,14 @@ struct verify_route {
   uint32_t main_cost;   // what runs beside k_verify_exact_lane_chain: executed instructions per item, thousands ...
   int main_all;         // ... over the whole pass (1) or over the on-curve list (0)
   bool keyed;           // the keyed forms of the kernels above (keyed_kernels.h): tab_a is the key's table in the key set
+  bool balanced;        // k_verify_halve runs the balanced search (halve.h: pairs up to B33) and k_verify_main_half HALF_WINDOWS_BALANCED windows; never with wide
 };
 static_assert(HALF_WINDOWS_SMALL == HALF_BITS_SMALL / 4 + 1 && HALF_WINDOWS == HALF_BITS / 4 + 1, "a bound is chosen together with its count of signed four-bit windows");
+static_assert(HALF_WINDOWS_BALANCED == HALF_WINDOWS - 1, "the balanced search saves one window of the full-size pass");
 
 // algo (eddsa_amd_set_verify_algo) 0: by size, as listed; 1: full-length windows; 2: half-length, one lane per item; 3: the
-// mid-size arrangement - below PAIR_ONE_MAX_N items: a larger pass has no such arrangement and takes the full-length route.
+// mid-size arrangement - below PAIR_ONE_MAX_N items: a larger pass has no such arrangement and takes the full-length route;
+// 4: the arrangement of full-size passes (balanced pairs, 33 windows) from one item on, for the tests.
 // Reject mode (exact_offcurve == 0) takes the full-length route whatever the algo: the half-length one relies on the exact
 // path for its give-ups.      n                   prepare   halve  pairs / windows  evaluation
 //   algo 0                    <= 256              pair      -      2^134 / 34       window sums + four-lane chain
@@ -1317,17 +1320,18 @@ static_assert(HALF_WINDOWS_SMALL == HALF_BITS_SMALL / 4 + 1 && HALF_WINDOWS == H
 //                             2049 .. 24 576      pair      -      2^138 / 35       half-length, four lanes
 //   algo 0 (3: from 1)        24 577 .. 2^18 - 1  pair      -      2^138 / 35       half-length, one lane, long loop in place
 //   algo 0 (2: from 1)        2^18 .. 2^19 - 1    one lane  yes    2^138 / 35       half-length, one lane
-//   algo 0, 2                 >= 2^19             one lane  yes    2^134 / 34       half-length, one lane
+//   algo 0, 2 (4: from 1)     >= 2^19             one lane  yes    B33 / 33         half-length, one lane (the balanced search: 1.7 give-ups in 10^3)
 //   algo 1; 3 from 2^18; reject mode              one lane  -      -                full-length: four lanes up to 2^14 items, one above
 // A KEYED pass (ed25519_verify_keyed*) takes the one-lane forms whatever its size and whatever the algo - the four-lane and
 // three-lane kernels have no keyed form, so a small keyed pass pays the latency of the one-lane ones:
 //   keyed, modes 1 and 2      < 2^19              one lane  yes    2^138 / 35       half-length, one lane
-//                             >= 2^19             one lane  yes    2^134 / 34       half-length, one lane
+//                             >= 2^19             one lane  yes    2^134 / 34       half-length, one lane (not yet the balanced search)
 //   keyed, reject mode        any                 one lane  -      -                full-length, one lane
 // A keyed pass over a COMB key set (eddsa_amd_keyset_create_comb) is the full-length route with another main kernel, in every
 // off-curve mode and at every size; in modes 1 and 2 the off-list and the exact path work as on the full-length route:
 //   keyed, comb key set       any                 one lane  -      -                both combs, one lane (keyed_lanes.h: verify_comb_lane)
 constexpr uint32_t COMB_MAIN_COST = 127;   // k_verify_main_comb_keyed, executed instructions per item, thousands: the static count of its blocks times their trip counts (profiles/verify_keyed_comb.txt, section 1)
+constexpr uint32_t HALF_MAIN_COST_34 = 226;   // k_verify_main_half<34>, executed instructions per item, thousands; <33> runs one window (4 doublings + 2 cached additions) less
 constexpr verify_route verify_route_of(size_t n, int algo, int exact_offcurve, bool keyed = false, bool comb = false) {
   if (keyed && comb) {
     verify_route c = {PREPARE_ONE, false, false, EVAL_COMB_ONE, 0, 0, COMB_MAIN_COST, 1, true};
@@ -1347,16 +1351,20 @@ constexpr verify_route verify_route_of(size_t n, int algo, int exact_offcurve, b
   // times in four.  Above QUAD_WIDE_MIN_N items the search goes up to 2^138 (2 in 10^7) for a 35th window in every item.
   else if (algo == 0 && n <= HALF_QUAD_MAX_N)
     r = {PREPARE_PAIR, false, n > QUAD_WIDE_MIN_N, n <= EDK_SUMS_MAX_ITEMS ? EVAL_SUMS_QUAD : EVAL_HALF_QUAD, 0, 0, 0, 0};
-  else if (algo == 0 || algo == 2)
-    r = {PREPARE_ONE, true, n < HALF_WIDE_MIN_N, EVAL_HALF_ONE, 0, 0, 0, 0};
+  else if (algo == 0 || algo == 2 || algo == 4)
+    r = {PREPARE_ONE, true, n < HALF_WIDE_MIN_N && algo != 4, EVAL_HALF_ONE, 0, 0, 0, 0};
+  // full-size passes search balanced pairs and run 33 windows (the keyed kernels have no such form yet: 34)
+  r.balanced = r.halve && !r.wide && !keyed;
   // Passes of EXACT_LANE_MIN_N items or more hand a work list of EXACT_LANE_MIN_LISTED entries or more to the one-lane
   // kernels; which form runs is decided on the device (the host does not know the list's length): the other ends at once.
   r.lane_min = n >= EXACT_LANE_MIN_N ? (uint32_t)EXACT_LANE_MIN_LISTED : 0u;
   r.dense = n >= EXACT_DENSE_MIN_N;
-  // (beside the chain: the half-length evaluation over the on-curve list, 226 k instructions per item, or the full-length one
+  // (beside the chain: the half-length evaluation over the on-curve list, 218 or 226 k instructions per item, or the full-length one
   // over the whole pass, 323 k: profiles/pmc_summary.json)
   const bool half_main = r.eval == EVAL_HALF_ONE || r.eval == EVAL_HALF_ONE_LONG;
-  r.main_cost = half_main ? 226u : 323u;
+  // (the half-length figure is that of the 33-window kernel, which config 2 of the profile runs; 34 and 35 windows: HALF_MAIN_COST_34)
+  r.main_cost = half_main ? 218u : 323u;
+  if (half_main && !r.balanced) r.main_cost = HALF_MAIN_COST_34;
   r.main_all = half_main ? 0 : 1;
   r.keyed = keyed;
   return r;
@@ -1369,6 +1377,15 @@ static_assert(route_is(verify_route_of(2048, 0, 1), PREPARE_PAIR, false, true, E
 static_assert(route_is(verify_route_of(24576, 0, 1), PREPARE_PAIR, false, true, EVAL_HALF_QUAD) && route_is(verify_route_of(24577, 0, 1), PREPARE_PAIR, false, true, EVAL_HALF_ONE_LONG), "PAIR_ONE_MIN_N");
 static_assert(route_is(verify_route_of((1 << 18) - 1, 0, 1), PREPARE_PAIR, false, true, EVAL_HALF_ONE_LONG) && route_is(verify_route_of(1 << 18, 0, 1), PREPARE_ONE, true, true, EVAL_HALF_ONE), "PAIR_ONE_MAX_N");
 static_assert(route_is(verify_route_of((1 << 19) - 1, 0, 1), PREPARE_ONE, true, true, EVAL_HALF_ONE) && route_is(verify_route_of(1 << 19, 0, 1), PREPARE_ONE, true, false, EVAL_HALF_ONE), "HALF_WIDE_MIN_N");
+static_assert(verify_route_of(1 << 19, 0, 1).balanced && verify_route_of(1 << 20, 2, 1).balanced && !verify_route_of((1 << 19) - 1, 0, 1).balanced && !verify_route_of((1 << 19) - 1, 2, 1).balanced &&
+              !verify_route_of(256, 0, 1).balanced && !verify_route_of(1 << 20, 1, 1).balanced && !verify_route_of(1 << 20, 3, 1).balanced && !verify_route_of(1 << 20, 0, 0).balanced,
+              "the balanced search: unkeyed half-length passes of HALF_WIDE_MIN_N items or more, nothing else");
+static_assert(route_is(verify_route_of(1, 4, 1), PREPARE_ONE, true, false, EVAL_HALF_ONE) && verify_route_of(1, 4, 1).balanced && verify_route_of(300, 4, 2).balanced && verify_route_of(1 << 20, 4, 1).balanced &&
+              route_is(verify_route_of(300, 4, 0), PREPARE_ONE, false, false, EVAL_FULL_QUAD) && !verify_route_of(300, 4, 0).balanced, "algo 4: the balanced arrangement from one item on; reject mode as ever");
+static_assert(!verify_route_of(1 << 20, 0, 1, true).balanced && !verify_route_of(1 << 20, 4, 1, true).balanced && !verify_route_of(1 << 20, 0, 1, true, true).balanced && verify_route_of(1 << 20, 0, 1, false, true).balanced,
+              "keyed passes keep 34 windows");
+static_assert(verify_route_of(1 << 20, 0, 1).main_cost == 218 && verify_route_of(1 << 19, 2, 1).main_cost == 218 && verify_route_of((1 << 19) - 1, 0, 1).main_cost == HALF_MAIN_COST_34 && verify_route_of(1 << 20, 0, 1).main_all == 0 && verify_route_of(1 << 20, 0, 1, true).main_cost == 226 &&
+              verify_route_of(1 << 20, 0, 1).lane_min == 8192 && verify_route_of(1, 4, 1).lane_min == 0, "the balanced row: its own cost beside the chain, the exact path's hints by size as ever");
 static_assert(route_is(verify_route_of(1 << 14, 1, 1), PREPARE_ONE, false, false, EVAL_FULL_QUAD) && route_is(verify_route_of((1 << 14) + 1, 1, 1), PREPARE_ONE, false, false, EVAL_FULL_ONE), "QUAD_MAIN_MAX_N");
 static_assert(route_is(verify_route_of((1 << 18) - 1, 3, 1), PREPARE_PAIR, false, true, EVAL_HALF_ONE_LONG) && route_is(verify_route_of(1 << 18, 3, 1), PREPARE_ONE, false, false, EVAL_FULL_ONE), "algo 3 ends at PAIR_ONE_MAX_N");
 static_assert(route_is(verify_route_of(1, 3, 1), PREPARE_PAIR, false, true, EVAL_HALF_ONE_LONG) && route_is(verify_route_of(1, 2, 1), PREPARE_ONE, true, true, EVAL_HALF_ONE), "algo 2 and 3 from one item on");
@@ -1586,13 +1603,15 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
   // 4. halve.  Below HALF_WIDE_MIN_N items the pass searches pairs up to 2^138 and runs 35 windows (2 t in 10^7 without a pair
   // instead of 8.5 in 10^5; 3 % more instructions in the main kernel): an item without a short pair goes through the exact
   // path's chain, and beside a main kernel of one or two rounds of resident blocks that chain costs the pass 0.3-0.4 ms (the
-  // SIMDs its waves sit on finish their tiles that much later and the grid has no slack: profiles/r04_small_grid.txt)
+  // SIMDs its waves sit on finish their tiles that much later and the grid has no slack: profiles/r04_small_grid.txt).  From
+  // HALF_WIDE_MIN_N items on an unkeyed pass searches balanced pairs (both values at most B33, halve.h) and runs 33 windows: 1.9 t
+  // in 10^3 without a pair, which the chain beside a full-size main kernel absorbs (profiles/verify_balanced_pairs.txt)
   if (r.halve && r.keyed) {
     const auto k = r.wide ? k_verify_halve_keyed<HALF_BITS_SMALL> : k_verify_halve_keyed<HALF_BITS>;
     EDK_LAUNCH(k, dim3(blocks), dim3(BLOCK), 0, stream, src.sigs, src.sig_stride, ws->digits, ws->hdigits, ws->rtable, ws->flags, ws->onlist, ws->offlist, ws->offcount,
                ws->table, src.ks_table, src.key_idx);
   } else if (r.halve) {
-    const auto k = r.wide ? k_verify_halve<HALF_BITS_SMALL> : k_verify_halve<HALF_BITS>;
+    const auto k = r.wide ? k_verify_halve<HALF_BITS_SMALL> : r.balanced ? k_verify_halve<HALF_BITS_BALANCED> : k_verify_halve<HALF_BITS>;
     EDK_LAUNCH(k, dim3(blocks), dim3(BLOCK), 0, stream, src.sigs, src.sig_stride, ws->digits, ws->hdigits, ws->rtable, ws->flags, ws->onlist, ws->offlist, ws->offcount);
   }
   if (marks) EDK_DO(hipEventRecord(marks[1], stream));
@@ -1643,7 +1662,8 @@ hipError_t edk_verify(uint8_t* ok, const edk_verify_src* srcp, size_t n, const u
         EDK_LAUNCH(kk, dim3(hblocks), dim3(MAIN_HALF_BLOCK), half_lds, stream, ok, ws->hdigits, src.ks_table, src.key_idx, ws->rtable, base16, ws->flags, ws->onlist, ws->offcount);
         break;
       }
-      const auto k = r.eval == EVAL_HALF_ONE_LONG ? k_verify_main_half<HALF_WINDOWS_SMALL, true> : r.wide ? k_verify_main_half<HALF_WINDOWS_SMALL> : k_verify_main_half<HALF_WINDOWS>;
+      const auto k = r.eval == EVAL_HALF_ONE_LONG ? k_verify_main_half<HALF_WINDOWS_SMALL, true> : r.wide ? k_verify_main_half<HALF_WINDOWS_SMALL> :
+                     r.balanced ? k_verify_main_half<HALF_WINDOWS_BALANCED> : k_verify_main_half<HALF_WINDOWS>;
       EDK_LAUNCH(k, dim3(hblocks), dim3(MAIN_HALF_BLOCK), half_lds, stream, ok, ws->hdigits, ws->table, ws->rtable, base16, ws->flags, ws->onlist, ws->offcount);
     } break;
     case EVAL_FULL_QUAD: EDK_LAUNCH(k_verify_main_quad, dim3(quad_blocks), dim3(QUAD_BLOCK), 0, stream, ws->digits, ws->table, base16, ws->acc, n); break;

@@ -381,7 +381,10 @@ enum : uint32_t { HALF_U_NEGATIVE = 1u, HALF_LONG = 2u, HALF_PAIR_REFUSED = 4u }
 static_assert(HALF_STATUS_WORD < HALF_DIGIT_WORDS, "the status word is one of the item's words");
 constexpr int HALF_LONG_WINDOWS = 64;
 
-// tdig / sdig: the digit words k_verify_prepare wrote (t + 0x88.., S mod l + 0x8000..); BITS: halve.h
+// tdig / sdig: the digit words k_verify_prepare wrote (t + 0x88.., S mod l + 0x8000..); BITS: halve.h - 134 or 138, the bound of
+// halve_scalar_lane (34 or 35 windows in verify_half_main_lane), or HALF_BITS_BALANCED: halve_balanced_lane, both values at most
+// B33, for verify_half_main_lane<false, HALF_WINDOWS_BALANCED> (its top window, 32, is no multiple of 4 below 32: it adds no
+// base-point entry, and the eight windows that do carry all sixteen digits of s' as ever)
 template <int BITS = HALF_BITS>
 ED_DEV void verify_half_scalars_lane(uint32_t hd[HALF_DIGIT_WORDS], const uint32_t tdig[8], const uint32_t sdig[8]) {
   uint32_t tw[8], sw[8], vw[5], uw[5], v8[8], u8[8];
@@ -390,7 +393,9 @@ ED_DEV void verify_half_scalars_lane(uint32_t hd[HALF_DIGIT_WORDS], const uint32
   words_sub_pattern(tw, 0x88888888u);
   words_sub_pattern(sw, 0x80008000u);
   bool uneg;
-  bool found = halve_scalar_lane<BITS>(vw, uw, uneg, tw);
+  bool found;
+  if constexpr (BITS == HALF_BITS_BALANCED) found = halve_balanced_lane(vw, uw, uneg, tw);   // both <= B33: 33 windows
+  else found = halve_scalar_lane<BITS>(vw, uw, uneg, tw);
   // The pair search takes its quotients from doubles under hand-derived error margins (halve.h); a wrong pair would be
   // a silent wrong verdict, so the congruence it promises is re-verified here with integers before anything depends
   // on it:  u t = v (mod 8 l)  <=>  W := |u| t - sign(u) v  is divisible by l and by 8 (l is odd).  W (13 words, >= 0

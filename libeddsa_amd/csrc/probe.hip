@@ -40,7 +40,7 @@ __global__ void __launch_bounds__(64) k_probe_comb_image(uint32_t* img, const ui
   comb_image_entry_lane(img + COMB_IMG_ENTRY_WORDS * id, comb, id / COMB_IMG_ENTRIES, id % COMB_IMG_ENTRIES);
 }
 
-// diagnostic (eddsa_amd_probe_halve): halve_scalar_lane on the device for given t; out = v (20 bytes) | |u| (20) |
+// diagnostic (eddsa_amd_probe_halve): halve_scalar_lane (BITS = HALF_BITS_BALANCED: halve_balanced_lane) on the device for given t; out = v (20 bytes) | |u| (20) |
 // u < 0 (1) | found (1) | 6 bytes of padding per item
 template <int BITS>
 __global__ void __launch_bounds__(BLOCK) k_debug_halve(uint8_t* out, const uint8_t* t, size_t n) {
@@ -49,7 +49,9 @@ __global__ void __launch_bounds__(BLOCK) k_debug_halve(uint8_t* out, const uint8
   uint32_t tw[8], vw[5], uw[5];
   load32(tw, t, i, 32);
   bool uneg;
-  const bool found = halve_scalar_lane<BITS>(vw, uw, uneg, tw);
+  bool found;
+  if constexpr (BITS == HALF_BITS_BALANCED) found = halve_balanced_lane(vw, uw, uneg, tw);
+  else found = halve_scalar_lane<BITS>(vw, uw, uneg, tw);
   uint32_t* o = reinterpret_cast<uint32_t*>(out + 48 * i);
 #pragma unroll
   for (int k = 0; k < 5; k++) { o[k] = vw[k]; o[5 + k] = uw[k]; }
@@ -441,7 +443,8 @@ int eddsa_amd_probe_halve(uint8_t* out48, const uint8_t* t32, size_t n, int wide
   PTRY(hipMalloc((void**)&d_t, n * 32));
   PTRY(hipMalloc((void**)&d_o, n * 48));
   PTRY(hipMemcpy(d_t, t32, n * 32, hipMemcpyHostToDevice));
-  if (wide) hipLaunchKernelGGL(k_debug_halve<HALF_BITS_SMALL>, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, nullptr, d_o, d_t, n);
+  if (wide == 2) hipLaunchKernelGGL(k_debug_halve<HALF_BITS_BALANCED>, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, nullptr, d_o, d_t, n);
+  else if (wide) hipLaunchKernelGGL(k_debug_halve<HALF_BITS_SMALL>, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, nullptr, d_o, d_t, n);
   else hipLaunchKernelGGL(k_debug_halve<HALF_BITS>, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, nullptr, d_o, d_t, n);
   PTRY(hipGetLastError());
   PTRY(hipMemcpy(out48, d_o, n * 48, hipMemcpyDeviceToHost));
