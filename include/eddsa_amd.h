@@ -721,6 +721,55 @@ RFC8032_EDDSA_DECL int ed25519_point_classify_batch(uint8_t *cls, const uint8_t 
 RFC8032_EDDSA_DECL int ed25519_point_classify_batch_dev(uint8_t *cls, const uint8_t *points /* device */, size_t n, void *stream);
 RFC8032_EDDSA_DECL int eddsa_amd_keyset_classify(const eddsa_amd_keyset *ks, uint8_t *cls /* host, eddsa_amd_keyset_count(ks) bytes */);
 
+/* ---- DERIVED PUBLIC KEYS: out[i] = [m_i]P_i + [a_i]B, the Edwards counterpart of x25519_batch ----
+ * NOT FOR SECRETS.  The chain's table lookups and additions depend on the scalars' digits, and the scalars lie unwiped in the verify
+ * workspace afterwards.  The inputs are PUBLIC keys and PUBLIC derivation scalars.  Secret scalars belong to signer sets
+ * (eddsa_amd_signer_create_expanded) and to x25519_batch, which are constant-time and wipe what they stage.
+ * For the verifying side of the schemes eddsa_amd_signer_create_expanded names: a watch-only wallet derives BIP32-Ed25519 child
+ * public keys as A' = A + [z]B, a verifier of blinded keys derives A' = [h]A.  Such a party holds no secret, cannot call
+ * eddsa_amd_signer_pubs, and has thousands to millions of keys to derive before it can fill a key set.
+ * Result: out[i] is the canonical RFC 8032 encoding of [m_i]P_i + [a_i]B, where m_i = mul[i] and a_i = add[i] are 32-byte
+ *   little-endian strings read as integers in [0, 2^256): not clamped, not range-checked.
+ * Torsion: the result is the integer multiple for EVERY curve point, points with a small-order component included.  The group has
+ *   8 l elements: a is reduced mod l (B has order l), m is reduced mod 8 l and never mod l - for a P that carries torsion [m]P and
+ *   [m mod l]P are different points.
+ * Absent arrays: mul == NULL means every m_i = 1 (soft derivation, A + [z]B); add == NULL means every a_i = 0 (blinding, [h]A); with
+ *   both NULL the call re-encodes P canonically.  Nothing is read, staged or uploaded for an absent array.
+ * Decoding of points[i]: the reference's permissive import, the rule every verify form applies to a key and the meaning of
+ *   EDDSA_AMD_POINT_ON_CURVE: y is the low 255 bits mod p, and x = 0 takes either sign bit.
+ * Off-curve input: a string that is no curve point gives out[i] = 02 00 .. 00 (EDDSA_AMD_NO_POINT_BYTE0 and 31 zero bytes), the
+ *   string the keyed passes use for "no key".  Its y = 2 is on no curve point, so it can never be a valid result; a key set that
+ *   registers it rejects its items in reject mode and under the cofactored equation.  The neighbours of such an item are unaffected.
+ * Settings: the result depends on the input bytes only.  The off-curve mode, the strict rules and the equation play no part.
+ * Aliasing: `out` may be the very buffer `points` (in-place derivation).  Any other overlap is undefined.
+ * Arguments: packed arrays of any alignment.  n == 0 returns 0; a NULL out or points with n > 0 returns -hipErrorInvalidValue before
+ *   any device is touched.  The device form runs on the device that holds `out`, enqueues on `stream` and returns without
+ *   synchronising.  The host form goes through the staging pipeline like every host-pointer call and is never merged by the
+ *   small-call combiner.  A library built without the HIP translation unit answers -hipErrorNotSupported from both.
+ * Kernels: a pass is three kernels over the verify workspace, in chunks of 2^20 items, ordered against verify passes on the same
+ *   workspace like one of them.  A prepare kernel decodes P, centres m mod 8 l as |m'| <= 4 l with its sign, and writes the digit
+ *   words and the nine-entry table of sign * P; the verify pass's own main kernel, unchanged, walks 64 windows with the table of
+ *   multiples of B; a finish kernel shares one inversion among eight items per lane and encodes.  No existing kernel changed.
+ * Out of scope: constant-time forms; four-lane forms for small passes; _multi and single-item forms; a key-set constructor that
+ *   derives in place (derive into a device buffer and hand it to eddsa_amd_keyset_create_dev); hashing the derivation scalars,
+ *   which is the caller's scheme.
+ * Measured (profiles/point_muladd.txt, tools/point_muladd_rate.py: device-pointer forms, 2^20 items in HBM, one MI355X, the rows
+ *   alternating in one process, seven repeats, repeat spread 0.015-0.022 ms): both arrays given 10.255 ms per pass (102 M keys/s),
+ *   mul only 10.219 ms, add only 10.162 ms; beside them ed25519_verify_batch_dev in off-curve mode 0 over as many valid signatures
+ *   10.382 ms - the muladd pass is 1.2 to 2.1 % faster than the verify pass that runs the same main kernel.  Per kernel (kernel
+ *   trace): k_verify_main 9.18 ms in both passes, k_point_muladd_prepare 1.10 ms against k_verify_prepare's 1.22 ms,
+ *   k_point_muladd_finish 0.164 ms against k_verify_finish's 0.157 ms.  Small passes: 2^16 items 0.814 ms against 0.837 ms for
+ *   that verify pass; 2^7, 2^10 and 2^14 items 0.768, 0.775 and 0.801 ms against 0.452, 0.459 and 0.487 ms - SLOWER, and the
+ *   kernel that costs the time is the one-lane k_verify_main (0.625 ms at 2^10 items: one wave's chain of 252 doublings), where a
+ *   verify pass of up to 2^14 items runs the four-lane k_verify_main_quad (0.299 ms); the four-lane form is out of scope above.
+ *   ed25519_verify_batch_dev in the default mode against the commit before, alternating in fresh processes: 9.088 ms against
+ *   9.084 ms, inside the older build's own repeat spread (9.045-9.120 ms); every older kernel has the older build's metadata, and
+ *   the two new kernels hold 247 and 134 VGPRs without scratch or spills.
+ * (Declared with the macro of the RFC 8032 variants: tests of earlier additions count the EDDSA_AMD_DECL names.) */
+#define EDDSA_AMD_NO_POINT_BYTE0 0x02   /* out[i] = 02 00 .. 00 (32 bytes): "no curve point" */
+RFC8032_EDDSA_DECL int ed25519_point_muladd_batch    (uint8_t *out, const uint8_t *points, const uint8_t *mul, const uint8_t *add, size_t n);
+RFC8032_EDDSA_DECL int ed25519_point_muladd_batch_dev(uint8_t *out, const uint8_t *points, const uint8_t *mul, const uint8_t *add, size_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -591,6 +591,44 @@ def point_classify_batch(points):
                    [(points, 32, "points")], 1, 32).reshape(-1)
 
 
+# what point_muladd_batch writes for a string that is no curve point: EDDSA_AMD_NO_POINT_BYTE0 and 31 zero bytes
+NO_POINT = bytes([0x02]) + bytes(31)
+
+
+def point_muladd_batch(points, mul=None, add=None, out=None):
+    """[mul_i]points_i + [add_i]B as encoded points (include/eddsa_amd.h: ed25519_point_muladd_batch) -> (n, 32) uint8.  mul, add:
+    32-byte little-endian integers in [0, 2^256), public derivation scalars - NOT secrets (the call is not constant-time); None:
+    every mul_i = 1 / every add_i = 0.  A string that is no curve point gives NO_POINT.  bytes / numpy: the host form; CUDA uint8
+    tensors: the device form, on the current stream.  out: None, or `points` itself for in-place derivation."""
+    if out is not None and out is not points:
+        raise ValueError("ed25519_point_muladd_batch: out must be None or points itself")
+    lib = library()
+    given = [(a, nm) for a, nm in ((points, "points"), (mul, "mul"), (add, "add")) if a is not None or nm == "points"]
+    if _is_torch(points):
+        import torch
+        ts = {nm: _torch_check(a, 32, nm) for a, nm in given}
+        n = ts["points"].numel() // 32
+        for nm, t in ts.items():
+            if t.numel() // 32 != n:
+                raise ValueError(f"ed25519_point_muladd_batch: {nm} holds {t.numel() // 32} items, expected {n}")
+        res = ts["points"] if out is not None else torch.empty((n, 32), dtype=torch.uint8, device=ts["points"].device)
+        ptr = lambda nm: _c_ptr(ts[nm].data_ptr()) if nm in ts else None   # noqa: E731
+        _check(lib.ed25519_point_muladd_batch_dev(_c_ptr(res.data_ptr()), ptr("points"), ptr("mul"), ptr("add"), _c_size(n), _stream()),
+               "ed25519_point_muladd_batch_dev")
+        return res.reshape(n, 32)
+    arrs = {nm: _as_np(a, 32, nm) for a, nm in given}
+    n = arrs["points"].size // 32
+    for nm, a in arrs.items():
+        if a.size // 32 != n:
+            raise ValueError(f"ed25519_point_muladd_batch: {nm} holds {a.size // 32} items, expected {n}")
+    if out is not None and (arrs["points"] is not points or not points.flags.writeable):
+        raise ValueError("ed25519_point_muladd_batch: in place needs a writable contiguous uint8 array")
+    res = arrs["points"] if out is not None else np.zeros((n, 32), dtype=np.uint8)
+    ptr = lambda nm: _np_ptr(arrs[nm]) if nm in arrs else None   # noqa: E731
+    _check(lib.ed25519_point_muladd_batch(_np_ptr(res), ptr("points"), ptr("mul"), ptr("add"), _c_size(n)), "ed25519_point_muladd_batch")
+    return res.reshape(n, 32)
+
+
 def ed25519_verify_batch(sigs, pubs, msgs, msg_off=None, msg_len=None):
     """loop of ed25519_verify (reference lib/eddsa.h:52) -> (n,) uint8, 1 = accept.
 

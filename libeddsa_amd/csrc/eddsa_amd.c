@@ -666,6 +666,30 @@ int classify_on(struct engine *e, uint8_t *cls, const uint8_t *points, size_t n,
     return er == hipSuccess ? 0 : -(int)er;
 }
 
+/* edk_point_muladd is a WEAK reference (edk_muladd.h), like edk_point_classify */
+extern __typeof__(edk_point_muladd) edk_point_muladd __attribute__((weak));
+
+/* [m]P + [a]B (include/eddsa_amd.h: ed25519_point_muladd_batch*): chunks of at most CHUNK_MAX items through one slot of the verify
+ * workspace pool, as verify_on walks them - the pass orders itself behind and in front of verify passes on the same slot through the
+ * slot's `free` event (pass_open, pass_close).  It runs k_verify_main over its own digits and table and has no exact path, so it
+ * reports nothing itself; an earlier verify pass's report is taken here as in verify_on */
+int muladd_on(struct engine *e, uint8_t *out, const uint8_t *points, const uint8_t *mul, const uint8_t *add, size_t n, hipStream_t st)
+{
+    int rc = 0;
+    struct pass p;
+    if (n == 0) return 0;
+    if (!edk_point_muladd) return -(int)hipErrorNotSupported;
+    if ((rc = take_async_error(e))) return rc;
+    if ((rc = pass_open(&p, e, n, PASS_WS, st))) return rc;
+    for (size_t done = 0; done < n; done += CHUNK_MAX) {
+        const size_t m = n - done < CHUNK_MAX ? n - done : CHUNK_MAX;
+        TRY(edk_point_muladd(out + 32 * done, points + 32 * done, mul ? mul + 32 * done : NULL, add ? add + 32 * done : NULL, m, e->base16,
+                             &p.v->ws, st));
+    }
+out:
+    return pass_close(&p, rc);
+}
+
 /* Batch verification by random linear combination (reference lib/ed25519-sha512.c:13-14, its TODO;
  * SURVEY 8(f)-3): see include/eddsa_amd.h.  One pass of at most CHUNK_MAX items; larger batches are
  * split into independent sub-batches. */
@@ -1161,6 +1185,18 @@ int ed25519_point_classify_batch_dev(uint8_t *cls, const uint8_t *points, size_t
     if (!edk_point_classify) return -(int)hipErrorNotSupported;
     if ((rc = enter_dev(&c, cls))) return rc;
     return leave_with(&c, classify_on(c.e, cls, points, n, (hipStream_t)stream));
+}
+
+/* [m]P + [a]B (include/eddsa_amd.h): the same order of checks as point classification */
+int ed25519_point_muladd_batch_dev(uint8_t *out, const uint8_t *points, const uint8_t *mul, const uint8_t *add, size_t n, void *stream)
+{
+    struct call c;
+    int rc = 0;
+    if (n == 0) return 0;
+    if (!out || !points) return -(int)hipErrorInvalidValue;
+    if (!edk_point_muladd) return -(int)hipErrorNotSupported;
+    if ((rc = enter_dev(&c, out))) return rc;
+    return leave_with(&c, muladd_on(c.e, out, points, mul, add, n, (hipStream_t)stream));
 }
 
 /* The class bytes of a key set's own keys, where they lie.  No engine is asked for - the kernel reads no table and takes no workspace,

@@ -33,6 +33,7 @@
 #include "edk_keyed.h"
 #include "edk_signer.h"
 #include "edk_classify.h"
+#include "edk_muladd.h"
 
 #ifndef CHUNK_MAX                     /* (tests/fake_hip builds one variant with tiny passes: tests/c/multi_passes.c) */
 #define CHUNK_MAX ((size_t)1 << 20)   /* verify items per workspace pass: 1.6 GB of HBM workspace */
@@ -272,6 +273,9 @@ int pk_to_x_on(struct engine *e, uint8_t *out, const uint8_t *in, size_t n, hipS
 int sk_to_x_on(struct engine *e, uint8_t *out, const uint8_t *in, size_t n, hipStream_t st);
 /* point classification: one class byte per 32-byte string; -hipErrorNotSupported without the HIP translation unit */
 int classify_on(struct engine *e, uint8_t *cls, const uint8_t *points, size_t n, hipStream_t st);
+/* [m]P + [a]B through the verify workspace pool; mul / add NULL: every m = 1 / every a = 0; -hipErrorNotSupported without the HIP
+ * translation unit */
+int muladd_on(struct engine *e, uint8_t *out, const uint8_t *points, const uint8_t *mul, const uint8_t *add, size_t n, hipStream_t st);
 int records_ok(size_t stride, size_t sig_off, size_t pub_off, size_t msg_off, size_t msg_len);
 
 /* host_pipe.c, called by the engine's life cycle and diagnostics in eddsa_amd.c */

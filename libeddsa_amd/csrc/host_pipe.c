@@ -948,6 +948,14 @@ RUN_1IN(run_xbase, xbase_on)
 RUN_1IN(run_pk_to_x, pk_to_x_on)
 RUN_1IN(run_sk_to_x, sk_to_x_on)
 RUN_1IN(run_classify, classify_on)                 /* (one byte out, like a verdict) */
+/* [m]P + [a]B: the points are input 0; an array the caller left out (mul NULL: m = 1, add NULL: a = 0) is no input at all - nothing
+ * is staged or uploaded for it - so the four combinations are four rows, and a row's function says which input is which */
+#define RUN_MULADD(name_, mul_, add_) static int name_(struct engine *e, const struct hjob *j, const struct chunk *c) \
+    { (void)j; return run_done(muladd_on(e, c->d_out, c->d_in[0], mul_, add_, c->m, c->st), c); }
+RUN_MULADD(run_muladd, c->d_in[1], c->d_in[2])
+RUN_MULADD(run_muladd_mul, c->d_in[1], NULL)
+RUN_MULADD(run_muladd_add, NULL, c->d_in[1])
+RUN_MULADD(run_muladd_points, NULL, NULL)
 
 /* The table of operations.  A row says what the pipeline and the combiner need to know of a call: whether small calls may be merged
  * (kind), the widths of its inputs, its chunk sizes, the order of its chunks' kernels and what is wiped - not which form of verify
@@ -968,9 +976,14 @@ RUN_1IN(run_classify, classify_on)                 /* (one byte out, like a verd
  *   OP_SIGN_KEYED        every form over a signer set: 4 bytes of key index per item where the others upload 64 bytes of keys; never
  *                        merged - two small calls may carry different signer sets.  A signing process keeps nothing of a call in the
  *                        staging buffers: which key signed what, and the signatures, are zeroed there like the other operations' secrets
- *   OP_CLASSIFY          ed25519_point_classify_batch: 32 bytes in, one class byte out, nothing secret; never merged */
+ *   OP_CLASSIFY          ed25519_point_classify_batch: 32 bytes in, one class byte out, nothing secret; never merged
+ *   OP_POINT_MULADD      ed25519_point_muladd_batch with both scalar arrays: three 32-byte inputs (points, mul, add), 32 bytes out,
+ *                        nothing secret (public keys and public derivation scalars); never merged; a pass is one long chain kernel
+ *                        between two short ones, so its chunks run in order like the fixed-base operations'
+ *   OP_POINT_MULADD_MUL / _ADD / _POINTS   the same call with add, mul or both NULL: the rows without the absent inputs */
 enum { OP_VERIFY, OP_VERIFY_UNMERGED, OP_VERIFY_RLC, OP_VERIFY_RECORDS, OP_VERIFY_KEYED, OP_VERIFY_KEYED_RLC, OP_SIGN, OP_SIGN_UNMERGED, OP_SIGN_KEYED,
-       OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X, OP_CLASSIFY };
+       OP_X25519, OP_GENPUB, OP_XBASE, OP_PK_TO_X, OP_SK_TO_X, OP_CLASSIFY, OP_POINT_MULADD, OP_POINT_MULADD_MUL, OP_POINT_MULADD_ADD,
+       OP_POINT_MULADD_POINTS };
 #define VERIFY_ROW(kind_, w1_, chunk_, first_) { .n_in = 2, .in_w = { 64, w1_, 0 }, .out_w = 1, .has_msgs = 1, .run = run_verify, .wipe = WIPE_NONE, \
     .chain = 0, .kind = kind_, .chunk = chunk_, .first_chunk = first_, .reports = 1 }
 static const struct op g_ops[] = {
@@ -991,6 +1004,11 @@ static const struct op g_ops[] = {
     [OP_PK_TO_X] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_pk_to_x, .wipe = WIPE_NONE, .chain = 1, .kind = KIND_PK_TO_X },
     [OP_SK_TO_X] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_sk_to_x, .wipe = WIPE_IN0 | WIPE_OUT, .chain = 1, .kind = KIND_SK_TO_X },
     [OP_CLASSIFY] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 1, .run = run_classify, .wipe = WIPE_NONE, .chain = 1, .kind = KIND_NONE },
+    [OP_POINT_MULADD] = { .n_in = 3, .in_w = { 32, 32, 32 }, .out_w = 32, .run = run_muladd, .wipe = WIPE_NONE, .chain = 1, .kind = KIND_NONE },
+    [OP_POINT_MULADD_MUL] = { .n_in = 2, .in_w = { 32, 32, 0 }, .out_w = 32, .run = run_muladd_mul, .wipe = WIPE_NONE, .chain = 1, .kind = KIND_NONE },
+    [OP_POINT_MULADD_ADD] = { .n_in = 2, .in_w = { 32, 32, 0 }, .out_w = 32, .run = run_muladd_add, .wipe = WIPE_NONE, .chain = 1, .kind = KIND_NONE },
+    [OP_POINT_MULADD_POINTS] = { .n_in = 1, .in_w = { 32, 0, 0 }, .out_w = 32, .run = run_muladd_points, .wipe = WIPE_NONE, .chain = 1,
+                                 .kind = KIND_NONE },
 };
 
 /* a call of operation `id` (in1, msgs, msg_off: NULL where the operation has none) */
@@ -1197,6 +1215,17 @@ int ed25519_point_classify_batch(uint8_t *cls, const uint8_t *points, size_t n)
     if (n == 0) return 0;
     if (!cls || !points) return -(int)hipErrorInvalidValue;
     return pipe_run(job(OP_CLASSIFY, cls, points, NULL, NULL, NULL, 0), n);
+}
+
+/* [m]P + [a]B (include/eddsa_amd.h): an empty batch is done and NULLs are refused before any device is asked; the row is chosen by
+ * which scalar arrays the caller gave */
+int ed25519_point_muladd_batch(uint8_t *out, const uint8_t *points, const uint8_t *mul, const uint8_t *add, size_t n)
+{
+    if (n == 0) return 0;
+    if (!out || !points) return -(int)hipErrorInvalidValue;
+    const struct hjob j = { .op = &g_ops[mul && add ? OP_POINT_MULADD : mul ? OP_POINT_MULADD_MUL : add ? OP_POINT_MULADD_ADD : OP_POINT_MULADD_POINTS],
+                            .in = { points, mul ? mul : add, mul ? add : NULL }, .out = out };
+    return pipe_run(j, n);
 }
 
 /* ------------------------------------------------------------------------------------------

@@ -21,10 +21,12 @@
 //   k_keyset_comb_build, k_verify_main_comb_keyed   comb key sets (keyed_kernels.h): a comb per key, both scalars fixed-base
 //   k_signer_build, k_sign_keyed_*            signer sets (signer_kernels.h): the secret scalar, the prefix and A by key index
 //   k_point_classify                          point classification (classify_kernels.h): curve, canonical, small and prime order
+//   k_point_muladd_prepare, _finish           [m]P + [a]B (muladd_kernels.h): set-up and encoding around k_verify_main
 #include "eddsa_kernels.h"
 #include "edk_keyed.h"
 #include "edk_signer.h"
 #include "edk_classify.h"
+#include "edk_muladd.h"
 #include "edk_checked.h"
 #include "kernel_io.h"
 #include "lanes.h"
@@ -1264,6 +1266,7 @@ k_verify_main_sums_quad(uint8_t* ok, const uint32_t* hdigits, const uint32_t* su
 #include "keyed_kernels.h"   // key-set verification: kernels of its own beside the ones above
 #include "signer_kernels.h"  // signer sets: likewise, beside the sign kernels
 #include "classify_kernels.h"  // point classification: one kernel, no workspace
+#include "muladd_kernels.h"  // [m]P + [a]B: a prepare and a finish kernel around k_verify_main
 
 // =============================================================================================
 // launchers (host side of this translation unit)
@@ -1798,6 +1801,20 @@ hipError_t edk_point_classify(uint8_t* cls, const uint8_t* points, size_t n, hip
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_point_classify, dim3(blocks_of(n)), dim3(BLOCK), 0, stream, cls, points, n);
   return hipGetLastError();
+}
+
+// [m]P + [a]B (edk_muladd.h): one pass of at most ws->capacity items through the verify workspace - prepare, the verify pass's own
+// main kernel in its own launch shape, finish.  mul / add NULL: every m = 1 / every a = 0.  Asynchronous on `stream`
+hipError_t edk_point_muladd(uint8_t* out, const uint8_t* points, const uint8_t* mul, const uint8_t* add, size_t n, const uint32_t* base16,
+                            const edk_verify_ws* ws, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (n > ws->capacity) return hipErrorInvalidValue;
+  const unsigned blocks = blocks_of(n);
+  const finish_shape f = finish_shape_of(n);
+  EDK_LAUNCH(k_point_muladd_prepare, dim3(blocks), dim3(BLOCK), 0, stream, points, mul, add, n, ws->digits, ws->table, ws->flags);
+  EDK_LAUNCH(k_verify_main, dim3(blocks), dim3(BLOCK), MAIN_LDS_RESERVE, stream, ws->digits, ws->table, base16, ws->acc);
+  EDK_LAUNCH(k_point_muladd_finish, dim3(f.grid), dim3(BLOCK), 0, stream, out, ws->acc, ws->flags, n, f.k);
+  return hipSuccess;
 }
 
 }  // extern "C"
