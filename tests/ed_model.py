@@ -237,9 +237,15 @@ def torsion_encodings():
 
 # ---------------------------------------------------------------- verification
 
-def verify(sig, pub, msg, prefix=b""):
-    """the reference's cofactorless rule for a key that decodes: the encoding of S B + t (-A) is R, byte for byte"""
+def verify_t(sig, pub, t):
+    """the reference's cofactorless rule for a key that decodes, with the challenge scalar t given: the encoding of
+    S B + t (-A) is R, byte for byte (S is used as its 256 bits say: B has order l, so S and S mod l give the same point)"""
     sig, pub = bytes(sig), bytes(pub)
     a = decode_reference(pub)
     assert a is not None, "a key on no curve point belongs to the exact path, not to this model"
-    return encode(pmul2(num(sig[32:]), B, challenge(sig, pub, msg, prefix), pneg(ext(a)))) == sig[:32]
+    return encode(pmul2(num(sig[32:]), B, t, pneg(ext(a)))) == sig[:32]
+
+
+def verify(sig, pub, msg, prefix=b""):
+    """the same rule with t = SHA-512(prefix | R | A | M) mod l"""
+    return verify_t(sig, pub, challenge(sig, pub, msg, prefix))

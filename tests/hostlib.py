@@ -3,7 +3,8 @@ header's text and a library's exported names.
 tests/host_check/: policy_check.cpp -> test_policy_lane_on_host.py; cofactor_check.cpp -> test_cofactor_lane_on_host.py;
 dom2_check.cpp -> test_dom2_on_host.py; digest_check.cpp -> test_digest_lane_on_host.py; keyed_check.cpp -> test_keyed_on_host.py;
 keyed_comb_check.cpp -> test_keyed_comb_on_host.py; keyed_forms_check.cpp -> test_keyed_forms_on_host.py; keyed_rlc_check.cpp ->
-test_keyed_rlc_on_host.py; signer_check.cpp -> test_sign_keyed_on_host.py; host_check.cpp -> conftest.py's `hostcheck`."""
+test_keyed_rlc_on_host.py; signer_check.cpp -> test_sign_keyed_on_host.py; crafted_check.cpp -> test_crafted_scalars_on_host.py;
+host_check.cpp -> conftest.py's `hostcheck`."""
 import ctypes
 import os
 import re
