@@ -25,11 +25,11 @@ $(BUILD)/kernels.o: $(CSRC)/kernels.hip $(wildcard $(CSRC)/*.h)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(BUILD)/%.o: $(CSRC)/%.c $(CSRC)/engine.h $(CSRC)/eddsa_kernels.h $(CSRC)/edk_keyed.h $(CSRC)/edk_signer.h $(CSRC)/edk_classify.h $(CSRC)/edk_muladd.h $(CSRC)/edk_layout.h include/eddsa.h include/eddsa_amd.h
+$(BUILD)/%.o: $(CSRC)/%.c $(CSRC)/engine.h $(CSRC)/eddsa_kernels.h $(CSRC)/edk_keyed.h $(CSRC)/edk_signer.h $(CSRC)/edk_classify.h $(CSRC)/edk_muladd.h $(CSRC)/edk_scatter.h $(CSRC)/edk_layout.h include/eddsa.h include/eddsa_amd.h
 	@mkdir -p $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(BUILD)/%.dbg.o: $(CSRC)/%.c $(CSRC)/engine.h $(CSRC)/eddsa_kernels.h $(CSRC)/edk_keyed.h $(CSRC)/edk_signer.h $(CSRC)/edk_classify.h $(CSRC)/edk_muladd.h $(CSRC)/edk_layout.h include/eddsa.h include/eddsa_amd.h include/eddsa_amd_debug.h
+$(BUILD)/%.dbg.o: $(CSRC)/%.c $(CSRC)/engine.h $(CSRC)/eddsa_kernels.h $(CSRC)/edk_keyed.h $(CSRC)/edk_signer.h $(CSRC)/edk_classify.h $(CSRC)/edk_muladd.h $(CSRC)/edk_scatter.h $(CSRC)/edk_layout.h include/eddsa.h include/eddsa_amd.h include/eddsa_amd_debug.h
 	@mkdir -p $(BUILD)
 	$(CC) $(CFLAGS) -DEDDSA_AMD_DEBUG_BUILD -c $< -o $@
 

@@ -770,6 +770,62 @@ RFC8032_EDDSA_DECL int eddsa_amd_keyset_classify(const eddsa_amd_keyset *ks, uin
 RFC8032_EDDSA_DECL int ed25519_point_muladd_batch    (uint8_t *out, const uint8_t *points, const uint8_t *mul, const uint8_t *add, size_t n);
 RFC8032_EDDSA_DECL int ed25519_point_muladd_batch_dev(uint8_t *out, const uint8_t *points, const uint8_t *mul, const uint8_t *add, size_t n, void *stream);
 
+/* ---- ITEMS IN PLACE: verify (signature, key, message) triples given by byte offsets into one buffer ----
+ * For callers that hold a buffer of network packets (transactions, votes): a packet carries one message and several (signature, key)
+ * pairs at positions that differ from packet to packet, and all the caller has per item is "signature at byte s, key at byte p,
+ * message at byte m, length l".  The packed forms would make it copy a message once per signer (two items can never share a span of
+ * msg_off[0..n]), and ed25519_verify_records takes one stride and three offsets for the whole call.
+ * Item i consists of three spans of `data`: the signature data[sig_off[i] .. +64), the key data[pub_off[i] .. +32) and the message
+ *   data[msg_off[i] .. +msg_len[i]).  The four index arrays are packed uint32, one entry per item: host memory in the first form, HBM
+ *   in the second, like key_idx.
+ * Verdicts: ok[i] is byte for byte what ed25519_verify_batch returns for those three spans, under the off-curve mode (0, 1, 2), the
+ *   strict rules and the equation in force when each pass is enqueued: the pass runs as a pass of ed25519_verify_digests, whose
+ *   contract says so.
+ * Overlap and alignment: spans may have any alignment; they may overlap each other and the spans of other items - several items
+ *   sharing one message is the point of the call.  `data` is only read.  `ok` must not overlap it.
+ * data_len: the caller vouches for it as the size of the buffer.  data_len >= 2^32 returns -hipErrorInvalidValue, and so does a NULL
+ *   ok, data or index array with n > 0 - both before any device is touched.  n == 0 returns 0.
+ * Spans that leave the buffer (the three conditions are computed in 64 bits, nothing wraps): in the device-pointer form an item with
+ *   sig_off[i] + 64 > data_len, pub_off[i] + 32 > data_len or msg_off[i] + msg_len[i] > data_len gets ok[i] = 0 under every setting;
+ *   no byte of `data` is read for that item, and the verdicts of its neighbours are unaffected.  This is the keyed forms' rule for an
+ *   index outside the set, not the ragged table's "hash the clamped span": an item that is not entirely in the buffer is no item.
+ *   The host-pointer form checks all four arrays first and returns -hipErrorInvalidValue with `ok` untouched, like a bad ragged table.
+ * Reads at the edge: for items inside the buffer the statement at the top of this header about whole-word loads applies unchanged -
+ *   the hashing lane may read the aligned 4-byte words that hold the first and last byte of a span, so up to 3 bytes outside
+ *   [data, data + data_len) lie in the same word as a byte of the buffer.
+ * Other rules: EDDSA_AMD_STALLED, return values, ownership and threading as at the top of this header.  The device-pointer form runs
+ *   on the device that holds `ok`; `data` must live on that device (-hipErrorInvalidValue otherwise).  The call is never merged by the
+ *   small-call combiner.  A library built without the HIP translation unit answers -hipErrorNotSupported from both.
+ * Host-pointer form: a plain wrapper, NOT chunked through the staging pipeline - a chunk of items may refer to any byte of `data`, so
+ *   the buffer has to be resident before the first pass.  It checks the arrays, allocates HBM for `data` and the four arrays on the
+ *   default device, uploads, runs the device form on a stream of its own, downloads `ok`, frees, and reports EDDSA_AMD_STALLED itself.
+ * Kernels: one kernel in front of a digest pass, as k_dom_challenge is for Ed25519ctx / Ed25519ph.  k_scatter_challenge, one lane per
+ *   item, gathers the 64 signature bytes and the 32 key bytes into packed areas of the verify workspace and writes
+ *   SHA-512(R || A || M) beside them; the prepare, halve, main, exact, finish, policy and cofactor kernels then see ordinary packed
+ *   input.  An item outside the buffer is written as the signature 00 .. 00, the digest 00 .. 00 and the key 02 00 .. 00
+ *   (EDDSA_AMD_NO_POINT_BYTE0), which every route rejects.  From 4096 items on the lanes take the items longest
+ *   message first.  The signature area costs 64 bytes of HBM per item of a workspace's capacity and exists only in a workspace that
+ *   has served a scattered pass.  No existing kernel changed.
+ * Out of scope: _rlc, keyed (key_idx in place of pub_off), digest, ctx / ph and _multi forms of the scattered call; 64-bit offsets; a
+ *   streaming host pipeline for the host-pointer form.
+ * Measured (profiles/verify_scattered.txt, tools/scattered_rate.py): device-pointer forms, 2^20 valid items with 32-byte messages in HBM, one
+ *   MI355X, the rows alternating in one process, seven repeats, repeat spread 0.03-0.11 ms): ed25519_verify_batch_dev over the items
+ *   packed 9.330 ms per pass; ed25519_verify_scattered_dev over the same items as 128-byte packets 9.507 ms (+1.9 %), with 8
+ *   signatures sharing each message 9.509 ms (+1.9 %); ed25519ctx_verify_batch_dev, the existing form with a front kernel, 9.569 ms
+ *   (+2.6 %) - the expectation was that form's 2 %.  Small passes, packed against scattered: 2^7 items 0.239 / 0.250 ms, 2^10
+ *   0.254 / 0.269 ms, 2^14 0.319 / 0.351 ms (+10 %: the order of length adds four small launches from 4096 items on), 2^16
+ *   0.638 / 0.663 ms.  The host form from ordinary memory, host to host: 16.21 ms against 10.66 ms for ed25519_verify_batch through
+ *   the staging pipeline - 52 % SLOWER, the price of the plain wrapper above.  ed25519_verify_batch_dev against the commit before,
+ *   alternating in fresh processes: 9.326 ms against 9.342 ms, inside the older build's own repeat spread (9.279-9.400 ms); every
+ *   older kernel has the older build's metadata, and k_scatter_challenge holds 110 VGPRs without scratch or spills.
+ * (Declared with the macro of the RFC 8032 variants: tests of earlier additions count the EDDSA_AMD_DECL names.) */
+RFC8032_EDDSA_DECL int ed25519_verify_scattered    (uint8_t *ok, const uint8_t *data, size_t data_len,
+                                                    const uint32_t *sig_off, const uint32_t *pub_off,
+                                                    const uint32_t *msg_off, const uint32_t *msg_len, size_t n);
+RFC8032_EDDSA_DECL int ed25519_verify_scattered_dev(uint8_t *ok, const uint8_t *data, size_t data_len,
+                                                    const uint32_t *sig_off, const uint32_t *pub_off,
+                                                    const uint32_t *msg_off, const uint32_t *msg_len, size_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

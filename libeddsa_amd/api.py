@@ -774,6 +774,46 @@ def ed25519_verify_records(records, sig_off, pub_off, msg_off, msg_len):
     return ok
 
 
+def ed25519_verify_scattered(data, sig_off, pub_off, msg_off, msg_len):
+    """loop of ed25519_verify over items given by byte offsets into one buffer (include/eddsa_amd.h: ed25519_verify_scattered):
+    item i's 64-byte signature lies at data[sig_off[i]:], its 32-byte key at data[pub_off[i]:] and its message at
+    data[msg_off[i]:msg_off[i] + msg_len[i]]; spans may have any alignment, overlap and be shared between items -> (n,) uint8,
+    1 = accept.  numpy (data uint8, the four arrays uint32): the host form, which refuses an item that leaves the buffer; CUDA tensors
+    on one device (the four arrays int32, read as unsigned like key_idx, or uint32): the device form on the current stream, where
+    such an item gets 0."""
+    name = "ed25519_verify_scattered"
+    lib = library()
+    given = ((sig_off, "sig_off"), (pub_off, "pub_off"), (msg_off, "msg_off"), (msg_len, "msg_len"))
+    if _is_torch(data):
+        import torch
+        data = _torch_check(data, 0, "data")
+        for a, nm in given:
+            if not _is_torch(a) or a.dtype not in (torch.int32, torch.uint32) or not a.is_cuda or not a.is_contiguous():
+                raise ValueError(f"{name}: {nm}: expected contiguous int32 or uint32 offsets on the device")
+            if a.device != data.device:
+                raise ValueError(f"{name}: {nm} is on {a.device}, data on {data.device}")
+            if a.numel() != sig_off.numel():
+                raise ValueError(f"{name}: {nm} holds {a.numel()} entries, expected {sig_off.numel()}")
+        n = sig_off.numel()
+        ok = torch.empty((n,), dtype=torch.uint8, device=data.device)
+        _check(lib.ed25519_verify_scattered_dev(_c_ptr(ok.data_ptr()), _c_ptr(data.data_ptr()), _c_size(data.numel()),
+                                                *(_c_ptr(a.data_ptr()) for a, _ in given), _c_size(n), _stream()), name)
+        return ok
+    data = _as_np(data, 0, "data")
+    arrs = []
+    for a, nm in given:
+        a = np.ascontiguousarray(np.asarray(a))
+        if a.dtype != np.uint32:
+            raise ValueError(f"{name}: {nm}: expected uint32 offsets")
+        if arrs and a.size != arrs[0].size:
+            raise ValueError(f"{name}: {nm} holds {a.size} entries, expected {arrs[0].size}")
+        arrs.append(a)
+    n = arrs[0].size
+    ok = np.zeros((n,), dtype=np.uint8)
+    _check(lib.ed25519_verify_scattered(_np_ptr(ok), _np_ptr(data), _c_size(data.size), *(_np_ptr(a) for a in arrs), _c_size(n)), name)
+    return ok
+
+
 def ed25519_sign_batch(secs, pubs, msgs, msg_off=None, msg_len=None):
     """loop of ed25519_sign (reference lib/eddsa.h:47) -> (n, 64) uint8"""
     return _run_items("ed25519_sign_batch", [(secs, 32, "secs"), (pubs, 32, "pubs")], msgs, (64,), msg_off=msg_off, msg_len=msg_len)

@@ -94,12 +94,14 @@ static void ws_release(struct vslot *v)
     if (v->ws.sums) HIP_NOTE(hipFree(v->ws.sums));
     if (v->ws.domdig) HIP_NOTE(hipFree(v->ws.domdig));
     if (v->ws.keybytes) HIP_NOTE(hipFree(v->ws.keybytes));
+    if (v->ws.gsigs) HIP_NOTE(hipFree(v->ws.gsigs));
     v->ws.capacity = 0;
     v->ws.digits = v->ws.table = v->ws.acc = v->ws.offlist = v->ws.offcount = v->ws.exact_pad = NULL;
     v->ws.hdigits = v->ws.rtable = v->ws.sums = v->ws.onlist = v->ws.perm = v->ws.lenbins = NULL;
     v->ws.flags = NULL;
     v->ws.domdig = NULL;
     v->ws.keybytes = NULL;
+    v->ws.gsigs = NULL;
 }
 
 /* bytes of the two secret-bearing buffers of a fixed-base workspace of `cap` items */
@@ -504,13 +506,29 @@ static edk_verify_src src_at(const edk_verify_src *all, size_t n, size_t done)
 {
     edk_verify_src src = *all;
     if (all->msg_off && !all->msg_end) src.msg_end = all->msg_off + n;   /* the kernels clamp every span into [0, msg_off[n]) */
-    src.sigs += done * all->sig_stride;
-    if (all->pubs) src.pubs += done * all->pub_stride;   /* (a keyed pass has none) */
-    if (all->msg_off) src.msg_off += done; else src.msgs += done * all->msg_stride;
+    if (all->sc_data) {   /* scattered: the chunk's four index arrays; its packed arrays are the workspace's (verify_on) */
+        src.sc_sig_off += done; src.sc_pub_off += done; src.sc_msg_off += done; src.sc_msg_len += done;
+    } else {
+        src.sigs += done * all->sig_stride;
+        if (all->pubs) src.pubs += done * all->pub_stride;   /* (a keyed pass has none) */
+        if (all->msg_off) src.msg_off += done; else src.msgs += done * all->msg_stride;
+    }
     if (all->key_idx) src.key_idx += done;   /* keyed passes: the chunk's indices are the chunk's */
     src.policy = g_verify_policy;   /* read where the pass is enqueued, like g_offcurve_mode */
     src.equation = g_verify_equation;
     return src;
+}
+
+/* edk_scatter_challenge is a WEAK reference (edk_scatter.h), like edk_point_classify and edk_point_muladd further down */
+extern __typeof__(edk_scatter_challenge) edk_scatter_challenge __attribute__((weak));
+extern __typeof__(edk_scatter_spans_inside) edk_scatter_spans_inside __attribute__((weak));
+
+/* caller holds e->lk, inside a pass on the slot: the area the front kernel of a scattered pass gathers the signatures into, 64 bytes
+ * per item of the slot's capacity.  Only a slot that serves such a pass ever holds one; ws_release frees it with the slot's other
+ * buffers, so one that exists fits the capacity.  (Fresh memory: nothing that is queued on the slot uses it.) */
+static hipError_t gsigs_reserve(struct vslot *v)
+{
+    return v->ws.gsigs ? hipSuccess : hipMalloc((void **)&v->ws.gsigs, v->ws.capacity * 64);
 }
 
 /* both verify forms */
@@ -520,15 +538,22 @@ int verify_on(struct engine *e, uint8_t *ok, const edk_verify_src *all, size_t n
     struct pass p;
     if (n == 0) return 0;
     if ((rc = take_async_error(e))) return rc;   /* an earlier pass's kernels gave up: see engine.h */
+    if (all->sc_data && !edk_scatter_challenge) return -(int)hipErrorNotSupported;
     if ((rc = pass_open(&p, e, n, PASS_WS, st))) return rc;
+    if (all->sc_data) TRY(gsigs_reserve(p.v));
     p.v->ws.exact_offcurve = pass_offcurve_mode();
     p.v->ws.comb = e->comb;
     p.v->ws.algo = p.v->ws.exact_offcurve ? g_verify_algo : 1;   /* the reject mode has no exact path for the items the pair search gives up on */
     for (size_t done = 0; done < n; done += CHUNK_MAX) {
         const size_t m = n - done < CHUNK_MAX ? n - done : CHUNK_MAX;
-        const edk_verify_src src = src_at(all, n, done);
+        edk_verify_src src = src_at(all, n, done);
         hipEvent_t *marks = NULL;
         if (g_profiling && e->marks_used < MARK_SLOTS) marks = e->marks[e->marks_used++];
+        if (src.sc_data) {   /* scattered: gather and hash in front, then the digest pass over what that left in the slot */
+            TRY(edk_scatter_challenge(src.sc_data, src.sc_data_len, src.sc_sig_off, src.sc_pub_off, src.sc_msg_off, src.sc_msg_len, m,
+                                      &p.v->ws, st));
+            src.sigs = p.v->ws.gsigs; src.pubs = p.v->ws.keybytes; src.msgs = p.v->ws.domdig;
+        }
         TRY(edk_verify(ok + done, &src, m, e->base16, &p.v->ws, marks, done + CHUNK_MAX >= n ? bulk_done : NULL, bulk_early, st));
     }
 out:
@@ -1197,6 +1222,72 @@ int ed25519_point_muladd_batch_dev(uint8_t *out, const uint8_t *points, const ui
     if (!edk_point_muladd) return -(int)hipErrorNotSupported;
     if ((rc = enter_dev(&c, out))) return rc;
     return leave_with(&c, muladd_on(c.e, out, points, mul, add, n, (hipStream_t)stream));
+}
+
+/* items by byte offsets into one buffer (include/eddsa_amd.h: ed25519_verify_scattered*).  Both forms refuse the same arguments in
+ * the same order before any device is asked */
+static int scattered_open(const uint8_t *ok, const uint8_t *data, size_t data_len, const uint32_t *sig_off, const uint32_t *pub_off,
+                          const uint32_t *msg_off, const uint32_t *msg_len, size_t n)
+{
+    if (n == 0) return 1;
+    if (!ok || !data || !sig_off || !pub_off || !msg_off || !msg_len) return -(int)hipErrorInvalidValue;
+    if ((uint64_t)data_len > (uint64_t)UINT32_MAX) return -(int)hipErrorInvalidValue;
+    if (!edk_scatter_challenge || !edk_scatter_spans_inside) return -(int)hipErrorNotSupported;
+    return 0;
+}
+
+int ed25519_verify_scattered_dev(uint8_t *ok, const uint8_t *data, size_t data_len, const uint32_t *sig_off, const uint32_t *pub_off,
+                                 const uint32_t *msg_off, const uint32_t *msg_len, size_t n, void *stream)
+{
+    struct call c;
+    int rc = scattered_open(ok, data, data_len, sig_off, pub_off, msg_off, msg_len, n);
+    if (rc) return rc < 0 ? rc : 0;
+    int dev = -1, data_dev = -1;
+    if ((rc = device_of(ok, &dev)) || (rc = device_of(data, &data_dev))) return rc;
+    if (dev != data_dev) return -(int)hipErrorInvalidValue;   /* the lanes read `data` byte by byte: it lives where the pass runs */
+    if ((rc = enter(&c, dev))) return rc;
+    const edk_verify_src src = verify_src_scattered(data, data_len, sig_off, pub_off, msg_off, msg_len);
+    return leave_with(&c, verify_on(c.e, ok, &src, n, (hipStream_t)stream, NULL, 0));
+}
+
+/* The host-pointer form: a plain wrapper, not a job of the staging pipeline - a chunk of items may refer to any byte of `data`, so
+ * the whole buffer is resident before the first pass.  The arrays are checked first (a span that leaves the buffer refuses the call
+ * with `ok` untouched), then everything is uploaded to the default device, the device form runs on a stream of its own, the
+ * verdicts come back and every buffer is freed on every path.  The call has waited for its kernels, so it takes their report
+ * itself, like every host-pointer call */
+int ed25519_verify_scattered(uint8_t *ok, const uint8_t *data, size_t data_len, const uint32_t *sig_off, const uint32_t *pub_off,
+                             const uint32_t *msg_off, const uint32_t *msg_len, size_t n)
+{
+    struct call c;
+    const uint32_t *host[4] = { sig_off, pub_off, msg_off, msg_len };
+    uint32_t *d_idx[4] = { NULL, NULL, NULL, NULL };
+    uint8_t *d_data = NULL, *d_ok = NULL;
+    hipStream_t st = NULL;
+    int rc = scattered_open(ok, data, data_len, sig_off, pub_off, msg_off, msg_len, n);
+    if (rc) return rc < 0 ? rc : 0;
+    if (!edk_scatter_spans_inside(data_len, sig_off, pub_off, msg_off, msg_len, n)) return -(int)hipErrorInvalidValue;
+    if ((rc = enter(&c, -1))) return rc;
+    TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    TRY(hipMalloc((void **)&d_data, data_len ? data_len : 1));
+    TRY(hipMalloc((void **)&d_ok, n));
+    TRY(hipMemcpyAsync(d_data, data, data_len, hipMemcpyHostToDevice, st));
+    for (int k = 0; k < 4; k++) {
+        TRY(hipMalloc((void **)&d_idx[k], n * sizeof(uint32_t)));
+        TRY(hipMemcpyAsync(d_idx[k], host[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+    {
+        const edk_verify_src src = verify_src_scattered(d_data, data_len, d_idx[0], d_idx[1], d_idx[2], d_idx[3]);
+        if ((rc = verify_on(c.e, d_ok, &src, n, st, NULL, 0))) goto out;
+    }
+    TRY(hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st));
+    TRY(hipStreamSynchronize(st));
+    rc = take_async_error(c.e);
+out:
+    if (st) { HIP_NOTE(hipStreamSynchronize(st)); HIP_NOTE(hipStreamDestroy(st)); }
+    for (int k = 0; k < 4; k++) if (d_idx[k]) HIP_NOTE(hipFree(d_idx[k]));
+    if (d_ok) HIP_NOTE(hipFree(d_ok));
+    if (d_data) HIP_NOTE(hipFree(d_data));
+    return leave_with(&c, rc);
 }
 
 /* The class bytes of a key set's own keys, where they lie.  No engine is asked for - the kernel reads no table and takes no workspace,

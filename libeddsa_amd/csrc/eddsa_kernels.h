@@ -62,6 +62,9 @@ typedef struct edk_verify_ws {
                          the kernels behind it read `pubs` there with stride 32 */
   const uint32_t* comb; /* the engine's comb of the base point in its global layout (edk_init_tables), not owned: keyed passes over a comb
                          key set (edk_verify_src.ks_comb) read S*B through it */
+  uint8_t* gsigs;     /* capacity * 64, or NULL: scattered passes (edk_verify_src.sc_data): the items' signatures, gathered by
+                         k_scatter_challenge (edk_scatter.h) beside their keys (keybytes) and digests (domdig).  Allocated by the first
+                         scattered pass a slot serves (eddsa_amd.c: verify_on) and freed with the slot: no other call pays for it */
 } edk_verify_ws;
 
 /* where the items of a verify pass live: item i has its signature at sigs + i * sig_stride, its key
@@ -101,6 +104,14 @@ typedef struct {
   const uint32_t* ks_comb;   /* != NULL: the key set is a COMB key set (eddsa_amd_keyset_create_comb) - KEYSET_COMB_WORDS words per key,
                                 [key][row][m - 1] = m * 2^(2 COMB_W row) * (-A); the pass takes the comb route (kernels.hip: verify_route_of).
                                 NULL for plain sets */
+  /* sc_data != NULL (ed25519_verify_scattered*): a SCATTERED pass - item i's signature, key and message lie at sc_sig_off[i],
+     sc_pub_off[i] and sc_msg_off[i] (sc_msg_len[i] bytes) of sc_data[0 .. sc_data_len), four packed uint32 arrays in HBM that
+     src_at advances with the chunk; sc_data is the same for every chunk.  Host side only: verify_on (eddsa_amd.c) runs
+     edk_scatter_challenge (edk_scatter.h) in front of edk_verify and points sigs, pubs and msgs at what it left in the workspace,
+     so that edk_verify sees the digest pass (`digest` set, strides 64 / 32 / 64) and never reads these fields */
+  const uint8_t* sc_data;
+  size_t sc_data_len;
+  const uint32_t *sc_sig_off, *sc_pub_off, *sc_msg_off, *sc_msg_len;
 } edk_verify_src;
 
 /* What the kernels take BY VALUE: the nine fields of edk_verify_src that lanes read, 72 bytes as before the flag existed.  The flag stays

@@ -34,6 +34,7 @@
 #include "edk_signer.h"
 #include "edk_classify.h"
 #include "edk_muladd.h"
+#include "edk_scatter.h"
 
 #ifndef CHUNK_MAX                     /* (tests/fake_hip builds one variant with tiny passes: tests/c/multi_passes.c) */
 #define CHUNK_MAX ((size_t)1 << 20)   /* verify items per workspace pass: 1.6 GB of HBM workspace */
@@ -227,6 +228,18 @@ static inline edk_verify_src verify_src_records(const uint8_t *records, size_t s
 {
     const edk_verify_src src = { .sigs = records + sig_off, .pubs = records + pub_off, .msgs = records + msg_off, .msg_len = msg_len,
                                  .sig_stride = stride, .pub_stride = stride, .msg_stride = stride };
+    return src;
+}
+
+/* items by byte offsets into one buffer (include/eddsa_amd.h: ed25519_verify_scattered*): the pass runs as a digest pass over packed
+ * arrays of the workspace slot, which verify_on (eddsa_amd.c) fills in per chunk behind edk_scatter_challenge - hence the digest
+ * form's strides and no buffers here */
+static inline edk_verify_src verify_src_scattered(const uint8_t *data, size_t data_len, const uint32_t *sig_off, const uint32_t *pub_off,
+                                                  const uint32_t *msg_off, const uint32_t *msg_len)
+{
+    const edk_verify_src src = { .msg_len = EDK_DOM_DIGEST_BYTES, .sig_stride = 64, .pub_stride = 32, .msg_stride = EDK_DOM_DIGEST_BYTES,
+                                 .digest = 1, .sc_data = data, .sc_data_len = data_len, .sc_sig_off = sig_off, .sc_pub_off = pub_off,
+                                 .sc_msg_off = msg_off, .sc_msg_len = msg_len };
     return src;
 }
 

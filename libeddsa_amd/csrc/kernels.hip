@@ -22,11 +22,13 @@
 //   k_signer_build, k_sign_keyed_*            signer sets (signer_kernels.h): the secret scalar, the prefix and A by key index
 //   k_point_classify                          point classification (classify_kernels.h): curve, canonical, small and prime order
 //   k_point_muladd_prepare, _finish           [m]P + [a]B (muladd_kernels.h): set-up and encoding around k_verify_main
+//   k_scatter_challenge, k_scatter_len_*      ed25519_verify_scattered (scatter_kernels.h): gather and hash in front of a digest pass
 #include "eddsa_kernels.h"
 #include "edk_keyed.h"
 #include "edk_signer.h"
 #include "edk_classify.h"
 #include "edk_muladd.h"
+#include "edk_scatter.h"
 #include "edk_checked.h"
 #include "kernel_io.h"
 #include "lanes.h"
@@ -131,11 +133,14 @@ __global__ void __launch_bounds__(64) k_init_comb_image(uint32_t* img, const uin
 constexpr int LEN_BINS = EDK_LEN_BINS;           // key = min(length / 128, LEN_BINS - 1), counted from the long end
 constexpr size_t MSG_ORDER_MIN_N = (size_t)1 << 12;
 
+ED_DEV uint32_t len_bin_of(size_t len) {
+  const size_t blocks = len >> 7;
+  return (uint32_t)(LEN_BINS - 1) - (uint32_t)(blocks < (size_t)LEN_BINS - 1 ? blocks : (size_t)LEN_BINS - 1);
+}
 ED_DEV uint32_t len_bin(const uint64_t* off, const uint64_t* end, size_t item) {
   uint64_t lo, hi;
   ragged_span(lo, hi, off, end, item);                         // (the clamped span: what the hashing kernels will read)
-  const size_t blocks = (size_t)(hi - lo) >> 7;
-  return (uint32_t)(LEN_BINS - 1) - (uint32_t)(blocks < (size_t)LEN_BINS - 1 ? blocks : (size_t)LEN_BINS - 1);
+  return len_bin_of((size_t)(hi - lo));
 }
 
 // bins[b] += items of bin b (per block in LDS first: a pass whose messages all have one length would otherwise send 2^20 atomics to one word)
@@ -1267,6 +1272,7 @@ k_verify_main_sums_quad(uint8_t* ok, const uint32_t* hdigits, const uint32_t* su
 #include "signer_kernels.h"  // signer sets: likewise, beside the sign kernels
 #include "classify_kernels.h"  // point classification: one kernel, no workspace
 #include "muladd_kernels.h"  // [m]P + [a]B: a prepare and a finish kernel around k_verify_main
+#include "scatter_kernels.h"  // items by byte offsets: one gathering and hashing kernel in front of a digest pass
 
 // =============================================================================================
 // launchers (host side of this translation unit)
@@ -1815,6 +1821,33 @@ hipError_t edk_point_muladd(uint8_t* out, const uint8_t* points, const uint8_t* 
   EDK_LAUNCH(k_verify_main, dim3(blocks), dim3(BLOCK), MAIN_LDS_RESERVE, stream, ws->digits, ws->table, base16, ws->acc);
   EDK_LAUNCH(k_point_muladd_finish, dim3(f.grid), dim3(BLOCK), 0, stream, out, ws->acc, ws->flags, n, f.k);
   return hipSuccess;
+}
+
+// the front of a scattered pass (edk_scatter.h): the order of length from MSG_ORDER_MIN_N items on, as msg_order builds it from an
+// offset table, then one lane per item.  Asynchronous on `stream`
+hipError_t edk_scatter_challenge(const uint8_t* data, size_t data_len, const uint32_t* sig_off, const uint32_t* pub_off,
+                                 const uint32_t* msg_off, const uint32_t* msg_len, size_t n, const edk_verify_ws* ws, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (n > ws->capacity || !ws->gsigs || (uint64_t)data_len > (uint64_t)UINT32_MAX) return hipErrorInvalidValue;
+  const scatter_spans sp = { sig_off, pub_off, msg_off, msg_len, (uint64_t)data_len };
+  const unsigned blocks = blocks_of(n);
+  const uint32_t* perm = nullptr;
+  if (n >= MSG_ORDER_MIN_N) {
+    EDK_DO(hipMemsetAsync(ws->lenbins, 0, (size_t)LEN_BINS * sizeof(uint32_t), stream));
+    EDK_LAUNCH(k_scatter_len_count, dim3(blocks), dim3(BLOCK), 0, stream, ws->lenbins, sp, n);
+    EDK_LAUNCH(k_len_starts, dim3(1), dim3(BLOCK), 0, stream, ws->lenbins);
+    EDK_LAUNCH(k_scatter_len_place, dim3(blocks), dim3(BLOCK), 0, stream, ws->perm, ws->lenbins, sp, n);
+    perm = ws->perm;
+  }
+  EDK_LAUNCH(k_scatter_challenge, dim3(blocks), dim3(BLOCK), 0, stream, data, sp, n, ws->gsigs, ws->keybytes, ws->domdig, perm);
+  return hipSuccess;
+}
+
+int edk_scatter_spans_inside(size_t data_len, const uint32_t* sig_off, const uint32_t* pub_off, const uint32_t* msg_off,
+                             const uint32_t* msg_len, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (!scatter_item_inside(sig_off[i], pub_off[i], msg_off[i], msg_len[i], (uint64_t)data_len)) return 0;
+  return 1;
 }
 
 }  // extern "C"
